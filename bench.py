@@ -1,21 +1,29 @@
 #!/usr/bin/env python
 """Benchmark of the CLSR training step on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 One "step" = one pass of the hot path (forward, losses, backward, per-tensor clip, Adam incl.
 the dense embedding-table sweeps, BN moving statistics) over one synthetic Taobao-shaped batch
 (BASELINE.json configs[1]: batch 4096 positives x (1+4) rows, seq_len 50, emb_dim 40), inputs
 already resident in HBM.  Rank 0 prints ONE JSON line:
-metric = train interactions/sec (interaction = one positive train line).
+metric = train interactions/sec (interaction = one positive train line);
+ms_per_step = milliseconds of one timed step.
+
+A plain run sets up, runs 2 + W untimed steps, times exactly K steps and prints the line; nothing else.
+--dump-outputs DIR: after the timed steps, rank 0 writes what the last timed step handed its caller
+(every array of the step's result, the loss terms) as DIR/<name>.npy (float32; loss terms float64); an
+array of more than DUMP_SAMPLE elements is written as a fixed, seeded sample of that many.  The inputs
+(synthetic feed, initial weights) are seeded: the same arguments give the same inputs on every run.
 
 N > 1: one process per GPU (torch.distributed, backend nccl == RCCL), weak scaling (every rank
-owns its own 4096-positive batch); `python bench.py --gpus N` re-executes itself under
-torch.distributed.run, and the same file is the per-rank program when the driver launches it that way.
+owns its own 4096-positive batch); `python bench.py --gpus N` starts itself under
+torch.distributed.run as a child process, and the same file is the per-rank program when the driver
+launches it that way.
 The gradient exchange (dense all-reduce or sparse touched-row exchange per table, see clsr_amd/dp.py)
 overlaps the tail of the backward pass; DP steps are launched eagerly.
 
-Extra objects on the line:
+Extra objects on the line, measured only with --full (each after the headline's timed steps):
   roofline        the embedding-history gather (north-star kernel; HBM bound): algorithmic bytes per
                   launch / average launch duration measured here with HIP events, on the HBM-resident
                   100M-item catalogue table (N = 1); the cache-resident figure of the benchmarked config is
@@ -26,6 +34,7 @@ Extra objects on the line:
                   attention activations + bf16 MFMA, fp32 accumulation / statistics / optimiser).
   extra_workloads BASELINE configs[2] (kuaishou) and configs[4] (catalogue100m, single GPU), and the
                   reference-exact clip mode (history replication, `--exact-clip` makes it the headline).
+--no-cpu-baseline / --no-catalogue / --no-extra leave parts of that out of a --full run.
 
 Other workloads: --config kuaishou (configs[2]) | catalogue100m (configs[4], lazy Adam).
 Experiment switches (environment): CLSR_FORCE_DP=1 (DP code path with one rank), CLSR_SPARSE_TABLES=auto|all|none,
@@ -177,6 +186,7 @@ class Workload(object):
                                    seed=20220425 + rank, ids="uniform" if big else "zipf")
         self.f = self.net.upload(self.feed, True)
         self.stepper = None
+        self.result = None      # what the step hands its caller (CLSRNet.train_step: the forward's arrays; DP: nothing)
         self.torch = torch
 
     def describe(self):
@@ -194,7 +204,7 @@ class Workload(object):
 
     def step(self):
         if self.stepper is None:
-            self.net.train_step(self.f)
+            self.result = self.net.train_step(self.f)
         else:
             self.stepper.train_step(self.f)
 
@@ -216,7 +226,7 @@ class Workload(object):
             run = self.step
         elif self.stepper is None:
             ops.graph_begin()
-            self.net.train_step(self.f)
+            self.result = self.net.train_step(self.f)      # (its arrays are the buffers every replay writes)
             g = ops.graph_end()
             run = lambda: ops.graph_launch(g)
         else:
@@ -260,7 +270,39 @@ class Workload(object):
         # the blocks stay with torch's caching allocator (the next workload reuses them): memory handed back to the
         # driver is unmapped in the background and perturbs what is timed right after
         self.torch.cuda.synchronize()
-        self.net = self.f = self.stepper = None
+        self.net = self.f = self.stepper = self.result = None
+
+
+DUMP_SAMPLE = 1 << 19              # elements written of a larger output array (a fixed, seeded sample)
+DUMP_BUDGET = 64 * 1000 * 1000     # bytes --dump-outputs may write in all
+
+
+def dump_outputs(path, result, losses):
+    """--dump-outputs: the arrays the last timed step handed its caller -> path/<name>.npy.  ``result`` = the step's return
+    value (dict of device tensors; None for the data-parallel stepper), ``losses`` = the host copy of the loss terms (data,
+    regular, contrastive, discrepancy), written as float64.  The arrays are written as float32; one of more than
+    DUMP_SAMPLE elements as its elements at DUMP_SAMPLE sorted positions drawn by a generator seeded with the array's name,
+    i.e. the same positions on every run and every build."""
+    import zlib
+
+    import torch
+
+    arrays = {"losses": np.asarray(losses, dtype=np.float64)}
+    for name, t in sorted((result or {}).items()):
+        if not isinstance(t, torch.Tensor):
+            continue
+        flat, shape = t.detach().reshape(-1), tuple(t.shape)
+        if flat.numel() > DUMP_SAMPLE:
+            idx = np.sort(np.random.default_rng(zlib.crc32(name.encode())).choice(flat.numel(), DUMP_SAMPLE, replace=False))
+            flat, shape = flat[torch.from_numpy(idx).to(flat.device)], (DUMP_SAMPLE,)
+        arrays[name] = flat.float().cpu().numpy().reshape(shape)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_BUDGET:
+        raise RuntimeError("--dump-outputs: %d bytes exceed the %d-byte budget" % (total, DUMP_BUDGET))
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    log("dumped %d arrays (%.1f MB) to %s" % (len(arrays), total / 1e6, path))
 
 
 NSETS = 3      # id sets the isolated kernel timings rotate through: the touched working set (>= 3 x 184 MB at the catalogue)
@@ -521,10 +563,15 @@ def main():
     ap.add_argument("--graph", action="store_true",
                     help="replay the step as ONE captured hipGraph instead of launching it eagerly")
     ap.add_argument("--no-graph", action="store_true", help="(default now; kept for old command lines)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure the rooflines, precision_modes, extra_workloads, the catalogue "
+                         "and the CPU baseline (off: the run times the headline's steps and prints the line, nothing else)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the arrays the last timed step returned (+ its loss terms) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip cpu_baseline")
     ap.add_argument("--no-catalogue", action="store_true",
-                    help="skip the HBM-resident (100M-item catalogue) measurements (gather roofline + configs[4] step)")
-    ap.add_argument("--no-extra", action="store_true", help="skip extra_workloads / precision_modes")
+                    help="(--full) skip the HBM-resident (100M-item catalogue) measurements (gather roofline + configs[4] step)")
+    ap.add_argument("--no-extra", action="store_true", help="(--full) skip extra_workloads / precision_modes")
     ap.add_argument("--cpu-seconds", type=float, default=25.0)
     ap.add_argument("--cpu-warmup", type=int, default=1)
     ap.add_argument("--cpu-steps", type=int, default=None)
@@ -550,7 +597,7 @@ def main():
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
-        # plain `python bench.py --gpus N`: re-exec under torch.distributed.run (one process per GPU, RCCL);
+        # plain `python bench.py --gpus N`: run under torch.distributed.run as a child (one process per GPU, RCCL);
         # rank 0 of that job prints the one JSON line
         have = torch.cuda.device_count()
         if have < args.gpus:
@@ -563,7 +610,10 @@ def main():
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(args.gpus),
                "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
         sys.stdout.flush()
-        os.execv(sys.executable, cmd)
+        import subprocess
+
+        rc = subprocess.call(cmd)
+        raise SystemExit(rc if rc >= 0 else 128 - rc)      # (killed by signal s: the shell's 128 + s)
     if args.gpus > 1 and world != args.gpus:
         raise SystemExit("--gpus %d but WORLD_SIZE=%d" % (args.gpus, world))
     # CLSR_BENCH_TRANSPORT=staged (test rig: tests/test_bench_ranks_gpu.py): the ranks of the job share ONE device and their
@@ -634,25 +684,27 @@ def main():
         ms = dt * 1e3 / args.steps
         value = world * P * args.steps / dt
         log("timed %d steps: %.3f ms/step" % (args.steps, ms))
+        if args.dump_outputs and rank == 0:
+            # (before anything of --full: the isolated kernel timings below write into the step's own buffers)
+            dump_outputs(args.dump_outputs, wl.result, host_losses[:4])
 
-        # ---- rooflines of two kernels, measured live with HIP events on this stream
-        B, Hn = P * G, P
-        D = cfg["Di"] + cfg["Dc"]
-        roof = gather_roofline(net, f, cfg, G, feed, big)
-        # PMC pass committed in profiles/r02_gather_hist_fwd_pmc_hbm_traffic.csv (same shape): WRITE_SIZE
-        # 33.3 MB + 2 x FETCH_SIZE 12.5 MB (gfx950 wide-load correction); reads of the 8 MB tables hit cache
-        roof.update(traffic=213.5e6 if big else 59.75e6, traffic_source="counters in KiB; profiles/r06_gather_pmc_{WRITE,FETCH}_SIZE.csv (rotating id sets; first 23 dispatches: this config; last 23: the catalogue)",
-                    note=("tables (%.1f MB) are L2/Infinity-Cache resident at this config; the HBM claim needs the "
-                          "100M-item config" % ((cfg["Vi"] * cfg["Di"] + cfg["Vc"] * cfg["Dc"]) * 4 / 1e6))
-                    if not big else "38 GB item table, uniform ids: every row read is an HBM read")
-        roof_mfma, roof_bwd = None, None
-        if args.model == "clsr":
-            roof_mfma = net.bench_att_layer0(f, time_kernel)
-            roof_bwd = net.bench_att_l1_bwd(f, time_kernel) if hasattr(net, "bench_att_l1_bwd") else None
+        roof, roof_mfma, roof_bwd = None, None, None
+        if args.full:
+            # ---- rooflines of two kernels, measured live with HIP events on this stream
+            roof = gather_roofline(net, f, cfg, G, feed, big)
+            # PMC pass committed in profiles/r02_gather_hist_fwd_pmc_hbm_traffic.csv (same shape): WRITE_SIZE
+            # 33.3 MB + 2 x FETCH_SIZE 12.5 MB (gfx950 wide-load correction); reads of the 8 MB tables hit cache
+            roof.update(traffic=213.5e6 if big else 59.75e6, traffic_source="counters in KiB; profiles/r06_gather_pmc_{WRITE,FETCH}_SIZE.csv (rotating id sets; first 23 dispatches: this config; last 23: the catalogue)",
+                        note=("tables (%.1f MB) are L2/Infinity-Cache resident at this config; the HBM claim needs the "
+                              "100M-item config" % ((cfg["Vi"] * cfg["Di"] + cfg["Vc"] * cfg["Dc"]) * 4 / 1e6))
+                        if not big else "38 GB item table, uniform ids: every row read is an HBM read")
+            if args.model == "clsr":
+                roof_mfma = net.bench_att_layer0(f, time_kernel)
+                roof_bwd = net.bench_att_l1_bwd(f, time_kernel) if hasattr(net, "bench_att_l1_bwd") else None
         products_note = net.precision_note() if args.model == "clsr" else None
 
         single = world == 1 and dist is None and args.model == "clsr" and args.config == "taobao"
-        if single and not args.no_extra:
+        if args.full and single and not args.no_extra:
             # ---- the other precision mode of the same workload (named secondary object; `dtype` stays the headline's)
             for other, td in (("bf16", "fp32"), ("bf16", "bf16"), ("fp32x3", "fp32"), ("fp32", "fp32")):
                 if other == args.precision and td == args.table_dtype:
@@ -710,7 +762,7 @@ def main():
                               ms_per_step=round(d6 * 100.0, 4), interactions_per_s=round(w6.P * 10 / d6, 1), steps=10, regions_ms=w6.reps_ms))
             log("%s lengths: %.3f ms/step" % (other_len, d6 * 100.0))
             w6.free()
-        if world == 1 and dist is None and not args.no_catalogue and not big:
+        if args.full and world == 1 and dist is None and not args.no_catalogue and not big:
             # BASELINE configs[4] on one GPU: 100M items x 96 floats (38 GB, uniform ids: no cache reuse, every row
             # read is an HBM read) -- the HBM claim of the gather kernel is made HERE (at configs[1]
             # the 8 MB of tables sit in the L2 / Infinity Cache), and the whole step is timed on the same net
@@ -762,23 +814,24 @@ def main():
         # the measured copy rate of this device next to the 8 TB/s datasheet figure (1 GiB device-to-device
         # copy: 1 GiB read + 1 GiB written per launch)
         copy_peak = None
-        try:
-            from clsr_amd import ops as _ops
+        if args.full:
+            try:
+                from clsr_amd import ops as _ops
 
-            # the repo's own 16-byte copy kernel (csrc/optim.hip: clsr_copy_words, non-temporal, 4 words in flight per
-            # lane, one pass per lane) over 4 GiB -- past the 256 MiB Infinity Cache; swept in scripts/copy_sweep.py:
-            # 5.0-5.4 TB/s at 1 GiB, 6.1 TB/s at 4 GiB (a torch copy_ of 1 GiB: 5.2 TB/s, below the gather itself)
-            nb_ = 4 << 30
-            src_, dst_ = torch.empty(nb_ // 4, device="cuda"), torch.empty(nb_ // 4, device="cuda")
-            t_copy = time_kernel(lambda: _ops.call("clsr_copy_words", dst_, src_.data_ptr(), nb_), iters=10, warm=2)
-            copy_peak = round(2.0 * nb_ / t_copy / 1e9, 1)
-            for r_ in (roof, roof.get("cache_resident_at_benchmarked_config")):
-                if r_ is not None:
-                    r_["measured_copy_peak_GBps"] = copy_peak
-                    r_["frac_of_measured_copy_peak"] = round(r_["achieved"] / copy_peak, 4)
-            del src_, dst_
-        except RuntimeError:
-            pass
+                # the repo's own 16-byte copy kernel (csrc/optim.hip: clsr_copy_words, non-temporal, 4 words in flight per
+                # lane, one pass per lane) over 4 GiB -- past the 256 MiB Infinity Cache; swept in scripts/copy_sweep.py:
+                # 5.0-5.4 TB/s at 1 GiB, 6.1 TB/s at 4 GiB (a torch copy_ of 1 GiB: 5.2 TB/s, below the gather itself)
+                nb_ = 4 << 30
+                src_, dst_ = torch.empty(nb_ // 4, device="cuda"), torch.empty(nb_ // 4, device="cuda")
+                t_copy = time_kernel(lambda: _ops.call("clsr_copy_words", dst_, src_.data_ptr(), nb_), iters=10, warm=2)
+                copy_peak = round(2.0 * nb_ / t_copy / 1e9, 1)
+                for r_ in (roof, roof.get("cache_resident_at_benchmarked_config")):
+                    if r_ is not None:
+                        r_["measured_copy_peak_GBps"] = copy_peak
+                        r_["frac_of_measured_copy_peak"] = round(r_["achieved"] / copy_peak, 4)
+                del src_, dst_
+            except RuntimeError:
+                pass
         out = {
             "metric": "train interactions/sec @ batch %d seq_len %d" % (P, T), "value": round(value, 1),
             "unit": "interactions/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -810,6 +863,8 @@ def main():
             out["config"]["ms_per_step_by_rank"] = [round(t * 1e3 / args.steps, 4) for t in wl.rank_seconds]
             out["config"]["sparse_tables"] = getattr(wl.stepper, "last_sparse", None)
             out["config"]["sync_bn_statistics_through"] = getattr(wl.stepper, "stats_transport", None)
+        if roof is None:
+            del out["roofline"]
         if roof_mfma is None:
             del out["roofline_mfma"]
         if args.model == "clsr" and roof_bwd is not None:
@@ -820,7 +875,7 @@ def main():
             out["precision_modes"] = modes
         if extra:
             out["extra_workloads"] = extra
-        if world == 1 and not args.no_cpu_baseline and not big and args.model == "clsr":
+        if args.full and world == 1 and not args.no_cpu_baseline and not big and args.model == "clsr":
             out["cpu_baseline"] = cpu_baseline(cfg, seconds=args.cpu_seconds, warmup=args.cpu_warmup,
                                                steps=args.cpu_steps, P=args.cpu_P)
         print(json.dumps(out), flush=True)

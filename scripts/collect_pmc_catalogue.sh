@@ -17,7 +17,7 @@ for set in "FETCH_SIZE" "WRITE_SIZE" \
            "SQ_INSTS_MFMA SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_INSTS_VMEM"; do
   i=$((i+1))
   rm -rf /tmp/pc_$i
-  timeout 900 rocprofv3 --kernel-trace --pmc $set --kernel-include-regex "$re" --output-format csv -d /tmp/pc_$i -o p -- python $root/bench.py --config catalogue100m --no-cpu-baseline --no-catalogue --no-extra --steps 4 --warmup 2 > /tmp/pc_$i.log 2>&1
+  timeout 900 rocprofv3 --kernel-trace --pmc $set --kernel-include-regex "$re" --output-format csv -d /tmp/pc_$i -o p -- python $root/bench.py --full --config catalogue100m --no-cpu-baseline --no-catalogue --no-extra --steps 4 --warmup 2 > /tmp/pc_$i.log 2>&1
   f=$(find /tmp/pc_$i -name "*counter_collection.csv" | head -1)
   [ -n "$f" ] && files="$files $f" || tail -5 /tmp/pc_$i.log
 done

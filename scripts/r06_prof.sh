@@ -16,7 +16,7 @@ cd $root
 EMBED_SITES=item bash scripts/prof_embed.sh ${tag}_item | tail -12
 bash scripts/prof_embed.sh ${tag} | tail -4
 cd /tmp
-rm -rf /tmp/pb && timeout 900 rocprofv3 --kernel-trace --stats --output-format rocpd -d /tmp/pb -o bench -- python $root/bench.py --no-cpu-baseline > /tmp/pb.log 2>&1
+rm -rf /tmp/pb && timeout 900 rocprofv3 --kernel-trace --stats --output-format rocpd -d /tmp/pb -o bench -- python $root/bench.py --full --no-cpu-baseline > /tmp/pb.log 2>&1
 grep "^{\"metric" /tmp/pb.log | tail -1 > $out/${tag}_bench_line_traced.json
 f=$(find /tmp/pb -name "*.db" | head -1); [ -n "$f" ] && python $root/scripts/rocpd_stats.py $f > $out/${tag}_bench_kernel_stats.md
 head -12 $out/${tag}_bench_kernel_stats.md
