@@ -268,6 +268,7 @@ class DataParallel(object):
         tensors = [net.dense, net.dense_m, net.dense_v, net.adam_state]
         tensors += list(net.tables.values()) + list(net.tab_m.values()) + list(net.tab_v.values())
         tensors.append(net.bn_moving)
+        tensors = [t for t in tensors if t is not None]     # (optimisers with fewer than two slots allocate fewer)
         for t in tensors:
             dist.broadcast(t, src=0, group=self.group)
 

@@ -20,6 +20,7 @@ their sum is used; ``dedup_histories=False`` runs the reference's replicated com
 import math
 import contextlib
 import os
+import warnings
 from collections import OrderedDict
 
 import numpy as np
@@ -36,6 +37,29 @@ F32 = torch.float32
 
 def _pad4(n):
     return (n + 3) // 4 * 4
+
+
+# The reference's optimisers other than (lazy)Adam (base_model.py:249-279, TF 1.15 defaults; csrc/optim_tf.hip):
+# name -> (kernel code of clsr_dense_tf / clsr_tables_tf_multi / clsr_table_tf_rows, slots as (TF slot name, initial
+# value) in TF's order -- slot 1 lives in dense_m / tab_m, slot 2 in dense_v / tab_v).  They update the touched rows
+# of an embedding table only (IndexedSlices semantics of TF's sparse_apply_* ops).
+TF_OPTIMIZERS = {
+    "sgd": (0, ()), "gd": (0, ()), "pgd": (0, ()),
+    "adagrad": (1, (("accumulator", 0.1),)), "padagrad": (2, (("accumulator", 0.1),)),
+    "rmsprop": (3, (("rms", 1.0), ("momentum", 0.0))),
+    "adadelta": (4, (("accum", 0.0), ("accum_update", 0.0))),
+    "ftrl": (5, (("accum", 0.1), ("linear", 0.0))),
+}
+ADAM_OPTIMIZERS = ("adam", "lazyadam")
+
+
+def resolve_optimizer(name):
+    """hparams.optimizer -> the name this package trains with: an unknown name falls back to GradientDescent, as the
+    reference does (base_model.py:277-278), with a warning."""
+    if name in ADAM_OPTIMIZERS or name in TF_OPTIMIZERS:
+        return name
+    warnings.warn("unknown optimizer %r: training with GradientDescent ('gd'), as the reference does" % (name,))
+    return "gd"
 
 
 class _BN(object):
@@ -85,6 +109,12 @@ class CLSRNet(object):
             raise NotImplementedError("table_dtype='bf16' needs item / cate embedding dims that are multiples of 8")
         self._th = "_h" if self.table_bf16 else ""          # suffix of the table kernels' entry points
         self._check_supported()
+        self.optimizer = resolve_optimizer(hp.optimizer)
+        # non-Adam optimisers: kernel code + slots (TF_OPTIMIZERS); None for (lazy)Adam
+        self.tf_opt = TF_OPTIMIZERS.get(self.optimizer)
+        if self.table_bf16 and self.tf_opt is not None:
+            raise NotImplementedError("table_dtype='bf16' with optimizer=%r: bf16 embedding tables are trained with adam / "
+                                      "lazyadam only" % hp.optimizer)
         self.Di, self.Dc = hp.item_embedding_dim, hp.cate_embedding_dim
         self.D = self.Di + self.Dc
         self.enc_in = self.D       # leading columns of the history rows the recurrent encoders read
@@ -92,7 +122,7 @@ class CLSRNet(object):
         self.A0, self.A1 = hp.att_fcn_layer_sizes or (0, 0)    # (models without an attention MLP have none)
         self.L0, self.L1 = hp.layer_sizes
         self.G_train = hp.train_num_ngs + 1
-        self.lazy = 1 if hp.optimizer == "lazyadam" else 0
+        self.lazy = 1 if self.optimizer == "lazyadam" else 0
         self._build_params(seed)
         self._bufs = {}
         self._zero_specs = OrderedDict()
@@ -315,8 +345,6 @@ class CLSRNet(object):
             bad.append("cross regularisers must be 0 (no model of this family has cross-layer parameters)")
         if hp.loss != "softmax" or hp.method != "classification":
             bad.append("loss must be softmax / method classification")
-        if hp.optimizer not in ("adam", "lazyadam"):
-            bad.append("optimizer must be adam or lazyadam")
         if len(hp.att_fcn_layer_sizes) != 2 or len(hp.layer_sizes) != 2:
             bad.append("att_fcn_layer_sizes / layer_sizes must have two layers")
         if hp.contrastive_loss not in ("bpr", "triplet"):
@@ -432,8 +460,11 @@ class CLSRNet(object):
         self.n_dense = int(off[-1])
         self.dense = torch.zeros(self.n_dense, dtype=F32, device=dev)
         self.dense_grad = None     # a view of grad_flat (below): dense and table gradients travel in ONE collective
-        self.dense_m = torch.zeros_like(self.dense)
-        self.dense_v = torch.zeros_like(self.dense)
+        self.dense_m, self.dense_v = self._new_slots(self.dense.shape)
+        # one byte per dense tensor for the non-Adam updates: tensors the reference graph gives no gradient (TF's
+        # apply_gradients skips them) keep their values and slots.  None: every variable this net creates gets one (the
+        # graph variants that leave variables unused -- manual_alpha, predict_long_short=False -- do not create them)
+        self.dense_skip = None
         self.seg_off = torch.tensor(off, dtype=torch.int32, device=dev)
         # (dense regulariser: one workgroup per tensor -- 1 024 threads when a tensor is large: 128-wide encoders)
         self.dense_reg_threads = 1024 if max(sizes) >= 65536 else 0
@@ -483,8 +514,11 @@ class CLSRNet(object):
                         self.P[name] = t
                     self.tables[key] = t
                     self.tab_grad[key] = self.tab_grad_flat[goff[key]:goff[key] + t.numel()].view(t.shape)
-                    self.tab_m[key] = torch.zeros(t.shape, dtype=F32, device=dev)
-                    self.tab_v[key] = torch.zeros(t.shape, dtype=F32, device=dev)
+                    sm, sv = self._new_slots(t.shape)
+                    if sm is not None:
+                        self.tab_m[key] = sm
+                    if sv is not None:
+                        self.tab_v[key] = sv
                     self.tab_flags[key] = self.tab_flags_flat[foff[key]:foff[key] + shape[0]]
             else:
                 (_, _, _), o = next(it_dense)
@@ -509,6 +543,29 @@ class CLSRNet(object):
                 o += _pad4(bn.C)
         assert o == self.bn_moving.numel()
 
+    def _slot_inits(self):
+        """Initial values of slot 1 / slot 2 (None: the optimiser has no such slot)."""
+        if self.tf_opt is None:
+            return 0.0, 0.0
+        init = [v for _, v in self.tf_opt[1]]
+        return tuple(init[i] if i < len(init) else None for i in range(2))
+
+    def _new_slots(self, shape):
+        return tuple(None if v is None else torch.full(tuple(shape), v, dtype=F32, device=self.device)
+                     for v in self._slot_inits())
+
+    def _slot_names(self):
+        return [n for n, _ in self.tf_opt[1]] if self.tf_opt is not None else ["m", "v"]
+
+    def _reset_slots(self):
+        """Every slot back to its initial value and the step counter to 0 (a checkpoint without this optimiser's slots)."""
+        i1, i2 = self._slot_inits()
+        for t, v in [(self.dense_m, i1), (self.dense_v, i2)] + [(t, i1) for t in self.tab_m.values()] + \
+                [(t, i2) for t in self.tab_v.values()]:
+            if t is not None:
+                t.fill_(v)
+        self.adam_state[:4].copy_(torch.tensor([0.0, 1.0, 1.0, 0.0], dtype=torch.float64))
+
     def state_dict(self):
         """All variables under their TF names + BN moving stats + Adam slots (checkpoint payload).  Raises ``StepAborted``
         instead of handing out the state an aborted step left behind (check_abort)."""
@@ -519,6 +576,16 @@ class CLSRNet(object):
         for scope, bn in self.bn.items():
             sd[scope + "moving_mean"] = bn.moving_mean.cpu().clone()
             sd[scope + "moving_variance"] = bn.moving_var.cpu().clone()
+        if self.tf_opt is not None:
+            # __opt__/<optimizer>/dense_<slot>, __opt__/<optimizer>/<table>_<slot> (TF slot names), __opt__/state
+            pre = "__opt__/%s/" % self.optimizer
+            names = self._slot_names()
+            for i, (dense, tabs) in enumerate(((self.dense_m, self.tab_m), (self.dense_v, self.tab_v))[:len(names)]):
+                sd[pre + "dense_" + names[i]] = dense.cpu().clone()
+                for k in self.tables:
+                    sd[pre + "%s_%s" % (k, names[i])] = tabs[k].cpu().clone()
+            sd["__opt__/state"] = self.adam_state[:4].cpu().clone()
+            return sd
         sd["__adam__/dense_m"] = self.dense_m.cpu().clone()
         sd["__adam__/dense_v"] = self.dense_v.cpu().clone()
         for k in self.tables:
@@ -559,15 +626,34 @@ class CLSRNet(object):
                 bn.moving_var.copy_(torch.as_tensor(np.asarray(sd[scope + "moving_variance"]), dtype=F32))
             elif strict:
                 raise KeyError(scope + "moving_mean")
-        if "__adam__/dense_m" in sd:
+        pre = "__opt__/%s/" % self.optimizer
+        names = self._slot_names()
+        if self.tf_opt is None and "__adam__/dense_m" in sd:
             self.dense_m.copy_(torch.as_tensor(sd["__adam__/dense_m"]))
             self.dense_v.copy_(torch.as_tensor(sd["__adam__/dense_v"]))
             for k in self.tables:
                 self.tab_m[k].copy_(torch.as_tensor(sd["__adam__/%s_m" % k]))
                 self.tab_v[k].copy_(torch.as_tensor(sd["__adam__/%s_v" % k]))
             self.adam_state[:4].copy_(torch.as_tensor(sd["__adam__/state"])[:4])
-            if self._aborted or float(self.adam_state[4].item()) != 0.0:
-                self._reset_after_abort()       # a full checkpoint is the recovery path of an aborted step
+        elif self.tf_opt is not None and "__opt__/state" in sd and all(pre + "dense_" + n in sd for n in names):
+            for i, (dense, tabs) in enumerate(((self.dense_m, self.tab_m), (self.dense_v, self.tab_v))[:len(names)]):
+                dense.copy_(torch.as_tensor(sd[pre + "dense_" + names[i]]))
+                for k in self.tables:
+                    tabs[k].copy_(torch.as_tensor(sd[pre + "%s_%s" % (k, names[i])]))
+            self.adam_state[:4].copy_(torch.as_tensor(sd["__opt__/state"])[:4])
+        elif self.tf_opt is not None or any(k.startswith("__opt__/") for k in sd):
+            # no slots of this net's optimiser: the variables are loaded, the slots start from their initial values
+            # ((lazy)Adam nets keep their slots when the checkpoint holds none at all, as they always did)
+            if any(k.startswith(("__adam__/", "__opt__/")) for k in sd):
+                warnings.warn("checkpoint holds the slots of another optimizer: variables loaded, the %r slots start from "
+                              "their initial values" % self.optimizer)
+            else:
+                warnings.warn("checkpoint holds no optimizer slots: variables loaded, the %r slots start from their "
+                              "initial values" % self.optimizer)
+            self._reset_slots()
+            return
+        if self._aborted or float(self.adam_state[4].item()) != 0.0:
+            self._reset_after_abort()       # a full checkpoint is the recovery path of an aborted step
 
     # ------------------------------------------------------------------ stream fork / join
     class _Branch(object):
@@ -2744,9 +2830,27 @@ class CLSRNet(object):
         tb, ss = self.tables, self.sumsq_tab
         V, C = tb[key].shape
         pt = tb[partner] if partner else None
-        return (tb[key].data_ptr(), ops._ptr(pt), self.tab_grad[key].data_ptr(), self.tab_m[key].data_ptr(),
-                self.tab_v[key].data_ptr(), self.tab_flags[key].data_ptr(), ss[slot:].data_ptr(), ops._ptr(dloss),
+        return (tb[key].data_ptr(), ops._ptr(pt), self.tab_grad[key].data_ptr(), ops._ptr(self.tab_m.get(key)),
+                ops._ptr(self.tab_v.get(key)), self.tab_flags[key].data_ptr(), ss[slot:].data_ptr(), ops._ptr(dloss),
                 ss[base:].data_ptr(), V, C, nsum, 2, dscale, dloss_scale, 0)
+
+    def _tables_update_multi(self, rows, clip):
+        """Optimiser update of the small tables of ``rows`` (_sweep_row tuples) in one launch."""
+        if self.tf_opt is not None:     # touched rows only (IndexedSlices), flags cleared by the launch
+            ops.multi("clsr_tables_tf_multi", ops.TableDesc, rows, self.tf_opt[0], clip, self.adam_state,
+                      float(self.hp.learning_rate))
+        else:
+            ops.multi("clsr_tables_adam_multi" + self._th, ops.TableDesc, rows, clip, self.adam_state, 0.9, 0.999, 1e-8,
+                      self.lazy)
+
+    def _dense_update(self, clip):
+        """Optimiser update of the flat dense buffer; clears the dense gradients."""
+        if self.tf_opt is not None:
+            call("clsr_dense_tf", self.tf_opt[0], self.dense, self.dense_grad, self.dense_m, self.dense_v, self.seg_of,
+                 self.dense_skip, self.dense_sumsq, clip, self.adam_state, float(self.hp.learning_rate), self.n_dense)
+        else:
+            call("clsr_dense_adam", self.dense, self.dense_grad, self.dense_m, self.dense_v, self.seg_of,
+                 self.dense_sumsq, clip, self.adam_state, 0.9, 0.999, 1e-8, self.n_dense)
 
     def _update_user_tables_early(self):
         """Regulariser (+ discrepancy term) and Adam of the two user tables as soon as their gradients are final -- the row
@@ -2762,7 +2866,7 @@ class CLSRNet(object):
         clip = float(hp.max_grad_norm) if hp.is_clip_norm else 0.0
         ops.multi("clsr_tables_reg_multi" + self._th, ops.TableDesc, rows, float(hp.embed_l2), float(hp.embed_l1), self.ucount,
                   self.losses[1:])
-        ops.multi("clsr_tables_adam_multi" + self._th, ops.TableDesc, rows, clip, self.adam_state, 0.9, 0.999, 1e-8, self.lazy)
+        self._tables_update_multi(rows, clip)
         self._updated_early = {sp[0] for sp in spec}
 
     def _apply_updates(self):
@@ -2802,8 +2906,7 @@ class CLSRNet(object):
                  float(hp.layer_l2), float(hp.layer_l1), self.dense_sumsq, self.losses[1:],
                  None if (self.capture_grads or tick_early) else self.adam_state, lr, 0.9, 0.999, self.dense_reg_threads)
             if not self.capture_grads:
-                call("clsr_dense_adam", self.dense, self.dense_grad, self.dense_m, self.dense_v, self.seg_of,
-                     self.dense_sumsq, clip, self.adam_state, 0.9, 0.999, 1e-8, self.n_dense)
+                self._dense_update(clip)
         lists, self._early_lists = self._early_lists, None
         if lists is None:
             lists = {k: self._involved_list(k) for k, t in tb.items() if t.numel() > self.rowlist_min_elems}
@@ -2818,9 +2921,7 @@ class CLSRNet(object):
                 call("clsr_table_reg_rows" + self._th, tb[key], pt, ids, count, cap, C, l2e, l1e, dscale, dloss_scale,
                      self.ucount if partner else None, tg[key], ss[slot:], self.losses[1:], dloss)
             else:   # small tables: one launch sweeps all of them (blockIdx.y = table)
-                sweep.append((tb[key].data_ptr(), ops._ptr(pt), tg[key].data_ptr(), self.tab_m[key].data_ptr(),
-                              self.tab_v[key].data_ptr(), fl[key].data_ptr(), ss[slot:].data_ptr(), ops._ptr(dloss),
-                              ss[base:].data_ptr(), V, C, nsum, 2, dscale, dloss_scale, 0))
+                sweep.append(self._sweep_row(key, partner, slot, dscale, dloss_scale, dloss, base, nsum))
         if sweep:
             ops.multi("clsr_tables_reg_multi" + self._th, ops.TableDesc, sweep, l2e, l1e, self.ucount, self.losses[1:])
         if self.capture_grads:  # test hook: pre-clip gradients (regularisers included) + squared norms
@@ -2828,14 +2929,17 @@ class CLSRNet(object):
                                  tables={k: g.detach().clone() for k, g in tg.items()},
                                  dense_sumsq=self.dense_sumsq.clone(), table_sumsq=ss.clone())
             call("clsr_adam_tick", self.adam_state, float(hp.learning_rate), 0.9, 0.999)
-            call("clsr_dense_adam", self.dense, self.dense_grad, self.dense_m, self.dense_v, self.seg_of,
-                 self.dense_sumsq, clip, self.adam_state, 0.9, 0.999, 1e-8, self.n_dense)
+            self._dense_update(clip)
         if not tick_early:
             self._join()          # the Adam clock ticked on @aux: the table updates below read it
         rest = []
         for key, partner, slot, dscale, dloss_scale, dloss, base, nsum in spec:
             V, C = tb[key].shape
-            if key in lists and self.lazy:
+            if key in lists and self.tf_opt is not None:     # touched rows only, as lazy Adam
+                ids, count, cap = lists[key]
+                call("clsr_table_tf_rows", self.tf_opt[0], tb[key], tg[key], self.tab_m.get(key), self.tab_v.get(key),
+                     fl[key], ids, count, cap, C, ss[base:], 2, nsum, clip, self.adam_state, lr)
+            elif key in lists and self.lazy:
                 ids, count, cap = lists[key]
                 call("clsr_table_adam_rows" + self._th, tb[key], tg[key], self.tab_m[key], self.tab_v[key], fl[key], ids, count,
                      cap, C, ss[base:], 2, nsum, clip, self.adam_state, 0.9, 0.999, 1e-8)
@@ -2845,9 +2949,7 @@ class CLSRNet(object):
             else:
                 rest.append(key)
         if rest:
-            ops.multi("clsr_tables_adam_multi" + self._th, ops.TableDesc, [r for r in sweep if r[0] in
-                                                                {tb[k].data_ptr() for k in rest}],
-                      clip, self.adam_state, 0.9, 0.999, 1e-8, self.lazy)
+            self._tables_update_multi([r for r in sweep if r[0] in {tb[k].data_ptr() for k in rest}], clip)
         if tick_early:
             self._join()          # the dense path (@aux): the next step reads the updated variables on this stream
 

@@ -52,8 +52,6 @@ class SeqNet(CLSRNet):
             bad.append("l1 / cross regularisers must be 0")
         if hp.loss != "softmax" or hp.method != "classification":
             bad.append("loss must be softmax / method classification")
-        if hp.optimizer not in ("adam", "lazyadam"):
-            bad.append("optimizer must be adam or lazyadam")
         if len(hp.layer_sizes) != 2:
             bad.append("layer_sizes must have two layers")
         D = hp.item_embedding_dim + hp.cate_embedding_dim

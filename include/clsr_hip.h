@@ -924,6 +924,26 @@ int clsr_tables_adam_multi(const clsr_table_desc* descs_host, int n, float clip_
                            float beta1, float beta2, float eps, int lazy, void* stream);
 int clsr_tables_adam_multi_h(const clsr_table_desc* descs_host, int n, float clip_norm, const double* adam_state,
                              float beta1, float beta2, float eps, int lazy, void* stream);
+/* ---- the reference's other optimisers (csrc/optim_tf.hip, base_model.py:249-279, TF 1.15 defaults):
+ *      opt 0 = GradientDescent (sgd, gd, pgd), 1 = Adagrad, 2 = ProximalAdagrad, 3 = RMSProp, 4 = Adadelta, 5 = Ftrl.
+ *      s1 / s2 are the optimiser's slots in TF's order (adagrad: accumulator; rmsprop: rms, momentum; adadelta: accum,
+ *      accum_update; ftrl: accum, linear) and may be NULL when it has fewer (clsr_tf_opt_slots).  g = grad * clip factor
+ *      of the variable's squared norm; lr = the learning rate; every kernel touches nothing while state[4] != 0 (the
+ *      abort flag of the step; state is the Adam state array, whose clock the caller advances as for Adam).  All clear
+ *      the gradients they consume. */
+int clsr_tf_opt_slots(int opt);          /* host query: number of slots of optimiser `opt` (negative: unknown) */
+/* flat dense update; skip (NULL or one byte per tensor): tensors without a gradient in the reference graph keep their
+ * values and slots */
+int clsr_dense_tf(int opt, float* param, float* grad, float* s1, float* s2, const int* seg_of, const unsigned char* skip,
+                  const double* sumsq, float clip_norm, const double* state, float lr, int n, void* stream);
+/* the flagged rows of up to four tables (desc.m / desc.v = slot 1 / slot 2, sumsq_adam / nsum / sumsq_stride = the clip
+ * norm pieces); clears the flags.  No LDS. */
+int clsr_tables_tf_multi(const clsr_table_desc* descs_host, int n, int opt, float clip_norm, const double* state,
+                         float lr, void* stream);
+/* the listed rows of one table (ids / count from clsr_flags_compact); clears their gradient rows and flags */
+int clsr_table_tf_rows(int opt, float* table, float* grad_table, float* s1, float* s2, unsigned char* flags,
+                       const int* ids, const int* count, int cap, int C, const double* sumsq, int sumsq_stride,
+                       int nsum, float clip_norm, const double* state, float lr, void* stream);
 
 /* ---- evaluation metrics on the device (csrc/metrics.hip): cal_metric / cal_weighted_metric of
  *      deeprec_utils.py:554-821 as SequentialBaseModel.run_eval / run_weighted_eval use them
