@@ -46,7 +46,7 @@ template <> __device__ __forceinline__ void af_store_piece<__bf16>(__bf16* dst, 
   __builtin_nontemporal_store(to_h(ld8f(src)), reinterpret_cast<bf16x8*>(dst));
 }
 
-template <int NZ, int NK, int NP, typename ST>      // NP = 0: fp32-input MFMAs; 1 / 2 / 3: bf16 pieces per operand (speed mode / x3 / x6 products)
+template <int NZ, int NK, int NP, typename ST>      // NP = 0: fp32-input MFMAs; 1 / 3: bf16 pieces per operand (speed mode / x6 products)
 __global__ void __launch_bounds__(256, (NK >= 8 && NP >= 2) ? 1 : 2) att_l0_fwd_kernel(AttL0FwdArgs s) {      // (K = 128 with two / three weight images: 110-151 KB of LDS, one workgroup per CU anyway)
   CLSR_CHAIN_PRIO();
   constexpr int PW = sizeof(ST) == 2 ? 8 : 4;      // values per 16-byte store piece
@@ -399,8 +399,8 @@ static int att_l0_fwd_any(const float* a, int lda, const float* q, int ldq, cons
   const int nz = af_class(A0), nk = af_class(Q);
 #define AF_GO(Z, K) \
   if (nz == Z && nk == K) \
-    return pieces == 3 ? att_l0_fwd_launch<Z, K, 3>(s, st) : pieces == 2 ? att_l0_fwd_launch<Z, K, 2>(s, st) \
-         : pieces == 1 ? att_l0_fwd_launch<Z, K, 1, __bf16>(s, st) : att_l0_fwd_launch<Z, K, 0>(s, st)
+    return pieces == 3 ? att_l0_fwd_launch<Z, K, 3>(s, st) : pieces == 1 ? att_l0_fwd_launch<Z, K, 1, __bf16>(s, st) \
+         : att_l0_fwd_launch<Z, K, 0>(s, st)
   AF_GO(3, 3); AF_GO(3, 5); AF_GO(5, 3); AF_GO(5, 5); AF_GO(3, 8); AF_GO(5, 8);
 #undef AF_GO
   return CLSR_OK;
@@ -411,14 +411,8 @@ extern "C" int clsr_att_l0_fwd(const float* a, int lda, const float* q, int ldq,
                                long Hn, int G, int T, int Q, int A0, void* stream) {
   return att_l0_fwd_any(a, lda, q, ldq, Wt, Kp, U, ldu, V, ldv, z0, ldz, stats, Hn, G, T, Q, A0, 0, stream);
 }
-// the same with the product as split-bf16 sums (see att_l0_fwd_kernel<.., X3>)
-extern "C" int clsr_att_l0_fwd_x3(const float* a, int lda, const float* q, int ldq, const float* Wt, int Kp,
-                                  const float* U, int ldu, const float* V, int ldv, float* z0, int ldz, double* stats,
-                                  long Hn, int G, int T, int Q, int A0, void* stream) {
-  return att_l0_fwd_any(a, lda, q, ldq, Wt, Kp, U, ldu, V, ldv, z0, ldz, stats, Hn, G, T, Q, A0, 2, stream);
-}
-// ... over three bf16 pieces per operand (2^-23 relative: the level of the fp32 fma chain; 60 bf16 MFMAs of ~20 cycles per
-// 16 x 80 tile instead of 100 fp32 MFMAs of 32)
+// the same with the product over three bf16 pieces per operand (2^-23 relative: the level of the fp32 fma chain; 60 bf16
+// MFMAs of ~20 cycles per 16 x 80 tile instead of 100 fp32 MFMAs of 32)
 extern "C" int clsr_att_l0_fwd_x6(const float* a, int lda, const float* q, int ldq, const float* Wt, int Kp,
                                   const float* U, int ldu, const float* V, int ldv, float* z0, int ldz, double* stats,
                                   long Hn, int G, int T, int Q, int A0, void* stream) {

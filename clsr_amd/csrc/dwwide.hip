@@ -244,7 +244,6 @@ static int dww_parts(long M, int K, int N) {
 extern "C" int clsr_pgemm_dw_wide_supported(long M, int K, int N) {
   return M >= 32768 && M < (1L << 31) && K >= 96 && N >= 96 && K % 4 == 0 && N % 4 == 0 && (long)K * N < (1L << 28);
 }
-extern "C" int clsr_pgemm_dw_wide_parts(long M, int K, int N) { return dww_parts(M, K, N); }
 extern "C" long clsr_pgemm_dw_wide_workspace_floats(long M, int K, int N) {
   return (long)dww_parts(M, K, N) * ((long)K * N + N);
 }

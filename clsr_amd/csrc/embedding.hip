@@ -289,86 +289,6 @@ extern "C" int clsr_scatter_add_rows(const float* src, int ld_src, int col0, con
   return CLSR_OK;
 }
 
-// Backward of the history gather + hist_mean / hist_recent:
-//   g[h,t,:] = dhist[h,t,:] + (t < len) * dmean[h,:] / len + recent(t) * drecent[h,:] / cnt
-//   item_grad[item_idx[h,t], :] += g[:Di] ; cate_grad[cate_idx[h,t], :] += g[Di:]
-// sumsq[0] / sumsq[1] receive sum(g^2) of the item / cate parts (clip norm of this site).
-__global__ void __launch_bounds__(256) gather_hist_bwd_kernel(
-    const float* __restrict__ dhist, const float* __restrict__ dmean,
-    const float* __restrict__ drecent, const int* __restrict__ item_idx,
-    const int* __restrict__ cate_idx, long idx_row_stride, const int* __restrict__ seq_len,
-    int len_stride, int Hn, int T, int Di, int Dc, int recent_k, float* __restrict__ item_grad,
-    float* __restrict__ cate_grad, double* __restrict__ sumsq) {
-  // Row 0 (padding / out-of-vocabulary id) receives the gradient of EVERY padded step: its slices are
-  // first summed per block in LDS (ds_add_f32) and reach the table as one atomic per column per block.
-  extern __shared__ float row0_acc[];  // [D]
-  const int D = Di + Dc;
-  for (int d = threadIdx.x; d < D; d += blockDim.x) row0_acc[d] = 0.f;
-  __syncthreads();
-  const long total = (long)Hn * T * D;
-  float s_item = 0.f, s_cate = 0.f;
-  for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < total;
-       e += (long)gridDim.x * blockDim.x) {
-    const int d = (int)(e % D);
-    const long ht = e / D;
-    const int t = (int)(ht % T);
-    const int h = (int)(ht / T);
-    const int len = seq_len[(long)h * len_stride];
-    float g = dhist[e];
-    if (t < len) {
-      if (dmean) g += dmean[(long)h * D + d] / (float)len;
-      if (drecent && t >= len - recent_k)
-        g += drecent[(long)h * D + d] / (float)(len < recent_k ? len : recent_k);
-    }
-    if (d < Di) {
-      s_item += g * g;
-      const int id = item_idx[(long)h * idx_row_stride + t];
-      if (id == 0) atomicAdd(row0_acc + d, g);
-      else atomicAdd(item_grad + (long)id * Di + d, g);
-    } else {
-      s_cate += g * g;
-      const int id = cate_idx[(long)h * idx_row_stride + t];
-      if (id == 0) atomicAdd(row0_acc + d, g);
-      else atomicAdd(cate_grad + (long)id * Dc + (d - Di), g);
-    }
-  }
-  __syncthreads();
-  for (int d = threadIdx.x; d < D; d += blockDim.x) {
-    const float v = row0_acc[d];
-    if (v != 0.f) {
-      if (d < Di) atomicAdd(item_grad + d, v);
-      else atomicAdd(cate_grad + (d - Di), v);
-    }
-  }
-  if (sumsq) {
-    __shared__ double red[2][4];
-    const double ti = block256_sum_d((double)s_item, red[0]);
-    const double tc = block256_sum_d((double)s_cate, red[1]);
-    if (threadIdx.x == 0) {
-      atomicAdd(sumsq + 0, ti);
-      atomicAdd(sumsq + 1, tc);
-    }
-  }
-}
-
-extern "C" int clsr_gather_hist_bwd(const float* dhist, const float* dmean, const float* drecent,
-                                    const int* item_idx, const int* cate_idx, long idx_row_stride,
-                                    const int* seq_len, int len_stride, int Hn, int T, int Di, int Dc,
-                                    int recent_k, float* item_grad, float* cate_grad, double* sumsq,
-                                    void* stream) {
-  CLSR_CHECK_ARG(dhist && item_idx && cate_idx && seq_len && item_grad && cate_grad);
-  CLSR_CHECK_ARG(Hn >= 0 && T > 0 && Di > 0 && Dc > 0);
-  if (Hn == 0) return CLSR_OK;
-  int blocks = clsr_cdiv((long)Hn * T * (Di + Dc), 256 * 4);
-  if (blocks > 2048) blocks = 2048;
-  hipLaunchKernelGGL(gather_hist_bwd_kernel, dim3(blocks), dim3(256), (Di + Dc) * sizeof(float),
-                     (hipStream_t)stream, dhist,
-                     dmean, drecent, item_idx, cate_idx, idx_row_stride, seq_len, len_stride, Hn, T,
-                     Di, Dc, recent_k, item_grad, cate_grad, sumsq);
-  CLSR_CHECK_LAUNCH();
-  return CLSR_OK;
-}
-
 // flags[idx[r * row_stride + c]] = 1 for r < nrows, c < ncols: the "involved" (tf.unique) id sets
 // of sequential_base_model.py:409-433 / clsr.py:118-127, kept as a dense byte map per table.
 __global__ void mark_rows_kernel(const int* __restrict__ idx, long nrows, int ncols, long row_stride,

@@ -791,31 +791,3 @@ extern "C" int clsr_pack_batch_bf16(const clsr_pack_desc* descs_device, int n, i
   CLSR_CHECK_LAUNCH();
   return CLSR_OK;
 }
-
-// fp32 <-> bf16 row copies (tests, and tensors that cross between the two storage modes)
-__global__ void cvt_f2h_kernel(const float* __restrict__ src, __bf16* __restrict__ dst, long n) {
-  for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (long)gridDim.x * blockDim.x)
-    dst[e] = (__bf16)src[e];
-}
-__global__ void cvt_h2f_kernel(const __bf16* __restrict__ src, float* __restrict__ dst, long n) {
-  for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (long)gridDim.x * blockDim.x)
-    dst[e] = (float)src[e];
-}
-extern "C" int clsr_cvt_f32_to_bf16(const float* src, void* dst, long n, void* stream) {
-  CLSR_CHECK_ARG(src && dst && n >= 0);
-  if (n == 0) return CLSR_OK;
-  int blocks = clsr_cdiv(n, 256);
-  if (blocks > 4096) blocks = 4096;
-  hipLaunchKernelGGL(cvt_f2h_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, src, (__bf16*)dst, n);
-  CLSR_CHECK_LAUNCH();
-  return CLSR_OK;
-}
-extern "C" int clsr_cvt_bf16_to_f32(const void* src, float* dst, long n, void* stream) {
-  CLSR_CHECK_ARG(src && dst && n >= 0);
-  if (n == 0) return CLSR_OK;
-  int blocks = clsr_cdiv(n, 256);
-  if (blocks > 4096) blocks = 4096;
-  hipLaunchKernelGGL(cvt_h2f_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const __bf16*)src, dst, n);
-  CLSR_CHECK_LAUNCH();
-  return CLSR_OK;
-}

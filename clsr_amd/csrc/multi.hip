@@ -157,7 +157,7 @@ extern "C" int clsr_gather_rows_multi_h(const clsr_gather_desc* descs, int n, vo
   return gather_rows_multi_launch(descs, n, 1, stream);
 }
 
-// ---- out[e] (=|+=) scale * sum_p partial[p*stride + e]  (attention.hip: reduce_parts_f_kernel)
+// ---- out[e] (=|+=) scale * sum_p partial[p*stride + e]  (float partials; one block per output element)
 __global__ void __launch_bounds__(256) reduce_parts_multi_kernel(MultiArgs<clsr_rp_desc> a) {
   __shared__ float red[4];
   const clsr_rp_desc d = a.d[blockIdx.y];

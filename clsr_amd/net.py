@@ -141,42 +141,22 @@ class CLSRNet(object):
         # (round 5 ran the two-piece forms under the name "fp32"; round 6 moved them back here.)
         self.x3 = self.precision == "fp32x3"
         self.exact_products = self.precision == "fp32"      # no two-piece product anywhere
-        x3d = self.x3                                        # two-piece forms
-        x6d = self.precision in ("fp32", "fp32x3")           # three-piece forms (fp32 accuracy): both fp32-storage modes
-        self.x3_dw = False      # (the generic split-bf16 weight-gradient kernel, csrc/dw3.hip, measured level or slower in
-                                # round 4 and was removed in round 5: the attention weight gradients are folded into the
-                                # backward kernels instead, csrc/attbwdx3.hip)
-        self.x3_enc = x3d and True        # A/B: fused encoder tail (csrc/encbwd.hip)
-        # precision="fp32": CLSR_ENC_BWD=x6 runs the same kernel with three pieces per operand (weight gradients on the
-        # weight-gradient stream, beside d(hist) as a three-piece product and the time-feature chain).  Measured and NOT the
-        # default: its three 54 KB piece images fill the CU's LDS, the launch takes 394 us and starves what runs beside it
-        # (3.09 against 3.03 ms per step with the fp32-MFMA kernel that also computes d(hist), alone on the compute stream)
+        # precision="fp32": CLSR_ENC_BWD=x6 runs the fused encoder tail (csrc/encbwd.hip) with three pieces per operand
+        # (weight gradients on the weight-gradient stream, beside d(hist) as a three-piece product and the time-feature
+        # chain).  Measured and NOT the default: its three 54 KB piece images fill the CU's LDS, the launch takes 394 us and
+        # starves what runs beside it (3.09 against 3.03 ms per step with the fp32-MFMA kernel that also computes d(hist),
+        # alone on the compute stream)
         self.enc_x6 = self.exact_products and os.environ.get("CLSR_ENC_BWD", "fp32") == "x6"
-        self.enc_back_x3 = x3d and True   # A/B: d(hist) and d TT from one pass over dPin (csrc/projx3.hip)
-        self.att_l1_fwd_x6 = x6d and True   # A/B: second attention layer, forward, three pieces (csrc/attl1fwd.hip)
         # history-level attention backward in one launch (csrc/atthist.hip): two pieces in "fp32x3" / one-piece-compatible in
-        # the speed mode, THREE pieces in "fp32"
-        self.att_hist_bwd_x3 = True
+        # the speed mode, THREE pieces in "fp32".  (The forward products that feed a batch-norm + ReLU stay at fp32 accuracy
+        # in both fp32-storage modes: three pieces in the history-level prologue and the second attention layer, the
+        # fp32-MFMA layer-0 kernel.)
         self.att_hist_bwd_pieces = 3 if self.exact_products else 2
-        self.att_hist_x3 = True  # A/B: history-level attention prologue in one launch (csrc/atthist.hip)
-        # (forward products that feed a batch-norm + ReLU stay at fp32 accuracy in both fp32-storage modes -- three pieces in
-        # the history-level kernel, the fp32-MFMA layer-0 kernel -- see csrc/atthist.hip; the two-piece forms are opt-in
-        # under "fp32x3": CLSR_ATT_FWD_X3=1, CLSR_ATT_HIST_PIECES=2)
-        self.att_fwd_x3 = x3d and False
-        # the per-(row, step) layer-0 product over three bf16 pieces per operand (fp32 accuracy, 60 bf16 MFMAs instead of 100
-        # fp32 ones per tile: csrc/attl0fwd.hip): 102 -> 90 us alone, nothing in the step (three interleaved A/B runs) --
-        # opt-in (CLSR_ATT_FWD_X6=1), the default stays the bit-exact fp32-MFMA form
-        self.att_fwd_x6 = x6d and False
-        self.att_l0_fwd_entry = ("clsr_att_l0_fwd_x3" if self.att_fwd_x3 else
-                                 "clsr_att_l0_fwd_x6" if self.att_fwd_x6 else "clsr_att_l0_fwd")
-        self.att_hist_pieces = 3 if x3d else 3  # A/B: first attention layer, forward (csrc/attl0fwd.hip)
         # speed mode, round 5b: the (row, step)-level attention layers on the SAME chain kernels as the parity mode
         # (csrc/attl0fwd.hip, attl1fwd.hip, attbwdx3.hip) with ONE bf16 piece per operand and bf16 storage of z0 / z1 / dz0:
         # the weight gradients dW1 / db1 / dWp ride inside the backward kernels (no clsr_hdw launches over z0 / dz1 / dz0,
         # no stored dz1).  CLSR_BF16_CHAIN=old: the position-tiled csrc/hgemm.hip kernels of rounds 2-4.
         self.bf16_chain = self.precision == "bf16" and os.environ.get("CLSR_BF16_CHAIN", "x1") == "x1"
-        self.bf16_dw = True        # A/B switch: weight gradients on the bf16 matrix pipe
-        self.bf16_bwd = True      # A/B switch: back-propagating products likewise
         self._cur_descs_h = []
         self._plans, self._plan_keep, self._cur_descs = {}, [], []
         self._sort_bytes = {}
@@ -184,42 +164,16 @@ class CLSRNet(object):
         # side streams are shared by every net of the process on this device (one net steps at a time): a second net
         # with four streams of its own puts eight hardware queues in play and its step takes 5.7 instead of 3.4 ms
         self._side = _SIDE_STREAMS.setdefault(str(torch.device(device)), {})
-        self.rnn_first = True   # A/B switch (see forward)
-        self.dw_batch_late = True   # A/B: merged launches of the attention / head weight gradients
-        self.bn_bwd_fused = True   # A/B: coefficient + apply of the row-level batch-norm backward in one launch
-        self.hist_grad_two = True   # A/B: dhist + dhist_lt summed inside the segmented sums
-        self.l0_bwd_halves = True   # A/B: wide layer-0 backward as two launches of the x3 kernel over column halves
-        self.dense_upd_dw = True   # A/B: dense regulariser + Adam on the weight-gradient stream
         self._dense_fork = None
-        self.tick_early = True   # A/B: Adam clock in the first launch of the update phase
-        self.dw_stream = True   # A/B switch (see _dw)
         self._dw_async = False
-        # A/B switch (see _att_qh); the bf16 speed mode keeps the whole query in the per-(row, step) GEMM (K is cheap there)
+        # history-level half of the short-term query folded into U (see _att_qh; SeqNet has no such half).  Pays off at every
+        # width once the per-row half runs on the one-wave-per-history kernels (round 3; the position-tiled kernels needed
+        # Du >= 64); in the speed mode the history-level share of the product term rides inside the fused history-level
+        # kernels (csrc/atthist.hip): the split costs no launch and halves K of the per-(row, step) kernels
         self.split_query = True
-        # (speed mode, round 5: with the history-level share of the product term inside the fused history-level kernels
-        # -- csrc/atthist.hip -- the split costs no launch any more and halves K of the per-(row, step) kernels;
-        # CLSR_BF16_NO_SPLIT_QUERY=1: the whole query in those kernels, as before)
-        self.bf16_split_query = True
-        # history-level half of the short-term query folded into U (see _att_qh): pays off at every width once the per-row
-        # half runs on the one-wave-per-history kernels (round 3; the position-tiled kernels needed Du >= 64)
         self.split_query_min = 16
-        self.split_emb_grad = True   # A/B switch (embedding gradient sites)
         self.use_plans = not os.environ.get("CLSR_NO_PLAN")                # replay recorded launch sequences
-        self.split_g2 = True             # A/B switch (causal GRU off the main launch)
-        self.g2_stream = "@lt"           # A/B: which side stream runs the causal GRU's forward
         self._step_plans = {}
-        self.dw_streams = 1
-        self.fused_l0_bwd = True   # A/B switch (see _att_bwd)
-        self.dw_batching = True          # A/B switch (see _dw_batched)
-        self.flush_side = True          # A/B switch (dense path off the main stream)
-        self.l1_bwd_2pass = True      # A/B switch (exact mode, see _att_bwd)
-        self.dpin_h = (self.bf16 and self.bf16_dw and self.bf16_bwd and type(self) is CLSRNet
-                       and True)          # bf16 dPin (speed mode, CLSR graph only)
-        # where the long-term attention backward forks: beside the short-term one (exact mode: -40 us) or underneath the
-        # backward-through-time launch (speed mode: the short-term backward is bandwidth bound there); CLSR_LT_BWD_EARLY=0|1
-        # (round 2: off in speed mode, +30 us there; with the fused encoder tail the long-term chain had become the LAST thing
-        #  to finish in that mode: early wins by 0.06 ms since round 3)
-        self.lt_bwd_early = True
         self._dw_batch = None
         self._buf_allocs = 0
         # HIP stream priorities of the side streams (0 = normal; the callers' compute stream can be created with -1 = high)
@@ -243,13 +197,10 @@ class CLSRNet(object):
             self.rnn_products = "fp32"      # (wide encoders: no three-piece instance -- fp32-input MFMAs, same accuracy)
         self.rnn_fused_proj = self.rnn_products in ("x3", "x6") and not os.environ.get("CLSR_NO_RNN_FUSED_PROJ")
         # the Time4LSTM's K-fused time-gate projection as split products too (csrc/projx3.hip): three pieces in "fp32", two
-        # in the other modes (it feeds the same sigmoid gates as the recurrences' two-piece hidden products there)
-        self.proj_x3 = True
+        # in the other modes (it feeds the same sigmoid gates as the recurrences' two-piece hidden products there); so are
+        # the whole input projection when it is NOT fused into the recurrence launch (hidden sizes > 48: configs[4]) and
+        # every plain wide product
         self.proj_gate_pieces = 3 if self.exact_products else 2
-        # ... and the whole input projection when it is NOT fused into the recurrence launch (hidden sizes > 48: configs[4])
-        self.proj_tt = self.proj_x3 and True      # A/B: tanh time features in that kernel's prologue
-        self.proj_x3_wide = self.proj_x3 and True
-        self.gemm_wide_x3 = self.proj_x3_wide and True   # A/B: every plain wide product
         self.proj_bwd_pieces = 3 if self.exact_products else 2
         self.proj_wide_pieces = (2 if self.precision == "bf16" else 3)
         self.rnn_act_tiled = self.rnn_products in ("x3", "x6")
@@ -260,7 +211,6 @@ class CLSRNet(object):
         # kernels + separate weight-gradient launches)
         # ("x6l1": three pieces in the layer-1 kernel only, the layer-0 backward on fp32 MFMAs + its weight-gradient launch)
         self.set_att_bwd(os.environ.get("CLSR_ATT_BWD", "x6l1" if self.exact_products else "x3"))   # (before the three-piece recurrences: x6l1 3.19-3.22 ms, fp32 3.32-3.34; x6 with the per-iteration K = 16 weight-gradient products is level with x6l1: 3.05-3.08 both)
-        self.fuse_tt = True   # A/B: time-gate blocks of the input projection as one product over [hist | TT]
         # the row-level heads (alpha gate, alpha / logit MLPs, loss, their backward) as two persistent launches with grid
         # barriers for the batch-norm statistics (csrc/headsfused.hip) instead of a chain of 22 dependent launches
         self.heads_fused = not os.environ.get("CLSR_NO_HEADS_FUSED")
@@ -274,24 +224,17 @@ class CLSRNet(object):
         self._heads_defer = False
         self._early_lists = None
         self.heads_comm = None      # data-parallel runs: communicator of the fused heads (clsr_amd/p2p.py: HeadsComm)
-        self.fused_logit_tail = True   # A/B: output layer + softmax loss + their backward in one launch
         self._defer_logit_out = False
-        self.early_scatter = True   # A/B: row scatters of the user / target lookups beside the encoder-backward tail instead of behind it
-        self.dhist_side = True      # A/B (speed mode): d(hist) product on the long-term stream (2.87 -> 2.84 ms)
-        self.enc_bwd_fused_h = True   # A/B: the speed-mode (bf16 dPin) form of the fused encoder tail
-        self.enc_bwd_fused = True   # A/B: one pass over dPin for the seven encoder-side weight gradients + d(hist) (csrc/encbwd.hip)
-        # ... which also adds the long-term d(hist) and the history prologue's shares, so that the segmented sums run lean
+        # the fused encoder tail (csrc/encbwd.hip) also adds the long-term d(hist) and the history prologue's shares, so that
+        # the segmented sums run lean
         self.fold_hist_shares = not os.environ.get("CLSR_NO_FOLD_SHARES")
         self._fold_args, self._folded = None, False
         self.early_user_update = not os.environ.get("CLSR_NO_EARLY_USER_UPDATE")   # user tables: regulariser + Adam behind their row scatters
         self._updated_early = set()
-        self.l0_fwd_wave = True      # A/B switch (exact mode, see _att_fwd)
-        self.fused_l0_wu = True   # A/B: dU . Wu^T inside that kernel as well (time-neutral, two launches fewer)
         self._joins = []
         self._dw_pending, self._dw_tables, self._dw_after, self._rp_pending = {}, {}, {}, {}
         self.defer_dw = True       # one batched reduction of the weight-gradient partials per stream and step
         self.overlap = not os.environ.get("CLSR_NO_OVERLAP")   # run the long-term attention chain etc. on side streams (fork / join); off: one stream, every kernel alone (diagnosis: contention-free kernel times)
-        self.sorted_hist_grad = True   # history-row gradients by sort + segmented sums (False: float atomics)
         # deterministic embedding gradients (csrc/segsum.hip): STABLE radix sort of every lookup site's ids + segmented sums
         # that write each row once, in a fixed order -- no float atomics; two runs of a step give bit-identical gradient
         # tables and clip norms.  CLSR_NO_DET_GRADS=1: the counting sort + atomics of rounds 2-3.
@@ -308,8 +251,8 @@ class CLSRNet(object):
         self._counts_zeroed = self._ucount_zeroed = self._ticked = False
         self.dp_world = 1          # data-parallel world size (loss normalisers are global)
         self.dp_stats_hook = None  # optional callable(tensor): sum BN partial statistics across ranks
-        self.dp_comm = None        # optional communicator handle (clsr_amd/p2p.py): the same sum as ONE kernel on this stream
-        self.bn_sync_fused = True  # ... fused with the fold of the partial sums and the layer's finalisation (round 6; False: three launches)
+        self.dp_comm = None        # optional communicator handle (clsr_amd/p2p.py): the same sum as ONE kernel on this stream,
+                                   # fused with the fold of the partial sums and the layer's finalisation
         # data-parallel exchange hooks (clsr_amd/dp.py): called (and recorded into launch plans) at the points of the
         # step where a piece of the gradient state becomes final, so that its collective overlaps the rest of the
         # backward pass: flags_ready() | dense_ready() | table_ready(name)
@@ -389,17 +332,14 @@ class CLSRNet(object):
     # The variable inventory, the trained embedding tables and the recurrent encoders are hooks so that the sibling
     # models of the reference that share these kernels (clsr_amd/seqnet.py) reuse everything below.
     # ------------------------------------------------------------------ launch plans
-    #: every mode switch that changes the recorded launch sequence: ONE tuple, so that flipping any of them on a live net (A/B
-    #: runs on the same feed, tests) records a new plan instead of silently replaying the old one
-    _SWITCHES = ("precision", "table_bf16", "exact_products", "overlap", "defer_dw", "sorted_hist_grad", "det_grads", "lazy",
-                 "rnn_first", "tick_early", "bn_sync_fused", "hist_grad_two", "dw_batch_late", "bn_bwd_fused", "dw_stream", "dw_streams",
-                 "split_query", "split_query_min", "bf16_split_query", "split_emb_grad", "bf16_chain", "bf16_dw", "bf16_bwd",
-                 "fused_l0_bwd", "fused_l0_wu", "l0_fwd_wave", "l0_bwd_halves", "dw_batching", "lt_bwd_early", "dpin_h", "flush_side",
-                 "l1_bwd_2pass", "split_g2", "g2_stream", "rnn_products", "rnn_fused_proj", "rnn_act_tiled", "att_bwd", "att_bwd_l0", "_l1x", "_l0x", "att_hist_x3",
-                 "att_hist_bwd_x3", "att_hist_bwd_pieces", "att_hist_pieces", "att_l1_fwd_x6", "att_fwd_x3", "att_fwd_x6",
-                 "att_l0_fwd_entry", "x3_enc", "enc_x6", "enc_back_x3", "enc_bwd_fused", "enc_bwd_fused_h", "fold_hist_shares", "early_user_update", "proj_x3", "proj_tt", "proj_x3_wide",
-                 "gemm_wide_x3", "proj_gate_pieces", "proj_bwd_pieces", "proj_wide_pieces", "dhist_side", "early_scatter",
-                 "fused_logit_tail", "fuse_tt", "heads_fused", "dense_upd_dw", "dw_wide", "dw_wide_entry", "rowlist_min_elems")
+    #: every attribute that can differ between two nets or be flipped on a live net (environment switches, tests) and that
+    #: changes the recorded launch sequence: ONE tuple, so that flipping any of them records a new plan instead of silently
+    #: replaying the old one
+    _SWITCHES = ("precision", "table_bf16", "exact_products", "x3", "bf16", "overlap", "defer_dw", "det_grads", "lazy",
+                 "use_plans", "heads_fused", "early_user_update", "fold_hist_shares", "enc_x6", "rnn_products", "rnn_fused_proj",
+                 "rnn_act_tiled", "att_bwd", "att_bwd_l0", "_l1x", "_l0x", "bf16_chain", "dw_wide", "dw_wide_entry", "split_query",
+                 "split_query_min", "rowlist_min_elems", "att_hist_bwd_pieces", "proj_gate_pieces", "proj_bwd_pieces",
+                 "proj_wide_pieces")
 
     def _plan_key(self, what, f):
         hp = self.hp
@@ -786,7 +726,7 @@ class CLSRNet(object):
         self.packed[key] = (buf, Kp)
         self._cur_descs.append(ops.pack_desc(W, out_f, in_f, buf, Kp, transposed=transposed, o0=o0, i0=i0,
                                              src2=W2, s2=s2))
-        if self.bf16 and self.bf16_bwd and key.endswith("^T") and out_t % 8 == 0 and in_t % 8 == 0:
+        if self.bf16 and key.endswith("^T") and out_t % 8 == 0 and in_t % 8 == 0:
             # speed mode: the back-propagating products run on the bf16 matrix pipe too (csrc/hgemm.hip: clsr_hgemm_f32)
             hKp = query("clsr_hgemm_kp", in_t)
             hbuf = self._buf("packh:" + key, 32 * ((out_t + 31) // 32) * hKp, dtype=torch.bfloat16)
@@ -824,7 +764,7 @@ class CLSRNet(object):
             call("clsr_hgemm_hf32" if X.dtype == torch.bfloat16 else "clsr_hgemm_f32", X, ldx, Wt, Kp, Y, ldy, acc, M, K, N)
             return
         Wt, Kp = self.packed[wkey]
-        if (self.gemm_wide_x3 and Xmul is None and aff is None and addU is None and addV is None and stats is None and T == 0
+        if (Xmul is None and aff is None and addU is None and addV is None and stats is None and T == 0
                 and X.dtype == F32 and Y.dtype == F32 and M >= 32768 and (K >= 128 or N >= 128) and K <= 4096 and K % 8 == 0 and ldx % 4 == 0
                 and query("clsr_proj_x3_wide_supported", M, K, N)):
             # plain position-level products of WIDE layers (BASELINE configs[4]): operands in registers, 128 output columns
@@ -845,27 +785,24 @@ class CLSRNet(object):
         partial chunks (into a workspace of its own); ``_dw_flush`` reduces every pending gradient of the current
         stream in ONE launch."""
         if (self.dw_wide and not x_bf16 and not dy_bf16 and aff is None and T == 0 and G == 0
-                and not (self.bf16 and self.bf16_dw) and not self.x3_dw and query("clsr_pgemm_dw_wide_supported", M, K, N)):
+                and not self.bf16 and query("clsr_pgemm_dw_wide_supported", M, K, N)):
             return self._dw_wide(X, ldx, Xmul, ldmul, dY, ldy, M, K, N, dW, ldw, db, acc)
         pend = self._dw_pending.setdefault(self._ws_tag, [])
         need = query("clsr_pgemm_dw_workspace_floats", M, K, N)
         ws = self._buf("dw_ws%s.%d" % (self._ws_tag, len(pend)), max(need, 1))
         sc, sh = (aff.scale, aff.shift) if aff is not None else (None, None)
-        if self._dw_batch is not None and not x_bf16 and not (dy_bf16 and not (self.bf16 and self.bf16_dw)):
+        if self._dw_batch is not None and not x_bf16 and not (dy_bf16 and not self.bf16):
             # inside _dw_batched(): the product joins the ONE multi-job launch issued when the block ends
             ptr = lambda t: 0 if t is None else t.data_ptr()
             self._dw_batch.append((ptr(X), ptr(Xmul), ptr(sc), ptr(sh), ptr(dY), ptr(ws), 0, ldx, T, G, ldmul, 1,
                                    int(dy_bf16), ldy, M, K, N, 0))
-        elif self.dw_stream and self.overlap and self._ws_tag == "":
+        elif self.overlap and self._ws_tag == "":
             # nothing on the main chain needs a weight gradient before the flush: the partial-sum kernels of the
             # main stream go to a stream of their own (inputs are final at this point and stay untouched until the
             # flush joins that stream), so they run beside the back-propagating GEMMs instead of between them.
             # ONE such stream: main + @lt + @aux + @dw0 = 4 concurrently active streams; a fifth one was measured at
             # 7.2 ms/step with GPU_MAX_HW_QUEUES=8 (hardware-queue oversubscription) -- do not add streams
-            name = "@dw%d" % (len(pend) % self.dw_streams)
-            side = self._side.get(name)
-            if side is None:
-                side = self._side_stream(name)
+            side = self._side_stream("@dw0")
             ops.stream_wait(side, self._fork_point())
             self._dw_launch(X, x_bf16, ldx, T, G, Xmul, ldmul, sc, sh, dY, dy_bf16, ldy, M, K, N, ws, side.cuda_stream)
             self._dw_async = True
@@ -887,7 +824,7 @@ class CLSRNet(object):
             self._dw_batch_wide.append(job)
             return
         side = None
-        if self.dw_stream and self.overlap and self._ws_tag == "":
+        if self.overlap and self._ws_tag == "":
             side = self._side_stream("@dw0")
             ops.stream_wait(side, self._fork_point())
             self._dw_async = True
@@ -899,7 +836,7 @@ class CLSRNet(object):
         for what had been enqueued on the current stream when the block was ENTERED: the encoders' hidden-to-hidden /
         time-feature / input-side weight gradients all read the finished dPin and forward activations.  One after the
         other on the weight-gradient stream those ~7 products were the last 350 us of the backward pass."""
-        if not self.dw_batching or not self.defer_dw or self._dw_batch is not None or (late and not self.dw_batch_late):
+        if not self.defer_dw or self._dw_batch is not None:
             yield
             return
         fork = self._fork_point()
@@ -919,12 +856,9 @@ class CLSRNet(object):
             # fills sit on the current stream BEHIND the entry point -- this once the launch waits for everything
             # enqueued so far
             fork = self._fork_point()
-        name = ("clsr_hdw_partial_multi" if (self.bf16 and self.bf16_dw) else
-                "clsr_pgemm_dw_partial_multi")
-        if self.dw_stream and self.overlap and self._ws_tag == "":
-            side = self._side.get("@dw0")
-            if side is None:
-                side = self._side_stream("@dw0")
+        name = "clsr_hdw_partial_multi" if self.bf16 else "clsr_pgemm_dw_partial_multi"
+        if self.overlap and self._ws_tag == "":
+            side = self._side_stream("@dw0")
             ops.stream_wait(side, fork)
             if jobs:
                 ops.dw_multi(name, jobs, stream=side.cuda_stream)
@@ -939,14 +873,12 @@ class CLSRNet(object):
 
     def _dw_parts_query(self, any_bf16=False):
         """which query tells how many partial chunks the weight-gradient kernel of this mode writes"""
-        if self.bf16 and self.bf16_dw:
-            return "clsr_hdw_parts"
-        return "clsr_pgemm_dw_parts"
+        return "clsr_hdw_parts" if self.bf16 else "clsr_pgemm_dw_parts"
 
     def _dw_launch(self, X, x_bf16, ldx, T, G, Xmul, ldmul, sc, sh, dY, dy_bf16, ldy, M, K, N, ws, stream):
         """Partial-sum kernel of one weight gradient: the exact fp32-MFMA kernel, or -- speed mode -- the bf16-MFMA
         one (csrc/hdw.hip: operands rounded to bf16 when staged, fp32 accumulation), same partial layout."""
-        if self.bf16 and self.bf16_dw:
+        if self.bf16:
             call("clsr_hdw_partial", X, x_bf16, ldx, T, G, Xmul, ldmul, sc, sh, 1, dY, dy_bf16, ldy, M, K, N, ws,
                  stream=stream)
         elif x_bf16 or dy_bf16:
@@ -976,10 +908,9 @@ class CLSRNet(object):
         pend = self._dw_pending.pop(tag, [])
         if tag == "" and self._dw_async:
             cur = ops.current_stream()
-            for i in range(self.dw_streams):
-                side = self._side.get("@dw%d" % i)
-                if side is not None and side.cuda_stream != cur.cuda_stream:   # (a stream does not wait for itself:
-                    ops.stream_wait(cur, ops.event_record(side))              #  under hipGraph capture that crashed)
+            side = self._side.get("@dw0")
+            if side is not None and side.cuda_stream != cur.cuda_stream:   # (a stream does not wait for itself:
+                ops.stream_wait(cur, ops.event_record(side))              #  under hipGraph capture that crashed)
             self._dw_async = False
         if pend:
             sig = tuple(pend)
@@ -998,7 +929,7 @@ class CLSRNet(object):
         return self._buf("stats" + self._ws_tag, 1024 * 2 * 256, dtype=torch.float64)[: parts * 2 * N], parts
 
     def _bn_fwd(self, bn, stats, parts, count, training):
-        if training and self.dp_stats_hook is not None and self.dp_comm is not None and 2 * bn.C <= 256 and self.bn_sync_fused:
+        if training and self.dp_stats_hook is not None and self.dp_comm is not None and 2 * bn.C <= 256:
             # SyncBN in ONE launch: partial sums folded, exchanged with the peers and finalised inside the kernel (csrc/p2p.hip)
             call("clsr_bn_finalize_sync", self.dp_comm, stats, parts, bn.C, float(count * self.dp_world), bn.gamma, bn.beta,
                  bn.moving_mean, bn.moving_var, BN_MOMENTUM, BN_EPS, bn.scale, bn.shift, bn.mean, bn.invstd)
@@ -1022,7 +953,7 @@ class CLSRNet(object):
         return one, 1
 
     def _bn_bwd_from_partial(self, bn, part, parts, dy, z, M):
-        if self.dp_stats_hook is None and M * bn.C <= (1 << 23) and bn.C % 4 == 0 and self.bn_bwd_fused:
+        if self.dp_stats_hook is None and M * bn.C <= (1 << 23) and bn.C % 4 == 0:
             # row-level layers (alpha / logit MLPs): coefficients + apply in one launch
             call("clsr_bn_bwd_coef_apply", part, parts, bn.C, float(M), bn.gamma, bn.mean, bn.invstd, bn.coef,
                  bn.dgamma, bn.dbeta, dy, z, M)
@@ -1031,7 +962,7 @@ class CLSRNet(object):
         call("clsr_bn_bwd_apply", dy, z, bn.coef, M, bn.C)
 
     def _bn_bwd_coef(self, bn, part, parts, M):
-        if self.dp_stats_hook is not None and self.dp_comm is not None and 2 * bn.C <= 256 and self.bn_sync_fused:
+        if self.dp_stats_hook is not None and self.dp_comm is not None and 2 * bn.C <= 256:
             call("clsr_bn_bwd_coef_sync", self.dp_comm, part, parts, bn.C, float(M * self.dp_world), bn.gamma, bn.mean, bn.invstd,
                  bn.coef, bn.dgamma, bn.dbeta, 1.0 / self.dp_world)
             return
@@ -1142,8 +1073,7 @@ class CLSRNet(object):
             return 0
         if self.precision == "bf16":
             # speed mode: only with the fused history-level kernels and the one-pass layer-0 backward (default widths)
-            ok = (self.bf16_split_query and self.att_hist_x3 and self.att_hist_bwd_x3 and self.fused_l0_bwd
-                  and query("clsr_att_hist_fwd_x3_supported", self.H, self.Du + self.D, self.A0, self.Du)
+            ok = (query("clsr_att_hist_fwd_x3_supported", self.H, self.Du + self.D, self.A0, self.Du)
                   and query("clsr_att_hist_bwd_x3_supported", self.H, self.Du + self.D, self.A0, self.Du)
                   and query("clsr_att_l0_bwd_h_supported", self.G_train, self.D, self.A0))
             return self.Du if ok else 0
@@ -1230,7 +1160,7 @@ class CLSRNet(object):
     def _fuse_tt_ok(self):
         """One product [hist | TT] . [W_x ; W_t] for the three time-gate blocks of the Time4LSTM projection (the last 3H
         columns of the fused input projection) instead of hist . W_x followed by an accumulating TT . W_t pass over them."""
-        return (self.fuse_tt and self._t4_kind == "time4lstm" and self.enc_in % 4 == 0
+        return (self._t4_kind == "time4lstm" and self.enc_in % 4 == 0
                 and self._enc_off("t4") + 6 * self.H == self._xw_blocks()[1])
 
     def _unpack_grads(self):
@@ -1388,7 +1318,7 @@ class CLSRNet(object):
         z1 = self._buf(key + ".z1", R * T, A1, dtype=BF if self.bf16 else F32)
         wts = self._buf(key + ".wts", R, T)
         out = self._buf(key + ".out", R, Dk)
-        hist_x3 = self.att_hist_x3 and bool(query("clsr_att_hist_fwd_x3_supported", Dk, Q, A0, qh))
+        hist_x3 = bool(query("clsr_att_hist_fwd_x3_supported", Dk, Q, A0, qh))
         if hist_x3:
             # a = keys . A and U = a . Wu (+ the history-level share of the product term) in ONE pass over the keys
             # (csrc/atthist.hip) instead of three position-tiled GEMM launches on the dependent chain
@@ -1396,7 +1326,7 @@ class CLSRNet(object):
             Wut, Kpu = self.packed[key + ".Wu"]
             Wpt, Kpp = self.packed[key + ".Wp1"] if qh else (None, 0)
             call("clsr_att_hist_fwd_x3", keys, Dk, At, Kpa, Wut, Kpu, Wpt, Kpp, q_hist if qh else None, qh, Hn, T, Dk, Q,
-                 A0, qh, self.att_hist_pieces, a, Q, U, A0)
+                 A0, qh, 3, a, Q, U, A0)
         else:
             self._gemm(keys, Dk, key + ".A", Hn * T, Dk, Q, a, Q)
             self._gemm(a, Q, key + ".Wu", Hn * T, Q, A0, U, A0)
@@ -1428,7 +1358,7 @@ class CLSRNet(object):
                      seq_len, len_stride, keys, Hn, G, T, A1, Dk, wts, out)
                 return out
             Wt, Kp = self.packed_h[key + (".Wp2" if qh else ".Wp")]
-            if self.l0_fwd_wave and query("clsr_hgemm_l0_group_supported", G, Qe, A0):
+            if query("clsr_hgemm_l0_group_supported", G, Qe, A0):
                 # one wave per history group: a / U loaded once per 16 steps and re-used for the G rows
                 p0 = query("clsr_hgemm_l0_group_stats_parts", Hn) if training else 0
                 call("clsr_hgemm_l0_group", ae, Q, qe, Q, Wt, Kp, U, A0, V, A0, z0, A0,
@@ -1450,7 +1380,7 @@ class CLSRNet(object):
             if not hist_x3:
                 self._gemm(a, Q, key + ".Wp1", Hn * T, qh, A0, U, A0, T=T, G=1, Xmul=q_hist, ldmul=qh, addU=U, ldu=A0,
                            addV=self._buf("att.zeroV", Hn, A0), ldv=A0)
-            if self.l0_fwd_wave and query("clsr_att_l0_fwd_supported", G, Q - qh, A0):
+            if query("clsr_att_l0_fwd_supported", G, Q - qh, A0):
                 # the per-row half (target columns of the query) on the one-wave-per-history kernel: K = Q - qh
                 parts = query("clsr_att_l0_fwd_stats_parts", Hn) if training else 0
                 st = (self._buf("stats" + self._ws_tag, 1024 * 2 * 256, dtype=torch.float64)[: parts * 2 * A0]
@@ -1460,7 +1390,7 @@ class CLSRNet(object):
             else:
                 self._gemm(a[:, qh:], Q, key + ".Wp2", R * T, Q - qh, A0, z0, A0, T=T, G=G, Xmul=q[:, qh:], ldmul=Q,
                            addU=U, ldu=A0, addV=V, ldv=A0, stats=st)
-        elif self.l0_fwd_wave and query("clsr_att_l0_fwd_supported", G, Q, A0):
+        elif query("clsr_att_l0_fwd_supported", G, Q, A0):
             # one wave per history, a / U loaded once per group of rows (csrc/attl0fwd.hip)
             parts = query("clsr_att_l0_fwd_stats_parts", Hn) if training else 0
             st = (self._buf("stats" + self._ws_tag, 1024 * 2 * 256, dtype=torch.float64)[: parts * 2 * A0]
@@ -1471,7 +1401,7 @@ class CLSRNet(object):
             self._gemm(a, Q, key + ".Wp", R * T, Q, A0, z0, A0, T=T, G=G, Xmul=q, ldmul=Q, addU=U, ldu=A0,
                        addV=V, ldv=A0, stats=st)
         self._bn_fwd(bn0, st, parts, R * T, training)
-        if self.att_l1_fwd_x6 and query("clsr_att_l1_fwd_supported", A0, A1) and R * T * A1 * 4 < (1 << 30):
+        if query("clsr_att_l1_fwd_supported", A0, A1) and R * T * A1 * 4 < (1 << 30):
             # z1 = relu(bn0(z0)) . W1 + b1 on the bf16 matrix pipe with three pieces per operand (csrc/attl1fwd.hip)
             parts = query("clsr_att_l1_fwd_stats_parts", R * T) if training else 0
             st = (self._buf("stats" + self._ws_tag, 1024 * 2 * 256, dtype=torch.float64)[: parts * 2 * A1]
@@ -1551,10 +1481,10 @@ class CLSRNet(object):
             self._dw(ae, Q, dz0, A0, M, Qe, A0, dW0[3 * Q + qh:4 * Q], A0, T=T, G=G, Xmul=qe, ldmul=Q, dy_bf16=1)
             Wt, Kp = self.packed_h[key + (".Wp2^T" if qh else ".Wp^T")]
             dU = self._buf(key + ".dU", Hn * T, A0)
-            if self.fused_l0_bwd and query("clsr_att_l0_bwd_h_supported", G, Qe, A0):
+            if query("clsr_att_l0_bwd_h_supported", G, Qe, A0):
                 # da, dq, dU, dV in one pass over dz0; daq = dz0 . Wp^T is never written (csrc/hattbwd.hip)
                 # (dU . Wu^T inside the kernel only while the history-level tail is not the fused launch of csrc/atthist.hip)
-                wu_in = self.bf16_bwd and self.fused_l0_wu and not qh and not self._hist_bwd_x3(Dk, Q, 0)
+                wu_in = not qh and not self._hist_bwd_x3(Dk, Q, 0)
                 Wu, Kpu = self.packed_h[key + ".Wu^T"] if wu_in else (None, Kp)
                 assert Kpu == Kp
                 call("clsr_att_l0_bwd_h", dz0, A0, Wt, Wu, Kp, ae, Q, qe, Q, Hn, G, T, Qe, A0,
@@ -1573,7 +1503,7 @@ class CLSRNet(object):
                 call("clsr_att_z0_bwd_reduce_h", dz0, Hn, G, T, A0, dU, dV)
             return self._att_bwd_hist(key, scope, nn, a, q, keys, dkeys, dU, dV, da, dq, dW0, Hn, R, T, Dk, Q, 0)
         x3b = self.att_bwd in ("x3", "x6")
-        if x3b and self.l1_bwd_2pass and query("clsr_att_l1_bwd_x3_supported", A1, A0) and (R * T * A0 + 80) * 4 < (1 << 31) - 1:
+        if x3b and query("clsr_att_l1_bwd_x3_supported", A1, A0) and (R * T * A0 + 80) * 4 < (1 << 31) - 1:
             # the same two passes as split-bf16 products; pass 2 also accumulates dW1 / db1 (dz1 is never stored)
             M = R * T
             Wt, Kp = self.packed[key + ".W1^T"]
@@ -1587,7 +1517,7 @@ class CLSRNet(object):
             call(self._l1x, z1, A1, ds, bn1.scale, bn1.shift, wo, bn1.coef, Wt, Kp, z0, A0, bn0.scale,
                  bn0.shift, None, None, bn0.coef, dz0, A0, ws, None, M, A1, A0)
             self._dw_fused(ws, parts, A0, A1, Gd[nn + "w_nn_layer1"], A1, db=Gd[nn + "b_nn_layer1"])
-        elif self.l1_bwd_2pass and query("clsr_att_l1_bwd_supported", A1, A0):
+        elif query("clsr_att_l1_bwd_supported", A1, A0):
             # two passes over (z1, z0) with dz1 recomputed in the GEMM prologue: the batch-norm sums of layer 0, then the
             # finished dz0 (+ dz1 for the weight gradient) -- no dy1-apply / bn-apply sweeps (csrc/attl1bwd.hip)
             M = R * T
@@ -1610,7 +1540,7 @@ class CLSRNet(object):
         x3b = self.att_bwd_l0 in ("x3", "x6")
         if qh:
             Q2 = Q - qh
-            l0x3 = x3b and self.fused_l0_bwd and query("clsr_att_l0_bwd_x3_supported", G, Q2, A0)
+            l0x3 = x3b and query("clsr_att_l0_bwd_x3_supported", G, Q2, A0)
             halves = (not l0x3) and x3b and self._l0_bwd_halves_ok(G, Q2)
             if not (l0x3 or halves):
                 self._dw(a[:, qh:], Q, dz0, A0, R * T, Q2, A0, dW0[3 * Q + qh:4 * Q], A0, T=T, G=G, Xmul=q[:, qh:],
@@ -1628,7 +1558,7 @@ class CLSRNet(object):
                      dq[:, qh:], Q, dU, A0, dV, A0, ws)
                 self._dw_fused(ws, parts, Q2, A0, dW0[3 * Q + qh:4 * Q], A0)
                 self._gemm(dV, A0, key + ".Wv^T", R, A0, Q, dq, Q, acc=1)
-            elif self.fused_l0_bwd and query("clsr_att_l0_bwd_supported", G, Q2, A0):
+            elif query("clsr_att_l0_bwd_supported", G, Q2, A0):
                 # per-row half in one pass over dz0 (csrc/hattbwd.hip): da / dq of the target columns, dU, dV; then the V
                 # path over ALL query columns is added (dq[:, :qh] was cleared with the step's accumulators)
                 Wt, Kp = self.packed[key + ".Wp2^T"]
@@ -1650,7 +1580,7 @@ class CLSRNet(object):
                 self._gemm(dU, A0, key + ".Wp1^T", Hn * T, A0, qh, daq1, qh)
                 call("clsr_att_prod_bwd_ld", daq1, qh, a, Q, q_hist, qh, Hn, 1, T, qh, da, Q, dq_hist, qh, 1)
         else:
-            l0x3 = x3b and self.fused_l0_bwd and query("clsr_att_l0_bwd_x3_supported", G, Q, A0)
+            l0x3 = x3b and query("clsr_att_l0_bwd_x3_supported", G, Q, A0)
             halves = (not l0x3) and x3b and self._l0_bwd_halves_ok(G, Q)
             if not (l0x3 or halves):
                 self._dw(a, Q, dz0, A0, R * T, Q, A0, dW0[3 * Q:4 * Q], A0, T=T, G=G, Xmul=q, ldmul=Q)
@@ -1664,7 +1594,7 @@ class CLSRNet(object):
                 call(self._l0x, dz0, A0, Wt, Kp, a, Q, q, Q, Hn, G, T, Q, A0, da, Q, dq, Q,
                      None if G == 1 else dU, A0, dV, A0, ws)
                 self._dw_fused(ws, parts, Q, A0, dW0[3 * Q:4 * Q], A0)
-            elif self.fused_l0_bwd and query("clsr_att_l0_bwd_supported", G, Q, A0):
+            elif query("clsr_att_l0_bwd_supported", G, Q, A0):
                 # da, dq, dU, dV in one pass over dz0 on the fp32 matrix pipe; daq = dz0 . Wp^T is never written
                 Wt, Kp = self.packed[key + ".Wp^T"]
                 call("clsr_att_l0_bwd", dz0, A0, Wt, Kp, a, Q, q, Q, Hn, G, T, Q, A0, da, Q, dq, Q,
@@ -1680,7 +1610,7 @@ class CLSRNet(object):
     def _l0_bwd_halves_ok(self, G, Qw):
         """wide product term (80 < Qw <= 160 query columns: BASELINE configs[4]): the one-pass layer-0 backward with folded dWp
         (csrc/attbwdx3.hip covers <= 80 columns) as TWO launches over the column halves?"""
-        return bool(self.l0_bwd_halves and self.fused_l0_bwd and Qw > 80 and Qw % 8 == 0 and Qw // 2 <= 80
+        return bool(Qw > 80 and Qw % 8 == 0 and Qw // 2 <= 80
                     and query("clsr_att_l0_bwd_x3_supported", G, Qw // 2, self.A0))
 
     def _att_l0_bwd_x3_halves(self, key, wkey, dz0, a, q, da, dq, dU, dV, dW0, Hn, G, R, T, Q, c_lo, Qw):
@@ -1704,14 +1634,12 @@ class CLSRNet(object):
         """Layer-0 forward entry for a product term of K query columns: wide layers (K > 80: BASELINE configs[4]) take the
         three-piece form (fp32 accuracy on the bf16 pipe: 120 bf16 MFMAs per 16 positions where the fp32-input form issues
         160 of twice the cost) unless bit-exact fp32 products are asked for."""
-        if K > 80 and not self.exact_products and self.att_l0_fwd_entry == "clsr_att_l0_fwd":
-            return "clsr_att_l0_fwd_x6"
-        return self.att_l0_fwd_entry
+        return "clsr_att_l0_fwd_x6" if K > 80 and not self.exact_products else "clsr_att_l0_fwd"
 
     def _bf16_chain_ok(self, G, Qe):
         """speed mode on the parity mode's chain kernels (one bf16 piece per operand, bf16 z0 / z1 / dz0)?"""
         A0, A1 = self.A0, self.A1
-        return bool(self.bf16_chain and A0 % 8 == 0 and A1 % 8 == 0 and self.l0_fwd_wave and self.fused_l0_bwd
+        return bool(self.bf16_chain and A0 % 8 == 0 and A1 % 8 == 0
                     and query("clsr_att_l0_fwd_supported", G, Qe, A0) and query("clsr_att_l1_fwd_supported", A0, A1)
                     and query("clsr_att_l1_bwd_x3_supported", A1, A0) and query("clsr_att_l0_bwd_x3_supported", G, Qe, A0))
 
@@ -1751,7 +1679,7 @@ class CLSRNet(object):
 
     def _hist_bwd_x3(self, Dk, Q, qh):
         """history-level tail of the attention backward as ONE launch of split-bf16 products (csrc/atthist.hip)?"""
-        return self.att_hist_bwd_x3 and bool(query("clsr_att_hist_bwd_x3_supported", Dk, Q, self.A0, qh))
+        return bool(query("clsr_att_hist_bwd_x3_supported", Dk, Q, self.A0, qh))
 
     def _att_bwd_hist(self, key, scope, nn, a, q, keys, dkeys, dU, dV, da, dq, dW0, Hn, R, T, Dk, Q, qh,
                       da_has_u=False, q_hist=None, dq_hist=None):
@@ -1922,11 +1850,9 @@ class CLSRNet(object):
 
     def _enc_bwd_fused_ok(self, dpin_h):
         """The default graph at the default widths: short_term_intention GRU + Time4LSTM + causal GRU, D = Du = H = 40,
-        fp32 dPin with the column layout csrc/encbwd.hip is written for."""
+        fp32 dPin (speed mode: bf16 dPin) with the column layout csrc/encbwd.hip is written for."""
         hp = self.hp
-        if self.bf16 and not (dpin_h and self.enc_bwd_fused_h):     # (speed mode: the bf16-dPin form of the kernel)
-            return False
-        return (self.enc_bwd_fused and (dpin_h if self.bf16 else not dpin_h) and type(self) is CLSRNet and self.defer_dw
+        return ((dpin_h if self.bf16 else not dpin_h) and type(self) is CLSRNet and self.defer_dw
                 and self._t4_kind == "time4lstm" and bool(hp.interest_evolve)
                 and (not hp.manual_alpha) and bool(hp.predict_long_short) and self.enc_in == self.D
                 and self.D == self.Du == self.H and bool(query("clsr_enc_bwd_fused_supported", self.D, self.H, self.NX))
@@ -2005,7 +1931,7 @@ class CLSRNet(object):
             wss.append(ws)
             pend.append((ws.data_ptr(), dW.data_ptr(), db.data_ptr() if db is not None else 0, 1.0, parts, K, N, ldw, 0))
         self._buf("t4.dTT", M, 2 * H)      # (workspaces of the branches exist before the fork: see _enc_bwd_fused)
-        side = self.dw_stream and self.overlap
+        side = self.overlap
         with self._branch("@dw0" if side else "@main", after=self._fork_point(), name="@encw"):
             call("clsr_enc_bwd_fused_x6" if self.enc_x6 else "clsr_enc_bwd_fused_x3", dPinAll, hist, self._buf("g1.hprev", Hn, T, H), self._buf("g1.gates", Hn, T, 3 * H),
                  self._buf("t4.mprev", Hn, T, H), self._buf("t4.TT", M, 2 * H), self._buf("g2.hprev", Hn, T, H),
@@ -2013,7 +1939,7 @@ class CLSRNet(object):
         if side:
             self._dw_async = True       # (the flush waits for the weight-gradient stream)
         tcol0 = self._enc_off("t4") + 3 * H
-        if (self.enc_back_x3 and "t4.tw^T" in self.packed
+        if (self.x3 and "t4.tw^T" in self.packed
                 and query("clsr_enc_back_x3_supported", M, NX, D, 2 * H, 3 * H, tcol0)):
             # d(hist) += dPin . W_x^T and d TT = dPin[:, o | tns | tls] . tw^T from ONE pass over dPin (csrc/projx3.hip)
             Wx, Kpx = self.packed["xw^T"]
@@ -2022,7 +1948,7 @@ class CLSRNet(object):
                  M, NX, D, 2 * H, 3 * H)
             self._t4_time_chain_bwd(f, dPinAll, Hn, T, hs, have_dtt=True)
             return
-        if self.dhist_side and self.overlap:
+        if self.overlap:
             with self._branch("@lt", after=self._fork_point(), name="@dhist"):
                 self._gemm(dPinAll, NX, "xw^T", M, NX, D, dhist, D, acc=1)
         else:
@@ -2050,15 +1976,16 @@ class CLSRNet(object):
         # (the kernel can also accumulate d(hist) = dPin . W_x^T -- Wt_bf16 / dhist arguments, tested -- but that product
         #  contracts over the COLUMNS: its operands come from global memory / L1, 100-150 us more in the kernel against the
         #  230 us of the separate clsr_hgemm_hf32 launch that otherwise runs BESIDE it: 2.93 against 2.90 ms per step)
-        side = self.dw_stream and self.overlap
+        side = self.overlap
         with self._branch("@dw0" if side else "@main", after=self._fork_point(), name="@encw"):
             call("clsr_enc_bwd_fused_h", dPinAll, hist, self._buf("g1.hprev", Hn, T, H), self._buf("g1.gates", Hn, T, 3 * H),
                  self._buf("t4.mprev", Hn, T, H), self._buf("t4.TT", M, 2 * H), self._buf("g2.hprev", Hn, T, H),
                  self._buf("g2.gates", Hn, T, 3 * H), *wss, None, 0, None, M)
         if side:
             self._dw_async = True       # (the flush waits for the weight-gradient stream)
-        if self.dhist_side and self.overlap:
-            # three ways: weight gradients on @dw0, d(hist) on the (by now idle) long-term stream, the time-feature chain here
+        if self.overlap:
+            # three ways: weight gradients on @dw0, d(hist) on the (by now idle) long-term stream (2.87 -> 2.84 ms against
+            # d(hist) here), the time-feature chain here
             with self._branch("@lt", after=self._fork_point(), name="@dhist"):
                 self._gemm(dPinAll, NX, "xw^T", M, NX, D, dhist, D, acc=1)
         else:
@@ -2130,7 +2057,7 @@ class CLSRNet(object):
         rnn_fp = self._rnn_fp_on()
         if not rnn_fp:      # (fused projection: the recurrences read the embeddings themselves)
             Nw = NX - 3 * H if fuse_tt else NX
-            if self.proj_x3_wide and D % 8 == 0 and query("clsr_proj_x3_supported", M, D, Nw):
+            if D % 8 == 0 and query("clsr_proj_x3_supported", M, D, Nw):
                 # wide encoders (BASELINE configs[4]: 128 -> 1 536): the projection in front of the recurrences as split
                 # products with the operands in registers, 128 output columns per workgroup column (csrc/projx3.hip)
                 Wt, Kp = self.packed["xw"]
@@ -2140,7 +2067,7 @@ class CLSRNet(object):
                 call("clsr_proj_x3", hist, D, Wt, Kp, self._buf("xw.bias", NX), PinAll, NX, M, D, Nw, self.proj_wide_pieces)
             else:
                 self._gemm(hist, D, "xw", M, D, Nw, PinAll, NX, bias=self._buf("xw.bias", NX))
-        if early_aux is not None or (training and self.sorted_hist_grad):
+        if early_aux is not None or training:
             # work that depends on the feed only -- accumulator zeroing / row marks of the training step
             # (``early_aux``) and the ~35 tiny launches that sort the history ids by row id for the backward's
             # segmented sums -- on the @aux stream (NOT a stream of its own: see _dw, four streams in all), ordered
@@ -2150,7 +2077,7 @@ class CLSRNet(object):
             with self._branch("@aux", after=step_start):
                 if early_aux is not None:
                     early_aux()
-                if training and self.sorted_hist_grad:
+                if training:
                     self._sort_hist_ids(f, Hn, T, hs)
         grus, t4d = [], None
         short_int, rnn_out, fs = ushort, None, None
@@ -2167,7 +2094,7 @@ class CLSRNet(object):
                 # longer waits for the side kernel that writes TT / the [hist | TT] image (those are for the backward pass
                 # only now: joined with the long-term branch in front of the heads) -- one kernel + two stream hops off the
                 # chain that starts the recurrences
-                tt_fused = bool(fuse_tt and self.proj_tt and query("clsr_proj_x3_tt_supported", M, D, Dp, H, 3 * H))
+                tt_fused = bool(fuse_tt and query("clsr_proj_x3_tt_supported", M, D, Dp, H, 3 * H))
                 if not tt_fused:
                     self._join("@lt")     # the time features were computed beside the fused input projection
                 if tt_fused:
@@ -2179,12 +2106,12 @@ class CLSRNet(object):
                 elif fuse_tt:
                     # ONE product over [hist | TT] (K = 48 + 80) writes the time-gate columns: the separate pass that
                     # re-read and re-wrote them (hist . W_x first, += TT . W_t behind it: 112 us alone) is gone
-                    if self.proj_x3 and query("clsr_proj_x3_supported", M, Dp + 2 * H, 3 * H):
+                    if query("clsr_proj_x3_supported", M, Dp + 2 * H, 3 * H):
                         # (split-bf16 products, result lanes = output features: csrc/projx3.hip)
                         Wt, Kp = self.packed["xw.t"]
                         call("clsr_proj_x3", XT, Dp + 2 * H, Wt, Kp, self._buf("xw.bias", NX)[t4off + 3 * H:],
                              PinAll[:, t4off + 3 * H:], NX, M, Dp + 2 * H, 3 * H, self.proj_gate_pieces)
-                    elif self.proj_x3_wide and query("clsr_proj_x3_wide_supported", M, Dp + 2 * H, 3 * H):
+                    elif query("clsr_proj_x3_wide_supported", M, Dp + 2 * H, 3 * H):
                         # (hidden 128: K = 384 as three slabs of 128, the later ones accumulating -- 3 x ~130 us against the
                         # 0.99 ms of the position-tiled product, on the chain in front of the recurrences)
                         Wt, Kp = self.packed["xw.t"]
@@ -2208,8 +2135,9 @@ class CLSRNet(object):
         g2_side = None
         if (not hp.manual_alpha) and hp.predict_long_short:
             d, fs, _ = self._gru_fwd_desc("g2", CL + "causal2/causal2/gru_cell/", H, PinAll, Hn, T, None, training)
-            if self.split_g2 and self.overlap and (grus or self._t4_scope is not None):
-                # only the alpha gate needs this state: off the critical recurrence launch
+            if self.overlap and (grus or self._t4_scope is not None):
+                # only the alpha gate needs this state: off the critical recurrence launch, on @lt ahead of the long-term
+                # attention
                 g2_side = d
             else:
                 grus.append(d)
@@ -2220,20 +2148,11 @@ class CLSRNet(object):
         #      started ~350 us late (profiles/r01_step_timeline_graph_before_after.txt)
         lt = CL + "long_term/attention_fcn/"
         fork = self._fork_point()
-        if self.rnn_first:
-            ops.rnn_multi("clsr_rnn_fwd_multi", grus, t4d, seq_len, ls, Hn, T)
-        g2_tag = self.g2_stream if g2_side is not None else None
-        if g2_tag and g2_tag != "@lt":
-            # the causal GRU on the weight-gradient stream, idle in the forward pass: behind it on @lt the long-term attention
-            # finished ~70 us after the short-term one and the heads waited for it (profiles/r05_step_timeline_fp32.txt)
-            with self._branch(g2_tag, after=fork, name="@g2"):
-                ops.rnn_multi("clsr_rnn_fwd_multi", [g2_side], None, seq_len, ls, Hn, T)
+        ops.rnn_multi("clsr_rnn_fwd_multi", grus, t4d, seq_len, ls, Hn, T)
         with self._branch("@lt", after=fork):
-            if g2_side is not None and g2_tag == "@lt":
+            if g2_side is not None:
                 ops.rnn_multi("clsr_rnn_fwd_multi", [g2_side], None, seq_len, ls, Hn, T)
             att_long = self._att_fwd("lt", lt, hist, ulong, Hn, 1, T, D, Du, seq_len, ls, training)
-        if not self.rnn_first:
-            ops.rnn_multi("clsr_rnn_fwd_multi", grus, t4d, seq_len, ls, Hn, T)
         # ---- short term attention: query = [short_term_intention | target]
         Qs = Du + D
         q = self._buf("st.q", B, Qs)
@@ -2295,7 +2214,7 @@ class CLSRNet(object):
         output-layer / softmax tail's conditions."""
         hp = self.hp
         return bool(self.heads_fused and type(self) is CLSRNet and not hp.manual_alpha and hp.predict_long_short
-                    and (self.dp_stats_hook is None or self.heads_comm is not None) and self.fused_logit_tail
+                    and (self.dp_stats_hook is None or self.heads_comm is not None)
                     and G == hp.train_num_ngs + 1
                     and query("clsr_heads_fused_supported", B, G, self.D, self.H, self.a_in, self.A0, self.A1,
                               self.L0, self.L1))
@@ -2376,7 +2295,7 @@ class CLSRNet(object):
         if B % G:
             raise ValueError("training feed rows (%d) must be a multiple of 1+train_num_ngs (%d)" % (B, G))
         Hn = B // G
-        D, Du, H, Di, Dc = self.D, self.Du, self.H, self.Di, self.Dc
+        D, Du, H = self.D, self.Du, self.H
         hs = 1 if f.get("compact") else G
         seq_len, ls = f["seq_len"], hs
         heads_fused = self._heads_fused_ok(B, G)
@@ -2389,10 +2308,9 @@ class CLSRNet(object):
             # ONE zero-fill launch: squared norms (16) + loss terms (8), the gradient pool, the counters of the
             # history-id sort and the distinct-user counter of the discrepancy loss
             zr = [(self.stats24.data_ptr(), 24 * 8), (zpool.data_ptr(), zpool.numel() * 4)]
-            if self.sorted_hist_grad:
-                counts = self._sort_counts()[0]
-                zr.append((counts.data_ptr(), counts.numel() * 4))
-                self._counts_zeroed = True
+            counts = self._sort_counts()[0]
+            zr.append((counts.data_ptr(), counts.numel() * 4))
+            self._counts_zeroed = True
             if "user_long" in self.tables:
                 zr.append((self.ucount.data_ptr(), 4))
                 self._ucount_zeroed = True
@@ -2413,7 +2331,7 @@ class CLSRNet(object):
                 (f["users"].data_ptr(), fl["user_long"].data_ptr(), Hn, hs, 1, 0),
                 (f["users"].data_ptr(), fl["user_short"].data_ptr(), Hn, hs, 1, 0)])
             self._dp_hook("flags_ready")      # involved-row byte maps are final: their exchange hides under the forward
-            if (apply and self.tick_early and not self.capture_grads and self.dp_hooks is None
+            if (apply and not self.capture_grads and self.dp_hooks is None
                     and "user_long" in self.tables):
                 # the distinct-user count of the discrepancy loss and the Adam clock need the marks only: HERE, under the
                 # forward, instead of as the first launch of the update phase (9 us + a stream hop in front of the table
@@ -2448,8 +2366,7 @@ class CLSRNet(object):
         Gl = hp.train_num_ngs + 1
         lscale = 1.0 / ((B // Gl) * self.dp_world)
         # output layer of the logit MLP + data loss + their backward as ONE launch at the turn of the step
-        fused_tail = (self.fused_logit_tail and B % Gl == 0
-                      and bool(query("clsr_mlp_tail_softmax_supported", Gl, self.L1)))
+        fused_tail = B % Gl == 0 and bool(query("clsr_mlp_tail_softmax_supported", Gl, self.L1))
         self._defer_logit_out = fused_tail
         self._heads_defer = heads_fused
         try:
@@ -2467,13 +2384,11 @@ class CLSRNet(object):
             self._heads_fused_step(f, out, B, G, Hn, T, lscale, dlogit, dtarget, dL, dS, dfs)
         else:
             self._heads_bwd_launches(f, out, B, G, Hn, Gl, lscale, fused_tail, dlogit, dtarget, dL, dS, dfs)
-        dul = None
-        if self.lt_bwd_early:
-            # long-term attention backward (dL is final here) on the side stream from NOW, beside the short-term one
-            with self._branch("@lt", after=self._fork_point()):
-                dul = self._att_bwd("lt", CL + "long_term/attention_fcn/", dL, out["hist_input"], out["u_long"],
-                                    dhist_lt, Hn, 1, T, D, Du, seq_len, ls)
-                self._dw_flush()
+        # long-term attention backward (dL is final here) on the side stream from NOW, beside the short-term one
+        with self._branch("@lt", after=self._fork_point()):
+            dul = self._att_bwd("lt", CL + "long_term/attention_fcn/", dL, out["hist_input"], out["u_long"],
+                                dhist_lt, Hn, 1, T, D, Du, seq_len, ls)
+            self._dw_flush()
         # ---- short-term attention
         st = CL + "short_term/"
         Qs = Du + D
@@ -2484,10 +2399,9 @@ class CLSRNet(object):
         M = Hn * T
         NX = self.NX
         hist = out["hist_input"]
-        scat_early = False
         # speed mode: the gradients of the input projections leave the backward-through-time kernel as bf16 -- their
         # consumers (input-side / hidden-side weight gradients, d(hist) = dPin . W^T) run on the bf16 matrix pipe anyway
-        dpin_h = (self.dpin_h and "xw^T" in self.packed_h and H % 8 == 0 and Du % 8 == 0 and D % 8 == 0
+        dpin_h = (self.bf16 and type(self) is CLSRNet and "xw^T" in self.packed_h and H % 8 == 0 and Du % 8 == 0 and D % 8 == 0
                   and self._hgemm_fits(NX, D)
                   and (self._t4_kind != "time4lstm" or "t4.tw^T" in self.packed_h))
         dPinAll = self._buf("xw.dPin", M, NX, dtype=torch.bfloat16 if dpin_h else F32)
@@ -2507,24 +2421,14 @@ class CLSRNet(object):
             grus.append(self._gru_bwd_desc("gs", st + "simple_gru/gru_cell/", H, dPinAll, Hn, T, None, drnn, None))
         if (not hp.manual_alpha) and hp.predict_long_short:
             grus.append(self._gru_bwd_desc("g2", CL + "causal2/causal2/gru_cell/", H, dPinAll, Hn, T, dfs, None, None))
-        # ---- long-term attention backward (dL has been final since the alpha gate): forked here so that it runs
-        #      on the side stream underneath the T-serial backward-through-time (own scratch + own d(hist))
         fork = self._fork_point()
-        if self.rnn_first:
-            ops.rnn_multi("clsr_rnn_bwd_multi", grus, t4d, seq_len, ls, Hn, T)
-        if dul is None:
-            with self._branch("@lt", after=fork):
-                dul = self._att_bwd("lt", CL + "long_term/attention_fcn/", dL, out["hist_input"], out["u_long"],
-                                    dhist_lt, Hn, 1, T, D, Du, seq_len, ls)
-                self._dw_flush()
-        if not self.rnn_first:
-            ops.rnn_multi("clsr_rnn_bwd_multi", grus, t4d, seq_len, ls, Hn, T)
+        ops.rnn_multi("clsr_rnn_bwd_multi", grus, t4d, seq_len, ls, Hn, T)
         # the row scatters of the user / target-item / target-category lookups need nothing from the encoder tail
         # below: they go to the side streams early instead of queueing behind it -- long-term user rows and target
         # rows UNDER the backward-through-time launch (latency bound, leaves issue slots; beside the MFMA-saturated
         # fused tail they ran 4x slower and the history-row sums waited for them), the short-term user rows (final
         # only now) beside the small d TT product
-        scat_early = self.early_scatter and self.sorted_hist_grad and self.split_emb_grad and self.overlap
+        scat_early = self.overlap
         if scat_early:
             self._scatter_rows_early(f, dul, None, dtarget, Hn, B, hs, fork)
             self._scatter_rows_early(f, None, dushort, None, Hn, B, hs, self._fork_point())
@@ -2535,10 +2439,9 @@ class CLSRNet(object):
                 with self._branch("@aux", after=self._fork_point(), name="@uupd"):
                     self._update_user_tables_early()
         self._folded = False
-        self._fold_args = ((dhist_lt, dM, dR, seq_len, ls) if (self.sorted_hist_grad and self.det_grads and self.hist_grad_two
-                                                              and dhist.dtype == F32) else None)
+        self._fold_args = (dhist_lt, dM, dR, seq_len, ls) if (self.det_grads and dhist.dtype == F32) else None
         if self._enc_bwd_fused_ok(dpin_h):
-            (self._enc_bwd_fused_h if self.bf16 else self._enc_bwd_fused_x3 if (self.x3_enc or self.enc_x6) else
+            (self._enc_bwd_fused_h if self.bf16 else self._enc_bwd_fused_x3 if (self.x3 or self.enc_x6) else
              self._enc_bwd_fused)(f, hist, dPinAll, dhist, Hn, T, hs)
         else:
           # input-side weights of every encoder in one reduction; d(hist) in one product; the hidden-side / time-feature
@@ -2558,12 +2461,11 @@ class CLSRNet(object):
         # ---- join the long-term attention branch; its d(hist) contribution was accumulated separately (NOT the early row
         #      scatters: nothing reads their tables before the update phase -- every wait is a barrier packet in front of
         #      the history-row sums)
-        side_dense = self.flush_side and self.overlap and self.dw_stream
         # (deterministic segmented sums update a row with a plain read-modify-write: the target / user row sums of the
         #  same tables -- the @scat branches -- must have finished, which they have long since: the wait costs a packet)
-        keep = () if (self.det_grads and self.sorted_hist_grad) else ("@scat",)
-        self._join(but=keep + ("@encw", "@uupd") if side_dense else keep + ("@uupd",))
-        if side_dense:
+        keep = () if self.det_grads else ("@scat",)
+        self._join(but=keep + ("@encw", "@uupd") if self.overlap else keep + ("@uupd",))
+        if self.overlap:
             # the dense path from here on (batched reduction of every weight gradient, unpacking, later the dense
             # regulariser + Adam) does not meet the embedding path (gradient tables, table regulariser / Adam) again:
             # it stays on the weight-gradient stream, where the last partial-sum kernel has just finished, and the main
@@ -2576,41 +2478,27 @@ class CLSRNet(object):
                 self._dense_grads_final()
         else:
             self._dense_grads_final()
-        # d(hist) = dhist + dhist_lt (the long-term branch's share): the segmented sums add the two on the fly; the
-        # float-atomics path gets one tensor
+        # d(hist) = dhist + dhist_lt (the long-term branch's share): the segmented sums add the two on the fly
         if self._folded:       # (the fused encoder tail added the long-term share and the prologue's shares to d(hist))
             dhist_lt = dM = dR = None
-        elif not (self.sorted_hist_grad and self.hist_grad_two):
-            call("clsr_axpby", dhist, dhist, 1.0, dhist_lt, 1.0, dhist.numel())
-            dhist_lt = None
         # ---- embedding gradients (IndexedSlices values -> dense grad tables + squared norms)
         ss = self.sumsq_tab
-        if self.sorted_hist_grad:
-            # segmented sums over the ids sorted during the forward (119 us vs 350 us for float atomics).  The
-            # lookup sites are independent (distinct norm slots; the two sites of a table meet in fp32 atomics):
-            # category history + category targets, item / user row scatters and the item history run on three
-            # streams that are idle by now instead of one after the other
-            fork = self._fork_point()
-            with self._branch("@lt" if self.split_emb_grad else "@main", after=fork):
-                self._hist_grad_sorted(dhist, dM, dR, Hn, T, seq_len, ls, ss, only="cate", dhist2=dhist_lt, dtarget=dtarget)
-                if not scat_early:
-                    self._scatter_cate_targets(f, dtarget, B)
-                self._dp_hook("table_ready", "cate")
+        # segmented sums over the ids sorted during the forward (119 us vs 350 us for float atomics).  The
+        # lookup sites are independent (distinct norm slots; the two sites of a table meet in fp32 atomics):
+        # category history + category targets, item / user row scatters and the item history run on three
+        # streams that are idle by now instead of one after the other
+        fork = self._fork_point()
+        with self._branch("@lt", after=fork):
+            self._hist_grad_sorted(dhist, dM, dR, Hn, T, seq_len, ls, ss, only="cate", dhist2=dhist_lt, dtarget=dtarget)
             if not scat_early:
-                with self._branch("@aux" if self.split_emb_grad else "@main", after=fork):
-                    self._scatter_user_item_rows(f, dul, dushort, dtarget, Hn, B, hs)
-            self._hist_grad_sorted(dhist, dM, dR, Hn, T, seq_len, ls, ss, only="item", dhist2=dhist_lt, dtarget=dtarget)
-            self._join(but=("@dense", "@uupd"))
-            self._dp_hook("table_ready", "item")
-        else:
-            call("clsr_gather_hist_bwd", dhist, dM, dR, f["item_history"], f["item_cate_history"], hs * T, seq_len,
-                 ls, Hn, T, Di, Dc, hp.contrastive_recent_k, self.tab_grad["item"], self.tab_grad["cate"], ss[0:])
-            call("clsr_scatter_add_rows", dtarget, D, 0, f["items"], 1, B, Di, self.tab_grad["item"], ss[2:])
-            call("clsr_scatter_add_rows", dtarget, D, Di, f["cates"], 1, B, Dc, self.tab_grad["cate"], ss[3:])
-            call("clsr_scatter_add_rows", dul, Du, 0, f["users"], hs, Hn, Du, self.tab_grad["user_long"], ss[6:])
-            call("clsr_scatter_add_rows", dushort, Du, 0, f["users"], hs, Hn, Du, self.tab_grad["user_short"], ss[7:])
-            for k in ("cate", "user_long", "user_short", "item"):
-                self._dp_hook("table_ready", k)
+                self._scatter_cate_targets(f, dtarget, B)
+            self._dp_hook("table_ready", "cate")
+        if not scat_early:
+            with self._branch("@aux", after=fork):
+                self._scatter_user_item_rows(f, dul, dushort, dtarget, Hn, B, hs)
+        self._hist_grad_sorted(dhist, dM, dR, Hn, T, seq_len, ls, ss, only="item", dhist2=dhist_lt, dtarget=dtarget)
+        self._join(but=("@dense", "@uupd"))
+        self._dp_hook("table_ready", "item")
         if apply:
             self._apply_updates()
             self._dense_fork = None
@@ -2882,7 +2770,7 @@ class CLSRNet(object):
         # the Adam clock ticks in the FIRST launch of the update phase (with the user count when there is one): the table
         # path and the dense path both only read it afterwards, so neither waits for the other (the clock used to tick
         # on the dense path, and the table Adam launches waited for the whole weight-gradient reduction: 50 us)
-        tick_early = self.tick_early and not self.capture_grads
+        tick_early = not self.capture_grads
         lr = float(hp.learning_rate)
         if self._ticked:        # (count + clock went out with the row marks at the start of the step)
             self._ticked = False
@@ -2895,11 +2783,11 @@ class CLSRNet(object):
         # dense variables (regulariser + norms, Adam clock, Adam) on the @aux stream beside the table regulariser
         # (single-GPU step with the dense path on the weight-gradient stream: the dense update STAYS on that stream, behind the
         # batched reduction -- on @aux it started two stream hops, ~25 us, after the reduction had finished, and the dense
-        # Adam launch was the last kernel of the step; CLSR_DENSE_UPD_AUX=1: as before)
+        # Adam launch was the last kernel of the step)
         fork = getattr(self, "_dense_fork", None)
-        on_dw = (fork is not None and not self.capture_grads and self.split_emb_grad and self.dense_upd_dw)
+        on_dw = fork is not None and not self.capture_grads
         with (self._branch("@dw0", after=fork, name="@denseupd") if on_dw else
-              self._branch("@main" if (self.capture_grads or not self.split_emb_grad) else "@aux")):
+              self._branch("@main" if self.capture_grads else "@aux")):
             self._join(only="@dense")     # (the batched weight-gradient reduction, see _train_step)
             # (the Adam clock of the step ticks in the same launch: every reader is ordered after it)
             call("clsr_dense_reg_norm_tick_t", self.dense, self.dense_grad, self.seg_off, len(self.dense_names),
@@ -2994,7 +2882,7 @@ class CLSRNet(object):
                         formula="B*T*A0*2 (bf16 z0 written) + Hn*T*(Q + A0)*4 (a, U read) + B*(Q + A0)*4 (q, V read)",
                         mfma_tflops=round(flops / t_mm / 1e12, 2))
         return dict(bound="mfma", kernel=(("hgemm_l0g_kernel (short-term attention layer 0, bf16 MFMA, one wave per history group)"
-                                           if self.l0_fwd_wave and query("clsr_hgemm_l0_group_supported", G, Qs, A0) else
+                                           if query("clsr_hgemm_l0_group_supported", G, Qs, A0) else
                                            "hgemm_kernel<MUL,UV> (short-term attention layer 0, bf16 MFMA)") if bf else
                                           "att_l0_fwd_kernel<5,5> (short-term attention layer 0, one wave per history)"
                                           if self._att_layer0_wave(G, Qs) else
@@ -3059,18 +2947,18 @@ class CLSRNet(object):
                 Wt, Kp = self.packed[key + ".Wp"]
                 return lambda: call("clsr_att_l0_fwd_x1_h", a, Q, q, Q, Wt, Kp, U, A0, V, A0, z0, A0, None, Hn, G, T, Q, A0)
             Wt, Kp = self.packed_h[key + ".Wp"]
-            if self.l0_fwd_wave and query("clsr_hgemm_l0_group_supported", G, Q, A0):
+            if query("clsr_hgemm_l0_group_supported", G, Q, A0):
                 return lambda: call("clsr_hgemm_l0_group", a, Q, q, Q, Wt, Kp, U, A0, V, A0, z0, A0, None, Hn, G, T, Q, A0)
             return lambda: call("clsr_hgemm_mul_uv", a, Q, T, G, q, Q, Wt, Kp, U, A0, V, A0, z0, A0, None, R * T, Q, A0)
         z0 = self._buf(key + ".z0", R * T, A0)
         Wt, Kp = self.packed[key + ".Wp"]
         if self._att_layer0_wave(G, Q):
-            return lambda: call(self.att_l0_fwd_entry, a, Q, q, Q, Wt, Kp, U, A0, V, A0, z0, A0, None, Hn, G, T, Q, A0)
+            return lambda: call("clsr_att_l0_fwd", a, Q, q, Q, Wt, Kp, U, A0, V, A0, z0, A0, None, Hn, G, T, Q, A0)
         return lambda: call("clsr_pgemm", a, Q, T, G, q, Q, None, None, 1, Wt, Kp, None, U, A0, V, A0, z0, A0, 0,
                             None, R * T, Q, A0)
 
     def _att_layer0_wave(self, G, Q):
-        return (not self.bf16) and self.l0_fwd_wave and bool(query("clsr_att_l0_fwd_supported", G, Q, self.A0))
+        return (not self.bf16) and bool(query("clsr_att_l0_fwd_supported", G, Q, self.A0))
 
     def check_abort(self):
         """Raise ``StepAborted`` if a bounded wait of some step gave up -- a grid barrier of the fused heads launches (a

@@ -171,11 +171,11 @@ class SeqNet(CLSRNet):
         out = dict(hist_input=hist, target=target, model_output=mo)
 
         def aux():
-            if early_aux is not None or (training and self.sorted_hist_grad):
+            if early_aux is not None or training:
                 with self._branch("@aux", after=step_start):
                     if early_aux is not None:
                         early_aux()
-                    if training and self.sorted_hist_grad:
+                    if training:
                         self._sort_hist_ids(f, Hn, T, hs)
 
         if kind == "gru4rec":
@@ -416,11 +416,7 @@ class SeqNet(CLSRNet):
         self._join()
         # ---- embedding gradients
         ss = self.sumsq_tab
-        if self.sorted_hist_grad:
-            self._hist_grad_sorted(dhist, dM, dR, Hn, T, seq_len, ls, ss)
-        else:
-            call("clsr_gather_hist_bwd", dhist, dM, dR, f["item_history"], f["item_cate_history"], hs * T, seq_len,
-                 ls, Hn, T, Di, Dc, 1, self.tab_grad["item"], self.tab_grad["cate"], ss[0:])
+        self._hist_grad_sorted(dhist, dM, dR, Hn, T, seq_len, ls, ss)
         call("clsr_scatter_add_rows", dtarget, D, 0, f["items"], 1, B, Di, self.tab_grad["item"], ss[2:])
         call("clsr_scatter_add_rows", dtarget, D, Di, f["cates"], 1, B, Dc, self.tab_grad["cate"], ss[3:])
         if apply:

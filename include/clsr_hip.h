@@ -45,10 +45,6 @@ int clsr_gather_hist_fwd_h(const void* item_tbl, const void* cate_tbl, const int
                            const int* cate_idx, long idx_row_stride, const int* seq_len, int len_stride,
                            int Hn, int T, int Di, int Dc, int recent_k, void* hist, int hist_bf16,
                            float* hist_mean, float* hist_recent, void* stream);
-int clsr_gather_hist_bwd(const float* dhist, const float* dmean, const float* drecent,
-                         const int* item_idx, const int* cate_idx, long idx_row_stride,
-                         const int* seq_len, int len_stride, int Hn, int T, int Di, int Dc, int recent_k,
-                         float* item_grad, float* cate_grad, double* sumsq, void* stream);
 int clsr_gather_rows(const float* tbl, const int* idx, long idx_stride, int N, int C, float* out,
                      int ldo, int col0, void* stream);
 int clsr_scatter_add_rows(const float* src, int ld_src, int col0, const int* idx, long idx_stride, int N,
@@ -143,7 +139,6 @@ int clsr_segsum_multi(const clsr_segsum_desc* descs_host, int n, void* workspace
  * ranges, partial tiles summed in range order by a second launch (csrc/dwwide.hip; reference: the kernel gradients of
  * GRUCell / Time4LSTMCell, rnn_cell_implement.py:129-298).  workspace: clsr_pgemm_dw_wide_workspace_floats floats. */
 int clsr_pgemm_dw_wide_supported(long M, int K, int N);
-int clsr_pgemm_dw_wide_parts(long M, int K, int N);
 long clsr_pgemm_dw_wide_workspace_floats(long M, int K, int N);
 int clsr_pgemm_dw_wide(const float* X, int ldx, const float* Xmul, int ldmul, const float* dY, int ldy, long M, int K, int N,
                        float* workspace, float* dW, int ldw, float* db, int accumulate, void* stream);
@@ -415,12 +410,8 @@ int clsr_att_hist_bwd_x3(const float* dU, int lddu, const float* WuT, int Kpu, c
                          const float* AT, int Kpa, const float* a, int lda, const float* q_hist, int ldqh,
                          long Hn, int T, int Dk, int Q, int A0, int qh, int pieces, float* da, int ldda, float* dq_hist,
                          int lddqh, float* dkeys, int lddk, void* stream);   /* pieces = 2 (2^-16 per term) | 3 (2^-23) */
-/* clsr_att_l0_fwd with the product term as split-bf16 sums on the bf16 matrix pipe (fp32 accumulators that start from
- * U + V; 2^-16 relative per product term): bound by its stores instead of the fp32 matrix pipe */
-int clsr_att_l0_fwd_x3(const float* a, int lda, const float* q, int ldq, const float* Wt, int Kp,
-                       const float* U, int ldu, const float* V, int ldv, float* z0, int ldz, double* stats,
-                       long Hn, int G, int T, int Q, int A0, void* stream);
-/* ... over three bf16 pieces per operand (2^-23 relative per product term: fp32 accuracy on the bf16 matrix pipe) */
+/* clsr_att_l0_fwd with the product term over three bf16 pieces per operand on the bf16 matrix pipe (fp32 accumulators that
+ * start from U + V; 2^-23 relative per product term: fp32 accuracy) */
 int clsr_att_l0_fwd_x6(const float* a, int lda, const float* q, int ldq, const float* Wt, int Kp,
                        const float* U, int ldu, const float* V, int ldv, float* z0, int ldz, double* stats,
                        long Hn, int G, int T, int Q, int A0, void* stream);
@@ -498,8 +489,6 @@ int clsr_hgemm_l0_group(const float* a, int lda, const float* q, int ldq, const 
 /* Y[m, :N] (fp32, =|+=) X[m, :K] . W with a bf16 X (the fp32-X form is clsr_hgemm_f32) */
 int clsr_hgemm_hf32(const void* X, int ldx, const void* Wt, int Kp, float* Y, int ldy, int accumulate,
                     int M, int K, int N, void* stream);
-int clsr_cvt_f32_to_bf16(const float* src, void* dst, long n, void* stream);
-int clsr_cvt_bf16_to_f32(const void* src, float* dst, long n, void* stream);
 int clsr_pgemm_stats_parts(int M);
 int clsr_pgemm_range(const float* X, int ldx, const float* Wt, int Kp, const float* bias, float* Y, int ldy,
                      int accumulate, int Hn, int T, int t0, int t1, int K, int N, void* stream);
@@ -535,8 +524,6 @@ int clsr_pgemm_dw_partial(const float* X, int ldx, int T, int G, const float* Xm
 /* max_outputs / 64 blocks per descriptor; one pass needs 64 * max(4 * ceil(K/16) * ceil(N/16) + ceil(N/64)) (a smaller
  * value is correct too: blocks stride over the remaining work) */
 int clsr_dw_reduce_batch(const clsr_dw_desc* descs_device, int n, int max_outputs, void* stream);
-int clsr_reduce_parts(const float* partial, int nparts, int stride, int n, float scale, float* out,
-                      int accumulate, void* stream);
 
 /* ---- batch normalisation of _fcn_net: tf.layers.batch_normalization(momentum=0.95, eps=1e-4)
  *      base_model.py:673-679 (non-fused: stats over all axes but the last, biased variance) */

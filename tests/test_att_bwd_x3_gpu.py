@@ -172,10 +172,10 @@ def test_layer1_backward_x3_two_passes_with_weight_gradient(M, C1, C0, entry, to
                                          (1, 5, 1, 80, 80), (2100, 2, 33, 48, 80), (11, 8, 18, 80, 80), (5, 4, 20, 40, 80),
                                          (7, 5, 16, 80, 40), (3, 2, 8, 16, 16),   # packed / unpacked ragged tiles
                                          (37, 5, 50, 128, 80), (9, 3, 17, 96, 40)])   # K up to 128: the wide layers of configs[4]
-@pytest.mark.parametrize("entry,tol", [("clsr_att_l0_fwd_x3", 5e-5), ("clsr_att_l0_fwd_x6", 2e-6)])
+@pytest.mark.parametrize("entry,tol", [("clsr_att_l0_fwd_x6", 2e-6)])
 def test_layer0_forward_x3(Hn, G, T, Q, A0, entry, tol):
-    """clsr_att_l0_fwd_x3: z0 = U[h,t] + V[r] + (a[h,t] * q[r]) . Wp with the product as split-bf16 sums: 2^-16 relative per
-    term against float64, statistics consistent with the stored z0, and close to the exact kernel."""
+    """clsr_att_l0_fwd_x6: z0 = U[h,t] + V[r] + (a[h,t] * q[r]) . Wp with the product over three bf16 pieces: 2^-23 relative
+    per term against float64, statistics consistent with the stored z0, and close to the exact kernel."""
     g = torch.Generator().manual_seed(Hn * 3 + T)
     R, M = Hn * G, Hn * G * T
     a, q = rnd(g, Hn * T, Q), rnd(g, R, Q)

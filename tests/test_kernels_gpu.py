@@ -37,7 +37,7 @@ def rnd(gen, *shape, scale=1.0):
 
 # ------------------------------------------------------------------------------- embedding
 @pytest.mark.parametrize("Hn,T,Di,Dc,G", [(37, 10, 32, 8, 5), (64, 50, 32, 8, 1), (9, 7, 96, 32, 3)])
-def test_gather_hist_fwd_bwd(Hn, T, Di, Dc, G):
+def test_gather_hist_fwd(Hn, T, Di, Dc, G):
     g = torch.Generator().manual_seed(1)
     Vi, Vc, k = 301, 23, 3
     item_tbl, cate_tbl = rnd(g, Vi, Di), rnd(g, Vc, Dc)
@@ -67,20 +67,6 @@ def test_gather_hist_fwd_bwd(Hn, T, Di, Dc, G):
     close(hist, exp.float(), name="hist")
     close(hm, (exp * m[..., None]).sum(1) / m.sum(1, keepdim=True), name="hist_mean")
     close(hr, (exp * rec[..., None]).sum(1) / rec.sum(1, keepdim=True), name="hist_recent")
-    # backward
-    dh, dm, dr = rnd(g, Hn, T, D), rnd(g, Hn, D), rnd(g, Hn, D)
-    gi = torch.zeros(Vi, Di, device="cuda")
-    gc = torch.zeros(Vc, Dc, device="cuda")
-    ss = torch.zeros(2, dtype=torch.float64, device="cuda")
-    call("clsr_gather_hist_bwd", dev(dh, torch.float32), dev(dm, torch.float32), dev(dr, torch.float32),
-         d_ii, d_ci, G * T, d_len, G, Hn, T, Di, Dc, k, gi, gc, ss)
-    gfull = dh + m[..., None] * (dm / m.sum(1, keepdim=True))[:, None, :] \
-        + rec[..., None] * (dr / rec.sum(1, keepdim=True))[:, None, :]
-    egi = torch.zeros(Vi, Di, dtype=torch.float64).index_add_(0, iih.reshape(-1), gfull[..., :Di].reshape(-1, Di))
-    egc = torch.zeros(Vc, Dc, dtype=torch.float64).index_add_(0, cih.reshape(-1), gfull[..., Di:].reshape(-1, Dc))
-    close(gi, egi, rtol=1e-4, atol=1e-5, name="item_grad")
-    close(gc, egc, rtol=1e-4, atol=1e-4, name="cate_grad")
-    close(ss, torch.stack([(gfull[..., :Di] ** 2).sum(), (gfull[..., Di:] ** 2).sum()]), rtol=1e-5, name="sumsq")
 
 
 def test_gather_scatter_rows_and_flags():

@@ -28,7 +28,6 @@ def _feed(golden_dir, name, b=0):
 def _run(hp, golden_dir, use_plans, steps=5):
     net = CLSRNet(hp, _dims(hp), device="cuda:0", seed=3)
     net.use_plans = use_plans
-    net.sorted_hist_grad = True
     feeds = [_feed(golden_dir, "iterator_train_sa.npz", b) for b in (0, 1)]
     ev = _feed(golden_dir, "iterator_eval_sa.npz", 0)
     st = [None, None]
