@@ -802,14 +802,11 @@ class CLSRNet(object):
             # flush joins that stream), so they run beside the back-propagating GEMMs instead of between them.
             # ONE such stream: main + @lt + @aux + @dw0 = 4 concurrently active streams; a fifth one was measured at
             # 7.2 ms/step with GPU_MAX_HW_QUEUES=8 (hardware-queue oversubscription) -- do not add streams
-            side = self._side_stream("@dw0")
-            ops.stream_wait(side, self._fork_point())
-            self._dw_launch(X, x_bf16, ldx, T, G, Xmul, ldmul, sc, sh, dY, dy_bf16, ldy, M, K, N, ws, side.cuda_stream)
-            self._dw_async = True
+            self._dw_launch(X, x_bf16, ldx, T, G, Xmul, ldmul, sc, sh, dY, dy_bf16, ldy, M, K, N, ws, self._dw_stream())
         else:
             self._dw_launch(X, x_bf16, ldx, T, G, Xmul, ldmul, sc, sh, dY, dy_bf16, ldy, M, K, N, ws, None)
         pend.append((ws.data_ptr(), dW.data_ptr(), db.data_ptr() if db is not None else 0, 1.0,
-                     query(self._dw_parts_query(x_bf16 or dy_bf16), M), K, N, ldw, acc))
+                     query("clsr_hdw_parts" if self.bf16 else "clsr_pgemm_dw_parts", M), K, N, ldw, acc))
         if not self.defer_dw:
             self._dw_flush()
 
@@ -823,12 +820,15 @@ class CLSRNet(object):
         if self._dw_batch is not None:
             self._dw_batch_wide.append(job)
             return
-        side = None
-        if self.overlap and self._ws_tag == "":
-            side = self._side_stream("@dw0")
-            ops.stream_wait(side, self._fork_point())
-            self._dw_async = True
-        call(self.dw_wide_entry, *job, stream=side.cuda_stream if side is not None else None)
+        call(self.dw_wide_entry, *job, stream=self._dw_stream() if self.overlap and self._ws_tag == "" else None)
+
+    def _dw_stream(self, fork=None):
+        """The weight-gradient stream @dw0 (raw handle), made to wait for ``fork`` (default: everything enqueued on the current
+        stream so far); ``_dw_flush`` will join it."""
+        side = self._side_stream("@dw0")
+        ops.stream_wait(side, fork if fork is not None else self._fork_point())
+        self._dw_async = True
+        return side.cuda_stream
 
     @contextlib.contextmanager
     def _dw_batched(self, late=False):
@@ -857,23 +857,11 @@ class CLSRNet(object):
             # enqueued so far
             fork = self._fork_point()
         name = "clsr_hdw_partial_multi" if self.bf16 else "clsr_pgemm_dw_partial_multi"
-        if self.overlap and self._ws_tag == "":
-            side = self._side_stream("@dw0")
-            ops.stream_wait(side, fork)
-            if jobs:
-                ops.dw_multi(name, jobs, stream=side.cuda_stream)
-            for job in wide:
-                call(self.dw_wide_entry, *job, stream=side.cuda_stream)
-            self._dw_async = True
-        else:
-            if jobs:
-                ops.dw_multi(name, jobs)
-            for job in wide:
-                call(self.dw_wide_entry, *job)
-
-    def _dw_parts_query(self, any_bf16=False):
-        """which query tells how many partial chunks the weight-gradient kernel of this mode writes"""
-        return "clsr_hdw_parts" if self.bf16 else "clsr_pgemm_dw_parts"
+        stream = self._dw_stream(fork) if self.overlap and self._ws_tag == "" else None
+        if jobs:
+            ops.dw_multi(name, jobs, stream=stream)
+        for job in wide:
+            call(self.dw_wide_entry, *job, stream=stream)
 
     def _dw_launch(self, X, x_bf16, ldx, T, G, Xmul, ldmul, sc, sh, dY, dy_bf16, ldy, M, K, N, ws, stream):
         """Partial-sum kernel of one weight gradient: the exact fp32-MFMA kernel, or -- speed mode -- the bf16-MFMA
@@ -924,9 +912,12 @@ class CLSRNet(object):
         for fn in self._dw_after.pop(tag, []):
             fn()
 
-    def _stats_buf(self, M, N):
-        parts = query("clsr_pgemm_stats_parts", M)
-        return self._buf("stats" + self._ws_tag, 1024 * 2 * 256, dtype=torch.float64)[: parts * 2 * N], parts
+    def _stats_buf(self, parts, N):
+        """``parts`` rows of per-block batch-norm partial sums, 2N doubles each, in the statistics workspace of the current
+        stream (no rows -- a forward pass that is not training: None)."""
+        if not parts:
+            return None
+        return self._buf("stats" + self._ws_tag, 1024 * 2 * 256, dtype=torch.float64)[: parts * 2 * N]
 
     def _bn_fwd(self, bn, stats, parts, count, training):
         if training and self.dp_stats_hook is not None and self.dp_comm is not None and 2 * bn.C <= 256:
@@ -980,7 +971,7 @@ class CLSRNet(object):
         then the coefficient + apply pass: ``out`` ends up holding dz of that layer."""
         Wt, Kp = self.packed[wkey]
         parts = query("clsr_pgemm_stats_parts", M)
-        st = self._buf("stats" + self._ws_tag, 1024 * 2 * 256, dtype=torch.float64)[: parts * 2 * N]
+        st = self._stats_buf(parts, N)
         call("clsr_pgemm_bnbwd", dY, ldy_in, Wt, Kp, out, N, z, N,
              bn.scale, bn.shift, bn.mean, bn.invstd, st, M, K, N)
         self._bn_bwd_from_partial(bn, st, parts, out, z, M)
@@ -1331,90 +1322,71 @@ class CLSRNet(object):
             self._gemm(keys, Dk, key + ".A", Hn * T, Dk, Q, a, Q)
             self._gemm(a, Q, key + ".Wu", Hn * T, Q, A0, U, A0)
         self._gemm(q, Q, key + ".Wv", R, Q, A0, V, A0, bias=P[nn + "b_nn_layer0"])
-        if self.bf16:
-            # speed mode: the two (row, step)-level layers on bf16 MFMA with bf16 storage (csrc/hgemm.hip)
-            M = R * T
+        if qh and not hist_x3:
+            # U[h,t] += (a[h,t,:qh] * q_hist[h]) . Wp[:qh]   (in place: every tile reads its own U before storing)
+            self._gemm(a, Q, key + ".Wp1", Hn * T, qh, A0, U, A0, T=T, G=1, Xmul=q_hist, ldmul=qh, addU=U, ldu=A0,
+                       addV=self._buf("att.zeroV", Hn, A0), ldv=A0)
+        M = R * T
+        # (split query: only the target columns stay in the per-(row, step) product, K = Q - qh)
+        entry, args, st, parts = self._att_l0_fwd_launch(key, ".Wp2" if qh else ".Wp", a, q, U, V, z0, Hn, G, T, Q, Q - qh,
+                                                         training)
+        call(entry, *args)
+        self._bn_fwd(bn0, st, parts, M, training)
+        chain = self.bf16 and self._bf16_chain_ok(G, Q - qh)
+        if chain or (not self.bf16 and query("clsr_att_l1_fwd_supported", A0, A1) and M * A1 * 4 < (1 << 30)):
+            # z1 = relu(bn0(z0)) . W1 + b1 on the bf16 matrix pipe with three pieces per operand (csrc/attl1fwd.hip); speed
+            # mode: the same chain kernel with one bf16 piece per operand, z0 / z1 stored as bf16
+            parts = query("clsr_att_l1_fwd_stats_parts", M) if training else 0
+            st = self._stats_buf(parts, A1)
+            Wt, Kp = self.packed[key + ".W1"]
+            call("clsr_att_l1_fwd_x1_h" if chain else "clsr_att_l1_fwd", z0, A0, bn0.scale, bn0.shift, Wt, Kp,
+                 P[nn + "b_nn_layer1"], z1, A1, st, M, A0, A1)
+        elif self.bf16:
+            # speed mode, CLSR_BF16_CHAIN=old: bf16 MFMA with bf16 storage (csrc/hgemm.hip)
             parts = query("clsr_hgemm_stats_parts", M) if training else 0
-            sbuf = self._buf("stats" + self._ws_tag, 1024 * 2 * 256, dtype=torch.float64)
-            st = sbuf[: parts * 2 * A0] if training else None
-            if qh and not hist_x3:
-                self._gemm(a, Q, key + ".Wp1", Hn * T, qh, A0, U, A0, T=T, G=1, Xmul=q_hist, ldmul=qh, addU=U, ldu=A0,
-                           addV=self._buf("att.zeroV", Hn, A0), ldv=A0)
-            # (split query: only the target columns stay in the per-(row, step) product, K = Q - qh)
-            Qe, ae, qe = Q - qh, (a[:, qh:] if qh else a), (q[:, qh:] if qh else q)
-            if self._bf16_chain_ok(G, Qe):
-                # the parity mode's chain kernels with one bf16 piece per operand, z0 / z1 stored as bf16
-                Wt, Kp = self.packed[key + (".Wp2" if qh else ".Wp")]
-                p0 = query("clsr_att_l0_fwd_stats_parts", Hn) if training else 0
-                call("clsr_att_l0_fwd_x1_h", ae, Q, qe, Q, Wt, Kp, U, A0, V, A0, z0, A0,
-                     sbuf[: p0 * 2 * A0] if training else None, Hn, G, T, Qe, A0)
-                self._bn_fwd(bn0, sbuf[: p0 * 2 * A0] if training else None, p0, M, training)
-                p1 = query("clsr_att_l1_fwd_stats_parts", M) if training else 0
-                st = sbuf[: p1 * 2 * A1] if training else None
-                Wt, Kp = self.packed[key + ".W1"]
-                call("clsr_att_l1_fwd_x1_h", z0, A0, bn0.scale, bn0.shift, Wt, Kp, P[nn + "b_nn_layer1"], z1, A1, st, M, A0, A1)
-                self._bn_fwd(bn1, st, p1, M, training)
-                call("clsr_att_out_fwd_h", z1, bn1.scale, bn1.shift, P[nn + "w_nn_output"], P[nn + "b_nn_output"],
-                     seq_len, len_stride, keys, Hn, G, T, A1, Dk, wts, out)
-                return out
-            Wt, Kp = self.packed_h[key + (".Wp2" if qh else ".Wp")]
-            if query("clsr_hgemm_l0_group_supported", G, Qe, A0):
-                # one wave per history group: a / U loaded once per 16 steps and re-used for the G rows
-                p0 = query("clsr_hgemm_l0_group_stats_parts", Hn) if training else 0
-                call("clsr_hgemm_l0_group", ae, Q, qe, Q, Wt, Kp, U, A0, V, A0, z0, A0,
-                     sbuf[: p0 * 2 * A0] if training else None, Hn, G, T, Qe, A0)
-                self._bn_fwd(bn0, sbuf[: p0 * 2 * A0] if training else None, p0, M, training)
-            else:
-                call("clsr_hgemm_mul_uv", ae, Q, T, G, qe, Q, Wt, Kp, U, A0, V, A0, z0, A0, st, M, Qe, A0)
-                self._bn_fwd(bn0, st, parts, M, training)
-            st = sbuf[: parts * 2 * A1] if training else None
+            st = self._stats_buf(parts, A1)
             Wt, Kp = self.packed_h[key + ".W1"]
             call("clsr_hgemm", z0, A0, bn0.scale, bn0.shift, 1, Wt, Kp, P[nn + "b_nn_layer1"], z1, A1, st, M, A0, A1)
-            self._bn_fwd(bn1, st, parts, M, training)
-            call("clsr_att_out_fwd_h", z1, bn1.scale, bn1.shift, P[nn + "w_nn_output"], P[nn + "b_nn_output"],
-                 seq_len, len_stride, keys, Hn, G, T, A1, Dk, wts, out)
-            return out
-        st, parts = self._stats_buf(R * T, A0) if training else (None, 0)
-        if qh:
-            # U[h,t] += (a[h,t,:qh] * q_hist[h]) . Wp[:qh]   (in place: every tile reads its own U before storing)
-            if not hist_x3:
-                self._gemm(a, Q, key + ".Wp1", Hn * T, qh, A0, U, A0, T=T, G=1, Xmul=q_hist, ldmul=qh, addU=U, ldu=A0,
-                           addV=self._buf("att.zeroV", Hn, A0), ldv=A0)
-            if query("clsr_att_l0_fwd_supported", G, Q - qh, A0):
-                # the per-row half (target columns of the query) on the one-wave-per-history kernel: K = Q - qh
-                parts = query("clsr_att_l0_fwd_stats_parts", Hn) if training else 0
-                st = (self._buf("stats" + self._ws_tag, 1024 * 2 * 256, dtype=torch.float64)[: parts * 2 * A0]
-                      if training else None)
-                Wt, Kp = self.packed[key + ".Wp2"]
-                call(self._att_l0_fwd_entry_for(Q - qh), a[:, qh:], Q, q[:, qh:], Q, Wt, Kp, U, A0, V, A0, z0, A0, st, Hn, G, T, Q - qh, A0)
-            else:
-                self._gemm(a[:, qh:], Q, key + ".Wp2", R * T, Q - qh, A0, z0, A0, T=T, G=G, Xmul=q[:, qh:], ldmul=Q,
-                           addU=U, ldu=A0, addV=V, ldv=A0, stats=st)
-        elif query("clsr_att_l0_fwd_supported", G, Q, A0):
-            # one wave per history, a / U loaded once per group of rows (csrc/attl0fwd.hip)
-            parts = query("clsr_att_l0_fwd_stats_parts", Hn) if training else 0
-            st = (self._buf("stats" + self._ws_tag, 1024 * 2 * 256, dtype=torch.float64)[: parts * 2 * A0]
-                  if training else None)
-            Wt, Kp = self.packed[key + ".Wp"]
-            call(self._att_l0_fwd_entry_for(Q), a, Q, q, Q, Wt, Kp, U, A0, V, A0, z0, A0, st, Hn, G, T, Q, A0)
         else:
-            self._gemm(a, Q, key + ".Wp", R * T, Q, A0, z0, A0, T=T, G=G, Xmul=q, ldmul=Q, addU=U, ldu=A0,
-                       addV=V, ldv=A0, stats=st)
-        self._bn_fwd(bn0, st, parts, R * T, training)
-        if query("clsr_att_l1_fwd_supported", A0, A1) and R * T * A1 * 4 < (1 << 30):
-            # z1 = relu(bn0(z0)) . W1 + b1 on the bf16 matrix pipe with three pieces per operand (csrc/attl1fwd.hip)
-            parts = query("clsr_att_l1_fwd_stats_parts", R * T) if training else 0
-            st = (self._buf("stats" + self._ws_tag, 1024 * 2 * 256, dtype=torch.float64)[: parts * 2 * A1]
-                  if training else None)
-            Wt, Kp = self.packed[key + ".W1"]
-            call("clsr_att_l1_fwd", z0, A0, bn0.scale, bn0.shift, Wt, Kp, P[nn + "b_nn_layer1"], z1, A1, st, R * T, A0, A1)
-        else:
-            st, parts = self._stats_buf(R * T, A1) if training else (None, 0)
-            self._gemm(z0, A0, key + ".W1", R * T, A0, A1, z1, A1, bias=P[nn + "b_nn_layer1"], aff=bn0, stats=st)
-        self._bn_fwd(bn1, st, parts, R * T, training)
-        call("clsr_att_out_fwd", z1, bn1.scale, bn1.shift, P[nn + "w_nn_output"], P[nn + "b_nn_output"],
-             seq_len, len_stride, keys, Hn, G, T, A1, Dk, wts, out)
+            parts = query("clsr_pgemm_stats_parts", M) if training else 0
+            st = self._stats_buf(parts, A1)
+            self._gemm(z0, A0, key + ".W1", M, A0, A1, z1, A1, bias=P[nn + "b_nn_layer1"], aff=bn0, stats=st)
+        self._bn_fwd(bn1, st, parts, M, training)
+        call("clsr_att_out_fwd_h" if self.bf16 else "clsr_att_out_fwd", z1, bn1.scale, bn1.shift, P[nn + "w_nn_output"],
+             P[nn + "b_nn_output"], seq_len, len_stride, keys, Hn, G, T, A1, Dk, wts, out)
         return out
+
+    def _att_l0_fwd_launch(self, key, wp, a, q, U, V, z0, Hn, G, T, Q, Qe, training):
+        """Layer 0 of the (row, step)-level attention MLP,  z0 = U[h,t] + V[r] + (a[h,t] * q[r]) . Wp  over the LAST Qe of the Q
+        query columns (weights ``key + wp``), as (entry point, its arguments, batch-norm partial sums, their row count).
+        Precision mode and width select the entry; ``_att_fwd`` launches it, ``_att_layer0_launcher`` times it."""
+        A0, M, c0 = self.A0, Hn * G * T, Q - Qe
+        ae, qe = (a[:, c0:], q[:, c0:]) if c0 else (a, q)
+        if self.bf16 and self._bf16_chain_ok(G, Qe):
+            # the parity mode's chain kernel with one bf16 piece per operand, z0 stored as bf16
+            wave = "clsr_att_l0_fwd_x1_h", self.packed, "clsr_att_l0_fwd_stats_parts"
+        elif self.bf16:
+            # one wave per history group: a / U loaded once per 16 steps and re-used for the G rows
+            wave = (("clsr_hgemm_l0_group", self.packed_h, "clsr_hgemm_l0_group_stats_parts")
+                    if query("clsr_hgemm_l0_group_supported", G, Qe, A0) else None)
+        else:
+            # one wave per history, a / U loaded once per group of rows (csrc/attl0fwd.hip)
+            wave = ((self._att_l0_fwd_entry_for(Qe), self.packed, "clsr_att_l0_fwd_stats_parts")
+                    if query("clsr_att_l0_fwd_supported", G, Qe, A0) else None)
+        if wave is not None:
+            entry, images, parts_query = wave
+            parts = query(parts_query, Hn) if training else 0
+            st = self._stats_buf(parts, A0)
+            Wt, Kp = images[key + wp]
+            return entry, (ae, Q, qe, Q, Wt, Kp, U, A0, V, A0, z0, A0, st, Hn, G, T, Qe, A0), st, parts
+        # position-tiled: bf16 MFMA with bf16 storage (csrc/hgemm.hip) / the fp32-MFMA GEMM with the product prologue
+        parts = query("clsr_hgemm_stats_parts" if self.bf16 else "clsr_pgemm_stats_parts", M) if training else 0
+        st = self._stats_buf(parts, A0)
+        if self.bf16:
+            Wt, Kp = self.packed_h[key + wp]
+            return "clsr_hgemm_mul_uv", (ae, Q, T, G, qe, Q, Wt, Kp, U, A0, V, A0, z0, A0, st, M, Qe, A0), st, parts
+        Wt, Kp = self.packed[key + wp]
+        return "clsr_pgemm", (ae, Q, T, G, qe, Q, None, None, 1, Wt, Kp, None, U, A0, V, A0, z0, A0, 0, st, M, Qe, A0), st, parts
 
     def _att_bwd(self, key, scope, dout, keys, q, dkeys, Hn, G, T, Dk, Q, seq_len, len_stride, q_hist=None,
                  dq_hist=None, dw_in=None):
@@ -1458,28 +1430,20 @@ class CLSRNet(object):
         da = self._buf(key + ".da", Hn * T, Q)
         dq = self._buf(key + ".dq", R, Q)
         dV = self._buf(key + ".dV", R, A0)
-        if self.bf16:
-            # speed mode: dz1 is recomputed from (z1, ds) in the prologue of the GEMM that back-propagates through the
-            # second layer; TWO passes over (z1, z0): the batch-norm sums of layer 0, then the finished dz0 (+ dz1 for the
-            # weight gradient) -- no separate dy1-apply / bn-apply sweeps (csrc/hgemm.hip: clsr_hgemm_att_l1_bwd)
-            M = R * T
-            if self._bf16_chain_ok(G, Q - qh):
-                return self._att_bwd_chain_h(key, scope, nn, bn0, bn1, a, q, keys, dkeys, z0, z1, dz0, ds, da, dq, dV, dW0,
-                                             Hn, G, R, T, Dk, Q, qh, q_hist, dq_hist)
-            Wt, Kp = self.packed_h[key + ".W1^T"]
-            parts = query("clsr_hgemm_stats_parts", M)
-            st = self._buf("stats" + self._ws_tag, 1024 * 2 * 256, dtype=torch.float64)[: parts * 2 * A0]
-            wo = P[nn + "w_nn_output"]
-            call("clsr_hgemm_att_l1_bwd", z1, A1, ds, bn1.scale, bn1.shift, wo, bn1.coef, Wt, Kp, z0, A0, bn0.scale,
-                 bn0.shift, bn0.mean, bn0.invstd, None, None, 0, None, 0, st, M, A1, A0)
-            self._bn_bwd_coef(bn0, st, parts, M)
-            call("clsr_hgemm_att_l1_bwd", z1, A1, ds, bn1.scale, bn1.shift, wo, bn1.coef, Wt, Kp, z0, A0, bn0.scale,
-                 bn0.shift, None, None, bn0.coef, dz1, A1, dz0, A0, None, M, A1, A0)
-            self._dw(z0, A0, dz1, A1, M, A0, A1, Gd[nn + "w_nn_layer1"], A1, db=Gd[nn + "b_nn_layer1"], aff=bn0,
-                     x_bf16=1, dy_bf16=1)
-            Qe, ae, qe = Q - qh, (a[:, qh:] if qh else a), (q[:, qh:] if qh else q)
-            self._dw(ae, Q, dz0, A0, M, Qe, A0, dW0[3 * Q + qh:4 * Q], A0, T=T, G=G, Xmul=qe, ldmul=Q, dy_bf16=1)
-            Wt, Kp = self.packed_h[key + (".Wp2^T" if qh else ".Wp^T")]
+        M = R * T
+        # (split query: only the target columns [qh, Q) stay in the per-(row, step) product; qh = 0: all of them)
+        Qe = Q - qh
+        ae, qe, dae, dqe = (a[:, qh:], q[:, qh:], da[:, qh:], dq[:, qh:]) if qh else (a, q, da, dq)
+        wpT, dWp = (".Wp2^T" if qh else ".Wp^T"), dW0[3 * Q + qh:4 * Q]
+        # speed mode on the parity mode's chain kernels: csrc/attbwdx3.hip with NP = 1, ST = bf16 (bf16 z0 / z1 / dz0)
+        chain = self.bf16 and self._bf16_chain_ok(G, Qe)
+        if self.bf16 and not chain:
+            # speed mode, CLSR_BF16_CHAIN=old: dz1 is recomputed from (z1, ds) in the prologue of the GEMM that back-propagates
+            # through the second layer; TWO passes over (z1, z0): the batch-norm sums of layer 0, then the finished dz0 (+ dz1
+            # for the weight gradient) -- no separate dy1-apply / bn-apply sweeps (csrc/hgemm.hip: clsr_hgemm_att_l1_bwd)
+            self._att_l1_bwd_dz1(key, nn, z0, z1, ds, dz1, dz0, M)
+            self._dw(ae, Q, dz0, A0, M, Qe, A0, dWp, A0, T=T, G=G, Xmul=qe, ldmul=Q, dy_bf16=1)
+            Wt, Kp = self.packed_h[key + wpT]
             dU = self._buf(key + ".dU", Hn * T, A0)
             if query("clsr_att_l0_bwd_h_supported", G, Qe, A0):
                 # da, dq, dU, dV in one pass over dz0; daq = dz0 . Wp^T is never written (csrc/hattbwd.hip)
@@ -1487,125 +1451,136 @@ class CLSRNet(object):
                 wu_in = not qh and not self._hist_bwd_x3(Dk, Q, 0)
                 Wu, Kpu = self.packed_h[key + ".Wu^T"] if wu_in else (None, Kp)
                 assert Kpu == Kp
-                call("clsr_att_l0_bwd_h", dz0, A0, Wt, Wu, Kp, ae, Q, qe, Q, Hn, G, T, Qe, A0,
-                     da[:, qh:] if qh else da, Q, dq[:, qh:] if qh else dq, Q, dU, A0, dV, A0)
+                call("clsr_att_l0_bwd_h", dz0, A0, Wt, Wu, Kp, ae, Q, qe, Q, Hn, G, T, Qe, A0, dae, Q, dqe, Q, dU, A0, dV, A0)
                 if qh:
-                    # the V path over ALL query columns (dq[:, :qh] was cleared with the step's accumulators), the weight
-                    # gradient of the history-level share of the product term; the rest of that share: _att_bwd_hist
-                    self._gemm(dV, A0, key + ".Wv^T", R, A0, Q, dq, Q, acc=1)
-                    self._dw(a, Q, dU, A0, Hn * T, qh, A0, dW0[3 * Q:3 * Q + qh], A0, T=T, G=1, Xmul=q_hist, ldmul=qh)
+                    self._att_bwd_qh_shares(key, a, q_hist, dU, dV, dq, dW0, Hn, R, T, Q, qh)
                 return self._att_bwd_hist(key, scope, nn, a, q, keys, dkeys, dU, dV, da, dq, dW0, Hn, R, T, Dk, Q, qh,
                                           da_has_u=Wu is not None, q_hist=q_hist, dq_hist=dq_hist)
-            else:
-                daq = self._buf(key + ".daq", M, Q, dtype=BF)
-                call("clsr_hgemm", dz0, A0, None, None, 0, Wt, Kp, None, daq, Q, None, M, A0, Q)
-                call("clsr_att_prod_bwd_h", daq, Q, a, Q, q, Q, Hn, G, T, Q, da, Q, dq, Q, 0)
-                call("clsr_att_z0_bwd_reduce_h", dz0, Hn, G, T, A0, dU, dV)
+            daq = self._buf(key + ".daq", M, Q, dtype=BF)
+            call("clsr_hgemm", dz0, A0, None, None, 0, Wt, Kp, None, daq, Q, None, M, A0, Q)
+            call("clsr_att_prod_bwd_h", daq, Q, a, Q, q, Q, Hn, G, T, Q, da, Q, dq, Q, 0)
+            call("clsr_att_z0_bwd_reduce_h", dz0, Hn, G, T, A0, dU, dV)
             return self._att_bwd_hist(key, scope, nn, a, q, keys, dkeys, dU, dV, da, dq, dW0, Hn, R, T, Dk, Q, 0)
         x3b = self.att_bwd in ("x3", "x6")
-        if x3b and query("clsr_att_l1_bwd_x3_supported", A1, A0) and (R * T * A0 + 80) * 4 < (1 << 31) - 1:
-            # the same two passes as split-bf16 products; pass 2 also accumulates dW1 / db1 (dz1 is never stored)
-            M = R * T
-            Wt, Kp = self.packed[key + ".W1^T"]
-            parts = query("clsr_att_l1_bwd_x3_parts", M)
-            st = self._buf("stats" + self._ws_tag, 1024 * 2 * 256, dtype=torch.float64)[: parts * 2 * A0]
-            wo = P[nn + "w_nn_output"]
-            call(self._l1x, z1, A1, ds, bn1.scale, bn1.shift, wo, bn1.coef, Wt, Kp, z0, A0, bn0.scale,
-                 bn0.shift, bn0.mean, bn0.invstd, None, None, 0, None, st, M, A1, A0)
-            self._bn_bwd_coef(bn0, st, parts, M)
-            ws = self._buf(key + ".dw1x_ws", parts * query("clsr_dw_chunk_floats"))
-            call(self._l1x, z1, A1, ds, bn1.scale, bn1.shift, wo, bn1.coef, Wt, Kp, z0, A0, bn0.scale,
-                 bn0.shift, None, None, bn0.coef, dz0, A0, ws, None, M, A1, A0)
-            self._dw_fused(ws, parts, A0, A1, Gd[nn + "w_nn_layer1"], A1, db=Gd[nn + "b_nn_layer1"])
+        if chain or (x3b and query("clsr_att_l1_bwd_x3_supported", A1, A0) and (M * A0 + 80) * 4 < (1 << 31) - 1):
+            # two passes over (z1, z0) as split-bf16 products; pass 2 also accumulates dW1 / db1 (dz1 is never stored)
+            self._att_l1_bwd_x(key, nn, z0, z1, ds, dz0, M)
         elif query("clsr_att_l1_bwd_supported", A1, A0):
             # two passes over (z1, z0) with dz1 recomputed in the GEMM prologue: the batch-norm sums of layer 0, then the
             # finished dz0 (+ dz1 for the weight gradient) -- no dy1-apply / bn-apply sweeps (csrc/attl1bwd.hip)
-            M = R * T
-            Wt, Kp = self.packed[key + ".W1^T"]
-            parts = query("clsr_att_l1_bwd_stats_parts", M)
-            st = self._buf("stats" + self._ws_tag, 1024 * 2 * 256, dtype=torch.float64)[: parts * 2 * A0]
-            wo = P[nn + "w_nn_output"]
-            call("clsr_att_l1_bwd", z1, A1, ds, bn1.scale, bn1.shift, wo, bn1.coef, Wt, Kp, z0, A0, bn0.scale,
-                 bn0.shift, bn0.mean, bn0.invstd, None, None, 0, None, 0, st, M, A1, A0)
-            self._bn_bwd_coef(bn0, st, parts, M)
-            call("clsr_att_l1_bwd", z1, A1, ds, bn1.scale, bn1.shift, wo, bn1.coef, Wt, Kp, z0, A0, bn0.scale,
-                 bn0.shift, None, None, bn0.coef, dz1, A1, dz0, A0, None, M, A1, A0)
-            self._dw(z0, A0, dz1, A1, M, A0, A1, Gd[nn + "w_nn_layer1"], A1, db=Gd[nn + "b_nn_layer1"], aff=bn0)
+            self._att_l1_bwd_dz1(key, nn, z0, z1, ds, dz1, dz0, M)
         else:
-            call("clsr_att_dy1_apply", z1, ds, bn1.scale, bn1.shift, P[nn + "w_nn_output"], bn1.coef, R * T, A1, dz1)
+            call("clsr_att_dy1_apply", z1, ds, bn1.scale, bn1.shift, P[nn + "w_nn_output"], bn1.coef, M, A1, dz1)
             # layer 1: z1 = relu(bn0(z0)) . W1 + b1
-            self._dw(z0, A0, dz1, A1, R * T, A0, A1, Gd[nn + "w_nn_layer1"], A1, db=Gd[nn + "b_nn_layer1"], aff=bn0)
-            self._gemm_bnbwd(dz1, A1, key + ".W1^T", R * T, A1, A0, dz0, bn0, z0)
+            self._dw(z0, A0, dz1, A1, M, A0, A1, Gd[nn + "w_nn_layer1"], A1, db=Gd[nn + "b_nn_layer1"], aff=bn0)
+            self._gemm_bnbwd(dz1, A1, key + ".W1^T", M, A1, A0, dz0, bn0, z0)
         # layer 0 (re-associated): z0 = U[h,t] + V[r] + (a[h,t]*q[r]) . Wp
+        # ONE pass over dz0 for da, dq, dU, dV: with the partial sums of dWp folded in (csrc/attbwdx3.hip; speed mode: one bf16
+        # piece, bf16 dz0; wide product terms: two launches over the column halves) or on the fp32 matrix pipe behind a
+        # weight-gradient launch of its own (csrc/hattbwd.hip); daq = dz0 . Wp^T is never written
         x3b = self.att_bwd_l0 in ("x3", "x6")
+        l0x = "clsr_att_l0_bwd_x1_h" if chain else (self._l0x if x3b and query("clsr_att_l0_bwd_x3_supported", G, Qe, A0)
+                                                    else None)
+        halves = l0x is None and x3b and self._l0_bwd_halves_ok(G, Qe)
+        if not (l0x or halves):
+            self._dw(ae, Q, dz0, A0, M, Qe, A0, dWp, A0, T=T, G=G, Xmul=qe, ldmul=Q)
+        # G == 1: dU, the sum of dz0 over the rows of a history group, IS dz0 -- the kernels are passed None (qh > 0 implies
+        # G > 1; the speed mode's dz0 is bf16 and never doubles as the fp32 dU)
+        own_dU = G > 1 or self.bf16
+        dU = self._buf(key + ".dU", Hn * T, A0) if own_dU else dz0
+        dU_out = dU if own_dU else None
+        v_path = True
+        if halves:
+            self._att_l0_bwd_x3_halves(key, wpT, dz0, a, q, da, dq, dU_out, dV, dW0, Hn, G, R, T, Q, qh, Qe)
+        elif l0x:
+            Wt, Kp = self.packed[key + wpT]
+            parts = query("clsr_att_l0_bwd_x1_h_parts" if chain else "clsr_att_l0_bwd_x3_parts", Hn)
+            ws = self._buf(key + ".dwpx_ws", parts * query("clsr_dw_chunk_floats"))
+            call(l0x, dz0, A0, Wt, Kp, ae, Q, qe, Q, Hn, G, T, Qe, A0, dae, Q, dqe, Q, dU_out, A0, dV, A0, ws)
+            self._dw_fused(ws, parts, Qe, A0, dWp, A0)
+        elif query("clsr_att_l0_bwd_supported", G, Qe, A0):
+            Wt, Kp = self.packed[key + wpT]
+            call("clsr_att_l0_bwd", dz0, A0, Wt, Kp, ae, Q, qe, Q, Hn, G, T, Qe, A0, dae, Q, dqe, Q, dU_out, A0, dV, A0)
+        elif qh:
+            # position-tiled, split query
+            daq = self._buf(key + ".daq2", M, Qe)
+            self._gemm(dz0, A0, key + wpT, M, A0, Qe, daq, Qe)
+            call("clsr_att_z0_bwd_reduce", dz0, Hn, G, T, A0, dU, dV)
+            # dq = dV . Wv^T first (all Q columns), then the per-row product term is added to its target columns
+            self._gemm(dV, A0, key + ".Wv^T", R, A0, Q, dq, Q)
+            call("clsr_att_prod_bwd_ld", daq, Qe, ae, Q, qe, Q, Hn, G, T, Qe, dae, Q, dqe, Q, 1)
+            v_path = False
+        else:
+            # position-tiled
+            daq = self._buf(key + ".daq", M, Q)
+            self._gemm(dz0, A0, key + wpT, M, A0, Q, daq, Q)
+            call("clsr_att_prod_bwd", daq, a, q, Hn, G, T, Q, da, dq)
+            call("clsr_att_z0_bwd_reduce", dz0, Hn, G, T, A0, dU_out, dV)
         if qh:
-            Q2 = Q - qh
-            l0x3 = x3b and query("clsr_att_l0_bwd_x3_supported", G, Q2, A0)
-            halves = (not l0x3) and x3b and self._l0_bwd_halves_ok(G, Q2)
-            if not (l0x3 or halves):
-                self._dw(a[:, qh:], Q, dz0, A0, R * T, Q2, A0, dW0[3 * Q + qh:4 * Q], A0, T=T, G=G, Xmul=q[:, qh:],
-                         ldmul=Q)
-            dU = self._buf(key + ".dU", Hn * T, A0)
-            if halves:
-                self._att_l0_bwd_x3_halves(key, ".Wp2^T", dz0, a, q, da, dq, dU, dV, dW0, Hn, G, R, T, Q, qh, Q2)
-                self._gemm(dV, A0, key + ".Wv^T", R, A0, Q, dq, Q, acc=1)
-            elif l0x3:
-                # the same pass as split-bf16 products, with the partial sums of dWp[qh:] (csrc/attbwdx3.hip)
-                Wt, Kp = self.packed[key + ".Wp2^T"]
-                parts = query("clsr_att_l0_bwd_x3_parts", Hn)
-                ws = self._buf(key + ".dwpx_ws", parts * query("clsr_dw_chunk_floats"))
-                call(self._l0x, dz0, A0, Wt, Kp, a[:, qh:], Q, q[:, qh:], Q, Hn, G, T, Q2, A0, da[:, qh:], Q,
-                     dq[:, qh:], Q, dU, A0, dV, A0, ws)
-                self._dw_fused(ws, parts, Q2, A0, dW0[3 * Q + qh:4 * Q], A0)
-                self._gemm(dV, A0, key + ".Wv^T", R, A0, Q, dq, Q, acc=1)
-            elif query("clsr_att_l0_bwd_supported", G, Q2, A0):
-                # per-row half in one pass over dz0 (csrc/hattbwd.hip): da / dq of the target columns, dU, dV; then the V
-                # path over ALL query columns is added (dq[:, :qh] was cleared with the step's accumulators)
-                Wt, Kp = self.packed[key + ".Wp2^T"]
-                call("clsr_att_l0_bwd", dz0, A0, Wt, Kp, a[:, qh:], Q, q[:, qh:], Q, Hn, G, T, Q2, A0, da[:, qh:], Q,
-                     dq[:, qh:], Q, dU, A0, dV, A0)
-                self._gemm(dV, A0, key + ".Wv^T", R, A0, Q, dq, Q, acc=1)
-            else:
-                daq = self._buf(key + ".daq2", R * T, Q2)
-                self._gemm(dz0, A0, key + ".Wp2^T", R * T, A0, Q2, daq, Q2)
-                call("clsr_att_z0_bwd_reduce", dz0, Hn, G, T, A0, dU, dV)
-                # dq = dV . Wv^T first (all Q columns), then the per-row product term is added to its target columns
-                self._gemm(dV, A0, key + ".Wv^T", R, A0, Q, dq, Q)
-                call("clsr_att_prod_bwd_ld", daq, Q2, a[:, qh:], Q, q[:, qh:], Q, Hn, G, T, Q2, da[:, qh:], Q,
-                     dq[:, qh:], Q, 1)
-            # history-level share of the product term: through dU = sum over the group's rows of dz0
-            self._dw(a, Q, dU, A0, Hn * T, qh, A0, dW0[3 * Q:3 * Q + qh], A0, T=T, G=1, Xmul=q_hist, ldmul=qh)
+            self._att_bwd_qh_shares(key, a, q_hist, dU, dV, dq, dW0, Hn, R, T, Q, qh, v_path=v_path)
             if not self._hist_bwd_x3(Dk, Q, qh):      # (else: inside the fused history-level kernel, _att_bwd_hist)
                 daq1 = self._buf(key + ".daq1", Hn * T, qh)
                 self._gemm(dU, A0, key + ".Wp1^T", Hn * T, A0, qh, daq1, qh)
                 call("clsr_att_prod_bwd_ld", daq1, qh, a, Q, q_hist, qh, Hn, 1, T, qh, da, Q, dq_hist, qh, 1)
-        else:
-            l0x3 = x3b and query("clsr_att_l0_bwd_x3_supported", G, Q, A0)
-            halves = (not l0x3) and x3b and self._l0_bwd_halves_ok(G, Q)
-            if not (l0x3 or halves):
-                self._dw(a, Q, dz0, A0, R * T, Q, A0, dW0[3 * Q:4 * Q], A0, T=T, G=G, Xmul=q, ldmul=Q)
-            dU = dz0 if G == 1 else self._buf(key + ".dU", Hn * T, A0)
-            if halves:
-                self._att_l0_bwd_x3_halves(key, ".Wp^T", dz0, a, q, da, dq, None if G == 1 else dU, dV, dW0, Hn, G, R, T, Q, 0, Q)
-            elif l0x3:
-                Wt, Kp = self.packed[key + ".Wp^T"]
-                parts = query("clsr_att_l0_bwd_x3_parts", Hn)
-                ws = self._buf(key + ".dwpx_ws", parts * query("clsr_dw_chunk_floats"))
-                call(self._l0x, dz0, A0, Wt, Kp, a, Q, q, Q, Hn, G, T, Q, A0, da, Q, dq, Q,
-                     None if G == 1 else dU, A0, dV, A0, ws)
-                self._dw_fused(ws, parts, Q, A0, dW0[3 * Q:4 * Q], A0)
-            elif query("clsr_att_l0_bwd_supported", G, Q, A0):
-                # da, dq, dU, dV in one pass over dz0 on the fp32 matrix pipe; daq = dz0 . Wp^T is never written
-                Wt, Kp = self.packed[key + ".Wp^T"]
-                call("clsr_att_l0_bwd", dz0, A0, Wt, Kp, a, Q, q, Q, Hn, G, T, Q, A0, da, Q, dq, Q,
-                     None if G == 1 else dU, A0, dV, A0)
-            else:
-                daq = self._buf(key + ".daq", R * T, Q)
-                self._gemm(dz0, A0, key + ".Wp^T", R * T, A0, Q, daq, Q)
-                call("clsr_att_prod_bwd", daq, a, q, Hn, G, T, Q, da, dq)
-                call("clsr_att_z0_bwd_reduce", dz0, Hn, G, T, A0, None if G == 1 else dU, dV)
         return self._att_bwd_hist(key, scope, nn, a, q, keys, dkeys, dU, dV, da, dq, dW0, Hn, R, T, Dk, Q, qh,
                                   q_hist=q_hist, dq_hist=dq_hist)
+
+    def _att_bwd_qh_shares(self, key, a, q_hist, dU, dV, dq, dW0, Hn, R, T, Q, qh, v_path=True):
+        """Split query, behind the layer-0 backward of the per-row half: the V path over ALL query columns (dq[:, :qh] was
+        cleared with the step's accumulators; ``v_path=False``: the caller has written it) and the weight gradient of the
+        history-level share of the product term, through dU = sum over the group's rows of dz0.  The rest of that share:
+        ``_att_bwd_hist``."""
+        A0 = self.A0
+        if v_path:
+            self._gemm(dV, A0, key + ".Wv^T", R, A0, Q, dq, Q, acc=1)
+        self._dw(a, Q, dU, A0, Hn * T, qh, A0, dW0[3 * Q:3 * Q + qh], A0, T=T, G=1, Xmul=q_hist, ldmul=qh)
+
+    def _att_l1_bwd_head(self, key, nn, z0, z1, ds, images):
+        """Leading arguments that every two-pass layer-1 backward entry shares, in both passes."""
+        A0, A1 = self.A0, self.A1
+        bn0, bn1 = self.bn[nn + "batch_normalization/"], self.bn[nn + "batch_normalization_1/"]
+        Wt, Kp = images[key + ".W1^T"]
+        return (z1, A1, ds, bn1.scale, bn1.shift, self.P[nn + "w_nn_output"], bn1.coef, Wt, Kp, z0, A0, bn0.scale, bn0.shift)
+
+    def _att_l1_bwd_dz1(self, key, nn, z0, z1, ds, dz1, dz0, M):
+        """Layer-1 backward of the attention MLP by the entries that store dz1 -- clsr_att_l1_bwd (fp32-input MFMAs,
+        CLSR_ATT_BWD=fp32) and clsr_hgemm_att_l1_bwd (speed mode, CLSR_BF16_CHAIN=old): pass 1 (BN-0 sums), the BN-0
+        coefficients, pass 2 (dz0, dz1), then the weight-gradient launch over (z0, dz1)."""
+        Gd, A0, A1, h = self.Gd, self.A0, self.A1, int(self.bf16)
+        bn0 = self.bn[nn + "batch_normalization/"]
+        entry, images, parts_query = (("clsr_hgemm_att_l1_bwd", self.packed_h, "clsr_hgemm_stats_parts") if h else
+                                      ("clsr_att_l1_bwd", self.packed, "clsr_att_l1_bwd_stats_parts"))
+        head = self._att_l1_bwd_head(key, nn, z0, z1, ds, images)
+        parts = query(parts_query, M)
+        st = self._stats_buf(parts, A0)
+        call(entry, *head, bn0.mean, bn0.invstd, None, None, 0, None, 0, st, M, A1, A0)
+        self._bn_bwd_coef(bn0, st, parts, M)
+        call(entry, *head, None, None, bn0.coef, dz1, A1, dz0, A0, None, M, A1, A0)
+        self._dw(z0, A0, dz1, A1, M, A0, A1, Gd[nn + "w_nn_layer1"], A1, db=Gd[nn + "b_nn_layer1"], aff=bn0, x_bf16=h,
+                 dy_bf16=h)
+
+    def _att_l1_bwd_x_passes(self, key, nn, z0, z1, ds, dz0, M):
+        """The same two passes by the entries that fold the weight gradient in -- clsr_att_l1_bwd_x3 / _x6 (``self._l1x``) and,
+        speed mode, clsr_att_l1_bwd_x1_h: (pass 1, pass 2, ws, st, parts).  Pass 1 leaves the BN-0 sums in ``st``; pass 2 writes
+        dz0 and the ``parts`` partial chunks of dW1 / db1 into ``ws``.  (``bench_att_l1_bwd`` times pass 2 alone.)"""
+        A0, A1 = self.A0, self.A1
+        bn0 = self.bn[nn + "batch_normalization/"]
+        entry = "clsr_att_l1_bwd_x1_h" if self.bf16 else self._l1x
+        head = self._att_l1_bwd_head(key, nn, z0, z1, ds, self.packed)
+        parts = query("clsr_att_l1_bwd_x3_parts", M)
+        st = self._stats_buf(parts, A0)
+        ws = self._buf(key + ".dw1x_ws", parts * query("clsr_dw_chunk_floats"))
+        return (lambda: call(entry, *head, bn0.mean, bn0.invstd, None, None, 0, None, st, M, A1, A0),
+                lambda: call(entry, *head, None, None, bn0.coef, dz0, A0, ws, None, M, A1, A0), ws, st, parts)
+
+    def _att_l1_bwd_x(self, key, nn, z0, z1, ds, dz0, M):
+        """Pass 1, the BN-0 coefficients, pass 2 of ``_att_l1_bwd_x_passes``; dW1 / db1 join the batched reduction."""
+        Gd, A0, A1 = self.Gd, self.A0, self.A1
+        pass1, pass2, ws, st, parts = self._att_l1_bwd_x_passes(key, nn, z0, z1, ds, dz0, M)
+        pass1()
+        self._bn_bwd_coef(self.bn[nn + "batch_normalization/"], st, parts, M)
+        pass2()
+        self._dw_fused(ws, parts, A0, A1, Gd[nn + "w_nn_layer1"], A1, db=Gd[nn + "b_nn_layer1"])
 
     def _l0_bwd_halves_ok(self, G, Qw):
         """wide product term (80 < Qw <= 160 query columns: BASELINE configs[4]): the one-pass layer-0 backward with folded dWp
@@ -1642,40 +1617,6 @@ class CLSRNet(object):
         return bool(self.bf16_chain and A0 % 8 == 0 and A1 % 8 == 0
                     and query("clsr_att_l0_fwd_supported", G, Qe, A0) and query("clsr_att_l1_fwd_supported", A0, A1)
                     and query("clsr_att_l1_bwd_x3_supported", A1, A0) and query("clsr_att_l0_bwd_x3_supported", G, Qe, A0))
-
-    def _att_bwd_chain_h(self, key, scope, nn, bn0, bn1, a, q, keys, dkeys, z0, z1, dz0, ds, da, dq, dV, dW0, Hn, G, R, T,
-                         Dk, Q, qh, q_hist, dq_hist):
-        """Speed-mode tail of ``_att_bwd`` behind the BN-1 coefficients: two passes over (z1, z0) -- the second one writes
-        dz0 (bf16) and the partial chunks of dW1 / db1 --, then ONE pass over dz0 for da, dq, dU, dV and dWp
-        (csrc/attbwdx3.hip with NP = 1, ST = bf16)."""
-        P, Gd, A0, A1 = self.P, self.Gd, self.A0, self.A1
-        M = R * T
-        Wt, Kp = self.packed[key + ".W1^T"]
-        parts = query("clsr_att_l1_bwd_x3_parts", M)
-        st = self._buf("stats" + self._ws_tag, 1024 * 2 * 256, dtype=torch.float64)[: parts * 2 * A0]
-        wo = P[nn + "w_nn_output"]
-        call("clsr_att_l1_bwd_x1_h", z1, A1, ds, bn1.scale, bn1.shift, wo, bn1.coef, Wt, Kp, z0, A0, bn0.scale,
-             bn0.shift, bn0.mean, bn0.invstd, None, None, 0, None, st, M, A1, A0)
-        self._bn_bwd_coef(bn0, st, parts, M)
-        ws = self._buf(key + ".dw1x_ws", parts * query("clsr_dw_chunk_floats"))
-        call("clsr_att_l1_bwd_x1_h", z1, A1, ds, bn1.scale, bn1.shift, wo, bn1.coef, Wt, Kp, z0, A0, bn0.scale,
-             bn0.shift, None, None, bn0.coef, dz0, A0, ws, None, M, A1, A0)
-        self._dw_fused(ws, parts, A0, A1, Gd[nn + "w_nn_layer1"], A1, db=Gd[nn + "b_nn_layer1"])
-        Qe, ae, qe = Q - qh, (a[:, qh:] if qh else a), (q[:, qh:] if qh else q)
-        dU = self._buf(key + ".dU", Hn * T, A0)
-        Wt, Kp = self.packed[key + (".Wp2^T" if qh else ".Wp^T")]
-        parts = query("clsr_att_l0_bwd_x1_h_parts", Hn)
-        ws = self._buf(key + ".dwpx_ws", parts * query("clsr_dw_chunk_floats"))
-        call("clsr_att_l0_bwd_x1_h", dz0, A0, Wt, Kp, ae, Q, qe, Q, Hn, G, T, Qe, A0, da[:, qh:] if qh else da, Q,
-             dq[:, qh:] if qh else dq, Q, dU, A0, dV, A0, ws)
-        self._dw_fused(ws, parts, Qe, A0, dW0[3 * Q + qh:4 * Q], A0)
-        if qh:
-            # the V path over ALL query columns (dq[:, :qh] was cleared with the step's accumulators), the weight
-            # gradient of the history-level share of the product term; the rest of that share: _att_bwd_hist
-            self._gemm(dV, A0, key + ".Wv^T", R, A0, Q, dq, Q, acc=1)
-            self._dw(a, Q, dU, A0, Hn * T, qh, A0, dW0[3 * Q:3 * Q + qh], A0, T=T, G=1, Xmul=q_hist, ldmul=qh)
-        return self._att_bwd_hist(key, scope, nn, a, q, keys, dkeys, dU, dV, da, dq, dW0, Hn, R, T, Dk, Q, qh,
-                                  q_hist=q_hist, dq_hist=dq_hist)
 
     def _hist_bwd_x3(self, Dk, Q, qh):
         """history-level tail of the attention backward as ONE launch of split-bf16 products (csrc/atthist.hip)?"""
@@ -1723,10 +1664,11 @@ class CLSRNet(object):
         bn0, bn1 = self.bn[nn + "batch_normalization/"], self.bn[nn + "batch_normalization_1/"]
         z0, z1 = self._buf(key + ".z0", B, C0), self._buf(key + ".z1", B, C1)
         logit = self._buf(key + ".logit", B)
-        st, parts = self._stats_buf(B, C0) if training else (None, 0)
+        parts = query("clsr_pgemm_stats_parts", B) if training else 0
+        st = self._stats_buf(parts, C0)
         self._gemm(X, ldx, key + ".W0", B, K0, C0, z0, C0, bias=P[nn + "b_nn_layer0"], stats=st)
         self._bn_fwd(bn0, st, parts, B, training)
-        st, parts = self._stats_buf(B, C1) if training else (None, 0)
+        st = self._stats_buf(parts, C1)
         self._gemm(z0, C0, key + ".W1", B, C0, C1, z1, C1, bias=P[nn + "b_nn_layer1"], aff=bn0, stats=st)
         self._bn_fwd(bn1, st, parts, B, training)
         if not (key == "lg" and self._defer_logit_out):   # (training step: the logits come out of clsr_mlp_tail_softmax)
@@ -1837,6 +1779,14 @@ class CLSRNet(object):
                          (3 * H, "_time_input_bias2")):
             self._rp(tp[off_:], parts, 4 * H, H, Gd[t + nm])
 
+    def _enc_input_bwd(self, hist, dPinAll, dhist, M):
+        """Input-side weight gradients of every encoder as one product (xw.dW / xw.db, scattered into the variables by
+        ``_unpack_grads``) and d(hist) += dPin . W_x^T as another."""
+        D, E, NX = self.D, self.enc_in, self.NX
+        self._dw(hist, D, dPinAll, NX, M, E, NX, self._buf("xw.dW", E, NX), NX, db=self._buf("xw.db", NX),
+                 dy_bf16=int(dPinAll.dtype == torch.bfloat16))
+        self._gemm(dPinAll, NX, "xw^T", M, NX, E, dhist, D, acc=1)
+
     def _gru_bwd_hidden(self, key, scope, n, dPinAll, Hn, T):
         """Hidden-to-hidden weight gradients of one GRU from its slice of dPin."""
         Gd, D, NX = self.Gd, self.enc_in, self.NX
@@ -1858,14 +1808,13 @@ class CLSRNet(object):
                 and self.D == self.Du == self.H and bool(query("clsr_enc_bwd_fused_supported", self.D, self.H, self.NX))
                 and self._enc_off("g1") == 0 and self._enc_off("g2") == 3 * self.H and self._enc_off("t4") == 6 * self.H)
 
-    def _enc_bwd_fused(self, f, hist, dPinAll, dhist, Hn, T, hs):
-        """Seven encoder-side weight gradients + d(hist) from ONE pass over dPin (csrc/encbwd.hip) on the compute stream,
-        behind the small time-feature chain (d TT, its tanh backward and parameter sums)."""
+    def _enc_bwd_fused_ws(self, tag, prefix, M):
+        """Workspaces (buffers ``<prefix>.ws0..6``) for the partial sums of the seven encoder-side weight gradients that the
+        fused tail kernel ``clsr_enc_bwd_fused<tag>`` writes, each entered into the batched reduction of the compute stream."""
         Gd, D, H, NX, E = self.Gd, self.D, self.H, self.NX, self.enc_in
-        M = Hn * T
         st, t = CL + "short_term/", self._t4_scope
         g1, g2 = st + "short_term_intention/gru_cell/", CL + "causal2/causal2/gru_cell/"
-        parts = query("clsr_enc_bwd_fused_parts", M)
+        parts = query("clsr_enc_bwd_fused%s_parts" % tag, M)
         prods = [(self._buf("xw.dW", D, NX), NX, self._buf("xw.db", NX), D, NX),
                  (Gd[g1 + "gates/kernel"][E:], 2 * H, None, H, 2 * H), (Gd[g1 + "candidate/kernel"][E:], H, None, H, H),
                  (Gd[t + "kernel"][E:], 4 * H, None, H, 4 * H), (self._buf("t4.dTW", 2 * H, 3 * H), 3 * H, None, 2 * H, 3 * H),
@@ -1873,70 +1822,60 @@ class CLSRNet(object):
         pend = self._dw_pending.setdefault("", [])
         wss = []
         for i, (dW, ldw, db, K, N) in enumerate(prods):
-            ws = self._buf("encb.ws%d" % i, query("clsr_enc_bwd_fused_workspace_floats", M, i))
+            ws = self._buf("%s.ws%d" % (prefix, i), query("clsr_enc_bwd_fused%s_workspace_floats" % tag, M, i))
             wss.append(ws)
             pend.append((ws.data_ptr(), dW.data_ptr(), db.data_ptr() if db is not None else 0, 1.0, parts, K, N, ldw, 0))
-        # d TT = dPin[:, o | tns | tls] . tw^T FIRST, on the compute stream (~35 us alone; beside the fused kernel, whose
-        # workgroups fill every CU's LDS, it found no room and took 500 us); its tanh backward + parameter sums then
-        # run beside the fused kernel on the weight-gradient stream, which the dense reduction follows in stream order
-        dPt = dPinAll[:, self._enc_off("t4"):]
-        dTT = self._buf("t4.dTT", M, 2 * H)
-        TT = self._buf("t4.TT", M, 2 * H)
-        # (every workspace of the side branch exists BEFORE the fork: a first-use allocation zero-fills on the compute
-        #  stream, and a fill enqueued behind the fork raced with the branch's writes in the first step of a net)
-        parts_t = query("clsr_t4_time_inputs_bwd_parts", Hn, T, H)
-        tp = self._buf("t4.tpart", 512 * 4 * 128)[: parts_t * 4 * H]
-        self._gemm(dPt[:, 3 * H:], NX, "t4.tw^T", M, 3 * H, 2 * H, dTT, 2 * H)
-        # ... and its tanh backward + parameter sums (27 us): beside the MFMA-saturated fused kernel they took 400 us and
-        # the batched reduction of ALL dense gradients waited for them
-        call("clsr_t4_time_inputs_bwd", dTT, TT, f["time_to_now"], f["time_from_first_action"], hs * T, Hn, T, H, tp)
-        for off_, nm in ((0, "_time_input_w1"), (H, "_time_input_w2"), (2 * H, "_time_input_bias1"),
-                         (3 * H, "_time_input_bias2")):
-            self._rp(tp[off_:], parts_t, 4 * H, H, Gd[t + nm])
-        Wt, Kp = self.packed["xw^T"]
-        fold = self._fold_args if self.fold_hist_shares else None
-        if fold is not None:
+        return wss
+
+    def _enc_bwd_fused(self, f, hist, dPinAll, dhist, Hn, T, hs):
+        """Seven encoder-side weight gradients from ONE pass over dPin (csrc/encbwd.hip), d(hist) += dPin . W_x^T and the small
+        time-feature chain (d TT, its tanh backward and parameter sums).  The precision mode selects the entry point and
+        where the three pieces run:
+          fp32                   clsr_enc_bwd_fused[_fold], which also computes d(hist), on the compute stream behind the chain;
+          fp32x3, CLSR_ENC_BWD=x6, bf16
+                                 clsr_enc_bwd_fused_x3 / _x6 / _h (split-bf16 products over the fp32 dPin / one pass over the bf16
+                                 dPin) on the weight-gradient stream, beside d(hist) on the long-term stream and the chain on
+                                 the compute stream."""
+        D, H, NX = self.D, self.H, self.NX
+        M = Hn * T
+        saved = (self._buf("g1.hprev", Hn, T, H), self._buf("g1.gates", Hn, T, 3 * H), self._buf("t4.mprev", Hn, T, H),
+                 self._buf("t4.TT", M, 2 * H), self._buf("g2.hprev", Hn, T, H), self._buf("g2.gates", Hn, T, 3 * H))
+        if not (self.bf16 or self.x3 or self.enc_x6):
+            wss = self._enc_bwd_fused_ws("", "encb", M)
+            # the time-feature chain FIRST, on the compute stream: d TT = dPin[:, o | tns | tls] . tw^T (~35 us alone; beside
+            # the fused kernel, whose workgroups fill every CU's LDS, it found no room and took 500 us), then its tanh backward
+            # + parameter sums (27 us: beside the MFMA-saturated fused kernel they took 400 us and the batched reduction of
+            # ALL dense gradients waited for them)
+            # (the chain allocates every workspace before its first launch: a first-use allocation zero-fills on the compute
+            #  stream, and a fill enqueued behind a fork raced with a side branch's writes in the first step of a net)
+            self._t4_time_chain_bwd(f, dPinAll, Hn, T, hs)
+            Wt, Kp = self.packed["xw^T"]
+            fold = self._fold_args if self.fold_hist_shares else None
+            if fold is None:
+                call("clsr_enc_bwd_fused", dPinAll, hist, *saved, Wt, Kp, dhist, *wss, M)
+                return
             # d(hist) += the long-term branch's d(hist) + the mean / recent-k shares of the history prologue INSIDE this launch
             # (it reads and writes every d(hist) row anyway): the segmented sums of the item / category sites then run in
             # their lean, software-pipelined form (csrc/segsum.hip) -- they are what the table update at the end of the step
             # waits for
             dhist_lt, dM, dR, seq_len, ls = fold
             self._join(only="@lt")          # (the long-term attention backward wrote dhist_lt on its branch, long ago)
-            call("clsr_enc_bwd_fused_fold", dPinAll, hist, self._buf("g1.hprev", Hn, T, H), self._buf("g1.gates", Hn, T, 3 * H),
-                 self._buf("t4.mprev", Hn, T, H), TT, self._buf("g2.hprev", Hn, T, H), self._buf("g2.gates", Hn, T, 3 * H),
-                 Wt, Kp, dhist, dhist_lt, dM, dR, seq_len, ls, T, int(self.hp.contrastive_recent_k), *wss, M)
+            call("clsr_enc_bwd_fused_fold", dPinAll, hist, *saved, Wt, Kp, dhist, dhist_lt, dM, dR, seq_len, ls, T,
+                 int(self.hp.contrastive_recent_k), *wss, M)
             self._folded = True
             return
-        call("clsr_enc_bwd_fused", dPinAll, hist, self._buf("g1.hprev", Hn, T, H), self._buf("g1.gates", Hn, T, 3 * H),
-             self._buf("t4.mprev", Hn, T, H), TT, self._buf("g2.hprev", Hn, T, H), self._buf("g2.gates", Hn, T, 3 * H),
-             Wt, Kp, dhist, *wss, M)
-
-    def _enc_bwd_fused_x3(self, f, hist, dPinAll, dhist, Hn, T, hs):
-        """fp32x3 mode: the seven encoder-side weight gradients from ONE pass over the fp32 dPin as split-bf16 products
-        (clsr_enc_bwd_fused_x3) on the weight-gradient stream, beside d(hist) = dPin . W_x^T (long-term stream) and the
-        time-feature chain on the compute stream -- the launch structure of the speed mode's tail."""
-        Gd, D, H, NX, E = self.Gd, self.D, self.H, self.NX, self.enc_in
-        M = Hn * T
-        st, t = CL + "short_term/", self._t4_scope
-        g1, g2 = st + "short_term_intention/gru_cell/", CL + "causal2/causal2/gru_cell/"
-        parts = query("clsr_enc_bwd_fused_x3_parts", M)
-        prods = [(self._buf("xw.dW", D, NX), NX, self._buf("xw.db", NX), D, NX),
-                 (Gd[g1 + "gates/kernel"][E:], 2 * H, None, H, 2 * H), (Gd[g1 + "candidate/kernel"][E:], H, None, H, H),
-                 (Gd[t + "kernel"][E:], 4 * H, None, H, 4 * H), (self._buf("t4.dTW", 2 * H, 3 * H), 3 * H, None, 2 * H, 3 * H),
-                 (Gd[g2 + "gates/kernel"][E:], 2 * H, None, H, 2 * H), (Gd[g2 + "candidate/kernel"][E:], H, None, H, H)]
-        pend = self._dw_pending.setdefault("", [])
-        wss = []
-        for i, (dW, ldw, db, K, N) in enumerate(prods):
-            ws = self._buf("encbx.ws%d" % i, query("clsr_enc_bwd_fused_x3_workspace_floats", M, i))
-            wss.append(ws)
-            pend.append((ws.data_ptr(), dW.data_ptr(), db.data_ptr() if db is not None else 0, 1.0, parts, K, N, ldw, 0))
-        self._buf("t4.dTT", M, 2 * H)      # (workspaces of the branches exist before the fork: see _enc_bwd_fused)
-        side = self.overlap
-        with self._branch("@dw0" if side else "@main", after=self._fork_point(), name="@encw"):
-            call("clsr_enc_bwd_fused_x6" if self.enc_x6 else "clsr_enc_bwd_fused_x3", dPinAll, hist, self._buf("g1.hprev", Hn, T, H), self._buf("g1.gates", Hn, T, 3 * H),
-                 self._buf("t4.mprev", Hn, T, H), self._buf("t4.TT", M, 2 * H), self._buf("g2.hprev", Hn, T, H),
-                 self._buf("g2.gates", Hn, T, 3 * H), *wss, M)
-        if side:
+        if self.bf16:
+            # (the kernel can also accumulate d(hist) = dPin . W_x^T -- Wt_bf16 / dhist arguments, tested -- but that product
+            #  contracts over the COLUMNS: its operands come from global memory / L1, 100-150 us more in the kernel against the
+            #  230 us of the separate clsr_hgemm_hf32 launch that otherwise runs BESIDE it: 2.93 against 2.90 ms per step)
+            entry, wss, rest = "clsr_enc_bwd_fused_h", self._enc_bwd_fused_ws("_h", "encbh", M), (None, 0, None)
+        else:
+            entry = "clsr_enc_bwd_fused_x6" if self.enc_x6 else "clsr_enc_bwd_fused_x3"
+            wss, rest = self._enc_bwd_fused_ws("_x3", "encbx", M), ()
+        dTT = self._buf("t4.dTT", M, 2 * H)      # (workspaces of the branches exist before the fork: see above)
+        with self._branch("@dw0" if self.overlap else "@main", after=self._fork_point(), name="@encw"):
+            call(entry, dPinAll, hist, *saved, *wss, *rest, M)
+        if self.overlap:
             self._dw_async = True       # (the flush waits for the weight-gradient stream)
         tcol0 = self._enc_off("t4") + 3 * H
         if (self.x3 and "t4.tw^T" in self.packed
@@ -1944,51 +1883,12 @@ class CLSRNet(object):
             # d(hist) += dPin . W_x^T and d TT = dPin[:, o | tns | tls] . tw^T from ONE pass over dPin (csrc/projx3.hip)
             Wx, Kpx = self.packed["xw^T"]
             Wt, Kpt = self.packed["t4.tw^T"]
-            call("clsr_enc_back_x3", dPinAll, NX, Wx, Kpx, Wt, Kpt, tcol0, dhist, D, self._buf("t4.dTT", M, 2 * H), 2 * H,
-                 M, NX, D, 2 * H, 3 * H)
+            call("clsr_enc_back_x3", dPinAll, NX, Wx, Kpx, Wt, Kpt, tcol0, dhist, D, dTT, 2 * H, M, NX, D, 2 * H, 3 * H)
             self._t4_time_chain_bwd(f, dPinAll, Hn, T, hs, have_dtt=True)
             return
-        if self.overlap:
-            with self._branch("@lt", after=self._fork_point(), name="@dhist"):
-                self._gemm(dPinAll, NX, "xw^T", M, NX, D, dhist, D, acc=1)
-        else:
-            self._gemm(dPinAll, NX, "xw^T", M, NX, D, dhist, D, acc=1)
-        self._t4_time_chain_bwd(f, dPinAll, Hn, T, hs)
-
-    def _enc_bwd_fused_h(self, f, hist, dPinAll, dhist, Hn, T, hs):
-        """Speed mode: the seven encoder-side weight gradients from ONE pass over the bf16 dPin (clsr_enc_bwd_fused_h) on
-        the weight-gradient stream, beside d(hist) = dPin . W_x^T and the time-feature chain on the compute stream."""
-        Gd, D, H, NX, E = self.Gd, self.D, self.H, self.NX, self.enc_in
-        M = Hn * T
-        st, t = CL + "short_term/", self._t4_scope
-        g1, g2 = st + "short_term_intention/gru_cell/", CL + "causal2/causal2/gru_cell/"
-        parts = query("clsr_enc_bwd_fused_h_parts", M)
-        prods = [(self._buf("xw.dW", D, NX), NX, self._buf("xw.db", NX), D, NX),
-                 (Gd[g1 + "gates/kernel"][E:], 2 * H, None, H, 2 * H), (Gd[g1 + "candidate/kernel"][E:], H, None, H, H),
-                 (Gd[t + "kernel"][E:], 4 * H, None, H, 4 * H), (self._buf("t4.dTW", 2 * H, 3 * H), 3 * H, None, 2 * H, 3 * H),
-                 (Gd[g2 + "gates/kernel"][E:], 2 * H, None, H, 2 * H), (Gd[g2 + "candidate/kernel"][E:], H, None, H, H)]
-        pend = self._dw_pending.setdefault("", [])
-        wss = []
-        for i, (dW, ldw, db, K, N) in enumerate(prods):
-            ws = self._buf("encbh.ws%d" % i, query("clsr_enc_bwd_fused_h_workspace_floats", M, i))
-            wss.append(ws)
-            pend.append((ws.data_ptr(), dW.data_ptr(), db.data_ptr() if db is not None else 0, 1.0, parts, K, N, ldw, 0))
-        # (the kernel can also accumulate d(hist) = dPin . W_x^T -- Wt_bf16 / dhist arguments, tested -- but that product
-        #  contracts over the COLUMNS: its operands come from global memory / L1, 100-150 us more in the kernel against the
-        #  230 us of the separate clsr_hgemm_hf32 launch that otherwise runs BESIDE it: 2.93 against 2.90 ms per step)
-        side = self.overlap
-        with self._branch("@dw0" if side else "@main", after=self._fork_point(), name="@encw"):
-            call("clsr_enc_bwd_fused_h", dPinAll, hist, self._buf("g1.hprev", Hn, T, H), self._buf("g1.gates", Hn, T, 3 * H),
-                 self._buf("t4.mprev", Hn, T, H), self._buf("t4.TT", M, 2 * H), self._buf("g2.hprev", Hn, T, H),
-                 self._buf("g2.gates", Hn, T, 3 * H), *wss, None, 0, None, M)
-        if side:
-            self._dw_async = True       # (the flush waits for the weight-gradient stream)
-        if self.overlap:
-            # three ways: weight gradients on @dw0, d(hist) on the (by now idle) long-term stream (2.87 -> 2.84 ms against
-            # d(hist) here), the time-feature chain here
-            with self._branch("@lt", after=self._fork_point(), name="@dhist"):
-                self._gemm(dPinAll, NX, "xw^T", M, NX, D, dhist, D, acc=1)
-        else:
+        # three ways: weight gradients on @dw0, d(hist) on the (by now idle) long-term stream (2.87 -> 2.84 ms against
+        # d(hist) here; without overlap the branch is the compute stream itself), the time-feature chain here
+        with self._branch("@lt", after=self._fork_point(), name="@dhist"):
             self._gemm(dPinAll, NX, "xw^T", M, NX, D, dhist, D, acc=1)
         self._t4_time_chain_bwd(f, dPinAll, Hn, T, hs)
 
@@ -2441,15 +2341,12 @@ class CLSRNet(object):
         self._folded = False
         self._fold_args = (dhist_lt, dM, dR, seq_len, ls) if (self.det_grads and dhist.dtype == F32) else None
         if self._enc_bwd_fused_ok(dpin_h):
-            (self._enc_bwd_fused_h if self.bf16 else self._enc_bwd_fused_x3 if (self.x3 or self.enc_x6) else
-             self._enc_bwd_fused)(f, hist, dPinAll, dhist, Hn, T, hs)
+            self._enc_bwd_fused(f, hist, dPinAll, dhist, Hn, T, hs)
         else:
           # input-side weights of every encoder in one reduction; d(hist) in one product; the hidden-side / time-feature
           # weight gradients ride in the same multi-job launch as the input-side one (they all depend on dPin only)
           with self._dw_batched():
-              self._dw(hist, D, dPinAll, NX, M, D, NX, self._buf("xw.dW", D, NX), NX, db=self._buf("xw.db", NX),
-                       dy_bf16=int(dpin_h))
-              self._gemm(dPinAll, NX, "xw^T", M, NX, D, dhist, D, acc=1)
+              self._enc_input_bwd(hist, dPinAll, dhist, M)
               if self._t4_kind is not None:
                   self._t4_bwd_weights(f, dPinAll, Hn, T, hs)
               else:
@@ -2899,19 +2796,13 @@ class CLSRNet(object):
         B, T, G, Hn = self.last_shape
         A0, A1, M = self.A0, self.A1, B * T
         key, nn = "st", CL + "short_term/attention_fcn/att_fcn/nn_part/"
-        bn0, bn1 = self.bn[nn + "batch_normalization/"], self.bn[nn + "batch_normalization_1/"]
         if self.bf16:
             if not self._bf16_chain_ok(G, self.D):
                 return None
             BF = torch.bfloat16
             z0, z1 = self._buf(key + ".z0", M, A0, dtype=BF), self._buf(key + ".z1", M, A1, dtype=BF)
             dz0, ds = self._buf(key + ".dz0", M, A0, dtype=BF), self._buf(key + ".ds", M)
-            Wt, Kp = self.packed[key + ".W1^T"]
-            parts = query("clsr_att_l1_bwd_x3_parts", M)
-            ws = self._buf(key + ".dw1x_ws", parts * query("clsr_dw_chunk_floats"))
-            wo = self.P[nn + "w_nn_output"]
-            t = time_kernel(lambda: call("clsr_att_l1_bwd_x1_h", z1, A1, ds, bn1.scale, bn1.shift, wo, bn1.coef, Wt, Kp, z0, A0,
-                                         bn0.scale, bn0.shift, None, None, bn0.coef, dz0, A0, ws, None, M, A1, A0))
+            t = time_kernel(self._att_l1_bwd_x_passes(key, nn, z0, z1, ds, dz0, M)[1])
             nbytes = float(M) * ((A1 + 2 * A0) * 2 + 4)
             return dict(bound="hbm", kernel="att_l1_bwd_x3_kernel<5,3,true,1,bf16> (short-term attention, layer-1 backward pass 2: dz0 + "
                                             "the partial sums of dW1 / db1 from one pass over the bf16 z1, z0; one bf16 piece per operand)",
@@ -2923,12 +2814,7 @@ class CLSRNet(object):
             return None
         z0, z1 = self._buf(key + ".z0", M, A0), self._buf(key + ".z1", M, A1)
         dz0, ds = self._buf(key + ".dz0", M, A0), self._buf(key + ".ds", M)
-        Wt, Kp = self.packed[key + ".W1^T"]
-        parts = query("clsr_att_l1_bwd_x3_parts", M)
-        ws = self._buf(key + ".dw1x_ws", parts * query("clsr_dw_chunk_floats"))
-        wo = self.P[nn + "w_nn_output"]
-        t = time_kernel(lambda: call(self._l1x, z1, A1, ds, bn1.scale, bn1.shift, wo, bn1.coef, Wt, Kp, z0, A0,
-                                     bn0.scale, bn0.shift, None, None, bn0.coef, dz0, A0, ws, None, M, A1, A0))
+        t = time_kernel(self._att_l1_bwd_x_passes(key, nn, z0, z1, ds, dz0, M)[1])
         nbytes = float(M) * (A1 + 2 * A0 + 1) * 4
         return dict(bound="hbm", kernel="att_l1_bwd_x3_kernel<5,3,true,%d> (short-term attention, layer-1 backward pass 2: dz0 + the "
                                         "partial sums of dW1 / db1 from one pass over z1, z0; %s bf16 pieces per operand)"
@@ -2941,21 +2827,9 @@ class CLSRNet(object):
         R, A0 = Hn * G, self.A0
         a, q = self._buf(key + ".a", Hn * T, Q), self._buf(key + ".q", R, Q)
         U, V = self._buf(key + ".U", Hn * T, A0), self._buf(key + ".V", R, A0)
-        if self.bf16:
-            z0 = self._buf(key + ".z0", R * T, A0, dtype=torch.bfloat16)
-            if self._bf16_chain_ok(G, Q):
-                Wt, Kp = self.packed[key + ".Wp"]
-                return lambda: call("clsr_att_l0_fwd_x1_h", a, Q, q, Q, Wt, Kp, U, A0, V, A0, z0, A0, None, Hn, G, T, Q, A0)
-            Wt, Kp = self.packed_h[key + ".Wp"]
-            if query("clsr_hgemm_l0_group_supported", G, Q, A0):
-                return lambda: call("clsr_hgemm_l0_group", a, Q, q, Q, Wt, Kp, U, A0, V, A0, z0, A0, None, Hn, G, T, Q, A0)
-            return lambda: call("clsr_hgemm_mul_uv", a, Q, T, G, q, Q, Wt, Kp, U, A0, V, A0, z0, A0, None, R * T, Q, A0)
-        z0 = self._buf(key + ".z0", R * T, A0)
-        Wt, Kp = self.packed[key + ".Wp"]
-        if self._att_layer0_wave(G, Q):
-            return lambda: call("clsr_att_l0_fwd", a, Q, q, Q, Wt, Kp, U, A0, V, A0, z0, A0, None, Hn, G, T, Q, A0)
-        return lambda: call("clsr_pgemm", a, Q, T, G, q, Q, None, None, 1, Wt, Kp, None, U, A0, V, A0, z0, A0, 0,
-                            None, R * T, Q, A0)
+        z0 = self._buf(key + ".z0", R * T, A0, dtype=torch.bfloat16 if self.bf16 else F32)
+        entry, args, _, _ = self._att_l0_fwd_launch(key, ".Wp", a, q, U, V, z0, Hn, G, T, Q, Q, False)
+        return lambda: call(entry, *args)
 
     def _att_layer0_wave(self, G, Q):
         return (not self.bf16) and bool(query("clsr_att_l0_fwd_supported", G, Q, self.A0))

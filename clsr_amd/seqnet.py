@@ -321,8 +321,7 @@ class SeqNet(CLSRNet):
             dPinAll = self._buf("xw.dPin", M, NX)
             ops.rnn_multi("clsr_rnn_bwd_multi", [self._gru_bwd_desc("gs", sc["gru"], H, dPinAll, Hn, T, dhT, None,
                                                                      None)], None, seq_len, ls, Hn, T)
-            self._dw(hist, D, dPinAll, NX, M, E, NX, self._buf("xw.dW", E, NX), NX, db=self._buf("xw.db", NX))
-            self._gemm(dPinAll, NX, "xw^T", M, NX, E, dhist, D, acc=1)
+            self._enc_input_bwd(hist, dPinAll, dhist, M)
             self._gru_bwd_hidden("gs", sc["gru"], H, dPinAll, Hn, T)
             self._dw_flush()
             self._unpack_grads()
@@ -366,8 +365,7 @@ class SeqNet(CLSRNet):
             dPinAll = self._buf("xw.dPin", M, NX)
             ops.rnn_multi("clsr_rnn_bwd_multi", [self._gru_bwd_desc("gs", sc["gru1"], H, dPinAll, Hn, T, None, drnn,
                                                                      None)], None, seq_len, ls, Hn, T)
-            self._dw(hist, D, dPinAll, NX, M, E, NX, self._buf("xw.dW", E, NX), NX, db=self._buf("xw.db", NX))
-            self._gemm(dPinAll, NX, "xw^T", M, NX, E, dhist, D, acc=1)
+            self._enc_input_bwd(hist, dPinAll, dhist, M)
             self._gru_bwd_hidden("gs", sc["gru1"], H, dPinAll, Hn, T)
             self._dw_flush()
             self._unpack_grads()
@@ -407,8 +405,7 @@ class SeqNet(CLSRNet):
             t4d = ops.t4_desc(H, Wm=P[t + "kernel"][E:], ldm=4 * H, act=self._buf("t4.act", Hn, T, 6 * H),
                               cst=self._buf("t4.cst", Hn, T, H), dout_seq=drnn, dPin=dPinAll[:, t4off:], lddp=NX)
             ops.rnn_multi("clsr_rnn_bwd_multi", [], t4d, seq_len, ls, Hn, T)
-            self._dw(hist, D, dPinAll, NX, M, E, NX, self._buf("xw.dW", E, NX), NX, db=self._buf("xw.db", NX))
-            self._gemm(dPinAll, NX, "xw^T", M, NX, E, dhist, D, acc=1)
+            self._enc_input_bwd(hist, dPinAll, dhist, M)
             self._t4_bwd_weights(f, dPinAll, Hn, T, hs)
             self._asvd_bwd(dL, hist, dhist, Hn, T)
             self._dw_flush()
