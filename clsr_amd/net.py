@@ -17,7 +17,6 @@ is replicated equally; dropout is 0).  The one observable difference: ``tf.clip_
 the embedding IndexedSlices uses the norm of the G un-summed replica slices, here the norm of
 their sum is used; ``dedup_histories=False`` runs the reference's replicated computation.
 """
-import math
 import contextlib
 import os
 import warnings
@@ -86,6 +85,21 @@ _SIDE_STREAMS = {}     # device -> {tag: HIP stream}, see CLSRNet.__init__
 class StepAborted(RuntimeError):
     """A bounded wait inside a training step gave up (see CLSRNet.check_abort): the step's results are invalid and no
     optimiser update has been applied since."""
+
+
+class _StepState(object):
+    """What the phases of ONE training step hand each other on the host.  ``_train_step`` binds a new one as ``net._step``;
+    ``_apply_updates`` takes it and leaves an idle one behind (these defaults: what a scoring pass or a bare
+    ``_apply_updates`` reads), and so does ``CLSRNet._drop_step`` when an exception leaves the step."""
+    __slots__ = ("cur_feed", "counts_zeroed", "ucount_zeroed", "ticked", "early_lists", "updated_early", "dense_fork",
+                 "fold_args", "folded", "heads_defer", "defer_logit_out")
+
+    def __init__(self, feed=None):
+        self.cur_feed, self.dense_fork = feed, None     # the uploaded feed | event the dense update on @dw0 is ordered behind
+        self.counts_zeroed = self.ucount_zeroed = self.ticked = False     # zero_and_mark cleared the sort / user counters, ticked the Adam clock
+        self.early_lists, self.updated_early = None, ()     # big tables' row lists, compacted under the forward | tables updated early
+        self.fold_args, self.folded = None, False     # what the fused encoder tail may add to d(hist) / has added
+        self.heads_defer = self.defer_logit_out = False     # forward: the heads / logits come out of the backward's launches
 
 
 class CLSRNet(object):
@@ -159,13 +173,9 @@ class CLSRNet(object):
         self.bf16_chain = self.precision == "bf16" and os.environ.get("CLSR_BF16_CHAIN", "x1") == "x1"
         self._cur_descs_h = []
         self._plans, self._plan_keep, self._cur_descs = {}, [], []
-        self._sort_bytes = {}
-        self._ws_tag = ""          # suffix of shared scratch buffers while a side-stream branch is recording
         # side streams are shared by every net of the process on this device (one net steps at a time): a second net
         # with four streams of its own puts eight hardware queues in play and its step takes 5.7 instead of 3.4 ms
         self._side = _SIDE_STREAMS.setdefault(str(torch.device(device)), {})
-        self._dense_fork = None
-        self._dw_async = False
         # history-level half of the short-term query folded into U (see _att_qh; SeqNet has no such half).  Pays off at every
         # width once the per-row half runs on the one-wave-per-history kernels (round 3; the position-tiled kernels needed
         # Du >= 64); in the speed mode the history-level share of the product term rides inside the fused history-level
@@ -173,17 +183,12 @@ class CLSRNet(object):
         self.split_query = True
         self.split_query_min = 16
         self.use_plans = not os.environ.get("CLSR_NO_PLAN")                # replay recorded launch sequences
-        self._step_plans = {}
-        self._dw_batch = None
+        self._step_plans, self._dw_tables = {}, {}
         self._buf_allocs = 0
-        # HIP stream priorities of the side streams (0 = normal; the callers' compute stream can be created with -1 = high)
-        # branch tag -> stream tag.  The @aux branches share the @lt stream: compute + @lt + @dw0 = three HIP streams, so
-        # that RCCL's stream is the FOURTH under data parallelism -- a fifth active queue (or a fourth next to a
-        # high-priority compute stream) cost 4.0 -> 6.6 ms per step (r03, CLSR_FORCE_DP=1); on a single GPU the fold
-        # measured 3.768 against 3.779 ms.  CLSR_FOLD_AUX=0: the round-2 layout with a stream of its own.
+        # branch tag -> stream tag.  The @aux branches share the @lt stream: compute + @lt + @dw0 = three HIP streams, so that
+        # RCCL's stream is the FOURTH under data parallelism -- a fifth active queue (or a fourth next to a high-priority compute
+        # stream) cost 4.0 -> 6.6 ms per step (r03, CLSR_FORCE_DP=1); one GPU: 3.768 against 3.779 ms with @aux on its own stream.
         self.stream_alias = {"@aux": "@lt"}
-        self.side_priority = 0
-        self.dw_priority = 0
         # Recurrences: hidden-to-hidden products as split-bf16 sums (csrc/rnn.hip, "x3") or fp32-input MFMAs ("fp32", bit-exact
         # fp32); with x3 the input projections of the GRUs and of the Time4LSTM blocks i | j | f run INSIDE the recurrence
         # launch from the history embeddings (no projection tensor, no GEMM in front of the T-serial chain), and the
@@ -220,19 +225,12 @@ class CLSRNet(object):
         # per operand (fp32 accuracy; CLSR_DW_WIDE=fp32: fp32-input MFMAs)
         self.dw_wide_entry = (("clsr_pgemm_dw_wide" if os.environ.get("CLSR_DW_WIDE", "x6") == "fp32" else "clsr_pgemm_dw_wide_x6")
                               if self.exact_products else "clsr_pgemm_dw_wide_x3")
-        self._dw_batch_wide = None
-        self._heads_defer = False
-        self._early_lists = None
         self.heads_comm = None      # data-parallel runs: communicator of the fused heads (clsr_amd/p2p.py: HeadsComm)
-        self._defer_logit_out = False
         # the fused encoder tail (csrc/encbwd.hip) also adds the long-term d(hist) and the history prologue's shares, so that
         # the segmented sums run lean
         self.fold_hist_shares = not os.environ.get("CLSR_NO_FOLD_SHARES")
-        self._fold_args, self._folded = None, False
         self.early_user_update = not os.environ.get("CLSR_NO_EARLY_USER_UPDATE")   # user tables: regulariser + Adam behind their row scatters
-        self._updated_early = set()
-        self._joins = []
-        self._dw_pending, self._dw_tables, self._dw_after, self._rp_pending = {}, {}, {}, {}
+        self._drop_step()          # the step's host-side state and the stream bookkeeping beside it, idle
         self.defer_dw = True       # one batched reduction of the weight-gradient partials per stream and step
         self.overlap = not os.environ.get("CLSR_NO_OVERLAP")   # run the long-term attention chain etc. on side streams (fork / join); off: one stream, every kernel alone (diagnosis: contention-free kernel times)
         # deterministic embedding gradients (csrc/segsum.hip): STABLE radix sort of every lookup site's ids + segmented sums
@@ -248,7 +246,6 @@ class CLSRNet(object):
         self.sumsq_tab, self.losses = self.stats24[:16], self.stats24[16:]
         self.ucount = torch.zeros(1, dtype=F32, device=self.device)
         self.last_shape = None
-        self._counts_zeroed = self._ucount_zeroed = self._ticked = False
         self.dp_world = 1          # data-parallel world size (loss normalisers are global)
         self.dp_stats_hook = None  # optional callable(tensor): sum BN partial statistics across ranks
         self.dp_comm = None        # optional communicator handle (clsr_amd/p2p.py): the same sum as ONE kernel on this stream,
@@ -681,14 +678,13 @@ class CLSRNet(object):
 
     def _side_stream(self, tag):
         """The side stream ``tag`` of this device, created on first use by whichever call site gets there first: the
-        weight-gradient streams (@dw*) with CLSR_DW_PRIORITY, every other one with CLSR_SIDE_PRIORITY.  A new stream
-        orders itself behind everything enqueued on the current stream so far -- the zero fills of workspaces allocated
-        before it existed included (``_buf`` makes the streams that exist at allocation time wait; a stream created later
-        in the same first step could still have written such a buffer ahead of its pending fill)."""
+        weight-gradient stream (@dw0) like every other one at the normal priority 0 (the callers' compute stream can be created
+        with -1 = high).  A new stream orders itself behind everything enqueued on the current stream so far -- the zero fills
+        of workspaces allocated before it existed included (``_buf`` makes the streams that exist at allocation time wait; a
+        stream created later in the same first step could still have written such a buffer ahead of its pending fill)."""
         side = self._side.get(tag)
         if side is None:
-            prio = self.dw_priority if tag.startswith("@dw") else self.side_priority
-            side = self._side[tag] = torch.cuda.Stream(device=self.device, priority=prio)
+            side = self._side[tag] = torch.cuda.Stream(device=self.device, priority=0)
             ev = torch.cuda.Event()
             ev.record(torch.cuda.current_stream(self.device))
             side.wait_event(ev)
@@ -771,7 +767,7 @@ class CLSRNet(object):
             # per workgroup column, K in slabs of 128 (csrc/projx3.hip) -- the position-tiled fp32 kernel ran these at
             # 0.3-0.4 of the fp32 matrix peak (profiles/r05_catalogue_pmc.md)
             # (back-propagating products -- transposed weights -- take two pieces like every other backward product of the
-            # default modes: half the MFMAs, two workgroups per CU instead of one; CLSR_PROJ_BWD_PIECES=3: as the forward ones)
+            # default modes: half the MFMAs, two workgroups per CU instead of one; three in "fp32", as the forward ones: proj_bwd_pieces)
             pieces = self.proj_bwd_pieces if wkey.endswith("^T") else self.proj_wide_pieces
             call("clsr_proj_x3_wide", X, ldx, Wt, Kp, bias, Y, ldy, M, K, N, pieces, int(acc))
             return
@@ -891,7 +887,7 @@ class CLSRNet(object):
 
     def _dw_flush(self, tag=None):
         """Reduce the partial chunks of every ``_dw`` issued under workspace tag ``tag`` (default: the current
-        stream's) since the last flush, then run the operations that were waiting for those gradients."""
+        stream's) since the last flush."""
         tag = self._ws_tag if tag is None else tag
         pend = self._dw_pending.pop(tag, [])
         if tag == "" and self._dw_async:
@@ -909,8 +905,6 @@ class CLSRNet(object):
         rp = self._rp_pending.pop(tag, [])
         if rp:
             ops.multi("clsr_reduce_parts_multi", ops.RpDesc, rp)
-        for fn in self._dw_after.pop(tag, []):
-            fn()
 
     def _stats_buf(self, parts, N):
         """``parts`` rows of per-block batch-norm partial sums, 2N doubles each, in the statistics workspace of the current
@@ -1671,14 +1665,14 @@ class CLSRNet(object):
         st = self._stats_buf(parts, C1)
         self._gemm(z0, C0, key + ".W1", B, C0, C1, z1, C1, bias=P[nn + "b_nn_layer1"], aff=bn0, stats=st)
         self._bn_fwd(bn1, st, parts, B, training)
-        if not (key == "lg" and self._defer_logit_out):   # (training step: the logits come out of clsr_mlp_tail_softmax)
+        if not (key == "lg" and self._step.defer_logit_out):   # (training step: the logits come out of clsr_mlp_tail_softmax)
             call("clsr_mlp_out_fwd", z1, bn1.scale, bn1.shift, P[nn + "w_nn_output"], P[nn + "b_nn_output"], B, C1, logit)
         return logit
 
     def _mlp_bwd(self, key, nn, dlogit, X, ldx, K0, K0_real, sizes, B, tail=None):
         """Returns dX [B, K0] (K0 = padded input width).  ``tail = (labels, groups, rows per group, loss scale)``: the
         output layer, the group-softmax loss and their backward run as ONE launch (the logits were not computed by the
-        forward: ``_defer_logit_out``)."""
+        forward: ``_step.defer_logit_out``)."""
         P, Gd = self.P, self.Gd
         C0, C1 = sizes
         bn0, bn1 = self.bn[nn + "batch_normalization/"], self.bn[nn + "batch_normalization_1/"]
@@ -1850,7 +1844,7 @@ class CLSRNet(object):
             #  stream, and a fill enqueued behind a fork raced with a side branch's writes in the first step of a net)
             self._t4_time_chain_bwd(f, dPinAll, Hn, T, hs)
             Wt, Kp = self.packed["xw^T"]
-            fold = self._fold_args if self.fold_hist_shares else None
+            fold = self._step.fold_args if self.fold_hist_shares else None
             if fold is None:
                 call("clsr_enc_bwd_fused", dPinAll, hist, *saved, Wt, Kp, dhist, *wss, M)
                 return
@@ -1862,7 +1856,7 @@ class CLSRNet(object):
             self._join(only="@lt")          # (the long-term attention backward wrote dhist_lt on its branch, long ago)
             call("clsr_enc_bwd_fused_fold", dPinAll, hist, *saved, Wt, Kp, dhist, dhist_lt, dM, dR, seq_len, ls, T,
                  int(self.hp.contrastive_recent_k), *wss, M)
-            self._folded = True
+            self._step.folded = True
             return
         if self.bf16:
             # (the kernel can also accumulate d(hist) = dPin . W_x^T -- Wt_bf16 / dhist arguments, tested -- but that product
@@ -1897,10 +1891,14 @@ class CLSRNet(object):
         """Run the forward pass on an uploaded feed; returns dict of device tensors.  ``after_attention(out)``
         (training) is launched on a side stream as soon as both attention outputs exist, beside the alpha / logit
         MLPs (the contrastive loss: it needs the interest vectors, not the logits)."""
-        with ops.stream_scope():
-            if training or after_attention is not None or early_aux is not None:
-                return self._forward(f, training, after_attention, early_aux)
-            return self._planned(("fwd",), f, lambda: self._forward(f, False, None, None))
+        try:
+            with ops.stream_scope():
+                if training or after_attention is not None or early_aux is not None:
+                    return self._forward(f, training, after_attention, early_aux)
+                return self._planned(("fwd",), f, lambda: self._forward(f, False, None, None))
+        except BaseException:
+            self._drop_step()
+            raise
 
     def _forward(self, f, training, after_attention, early_aux):
         hp, P = self.hp, self.P
@@ -2067,7 +2065,7 @@ class CLSRNet(object):
                                      hist_recent=hrec))
         alpha = self._buf("alpha", B)
         mo = self._buf("model_output", B, 2 * D)
-        if self._heads_defer:
+        if self._step.heads_defer:
             # training step: everything from here to d(model_output) is the first clsr_heads_fused launch (_train_step)
             logit = self._buf("lg.logit", B)
         elif not hp.manual_alpha:
@@ -2081,7 +2079,7 @@ class CLSRNet(object):
         else:
             call("clsr_alpha_fuse_fwd", None, float(hp.manual_alpha_value), att_long, att_short, target, B, G, D,
                  alpha, mo)
-        if not self._heads_defer:
+        if not self._step.heads_defer:
             logit = self._mlp_fwd("lg", "sequential/logit_fcn/nn_part/", mo, 2 * D, 2 * D, (self.L0, self.L1), B, training)
         return dict(logit=logit, alpha=alpha, att_fea_long=att_long, att_fea_short=att_short, hist_input=hist,
                     hist_mean=hmean, hist_recent=hrec, target=target, u_long=ulong, u_short=ushort,
@@ -2184,12 +2182,35 @@ class CLSRNet(object):
         with apply=False, all-reduce the gradient buffers, then call :meth:`_apply_updates`."""
         if self._aborted:
             self.check_abort()      # sticky: an aborted net is restored from a checkpoint first
-        with ops.stream_scope():
-            return self._planned(("train", bool(apply)), f, lambda: self._train_step(f, apply))
+        try:
+            with ops.stream_scope():
+                return self._planned(("train", bool(apply)), f, lambda: self._train_step(f, apply))
+        except BaseException:       # (a host exception, whatever phase raised it: the next step starts from idle state)
+            self._drop_step()
+            raise
+
+    def _drop_step(self):
+        """The ONE host-side reset and the definition of idle: no state of a step, no stream bookkeeping.  Launches nothing, never
+        synchronises (what a failed step left on the DEVICE is restored by ``load_state_dict`` / ``_reset_after_abort``)."""
+        self._step = _StepState()
+        self._joins = []                                    # finished branches the current stream has yet to wait for
+        self._dw_pending, self._rp_pending = {}, {}         # workspace tag -> partial sums the next flush reduces
+        self._dw_batch = self._dw_batch_wide = None         # jobs of an open _dw_batched() block
+        self._ws_tag, self._dw_async = "", False            # scratch-buffer suffix of a recording branch | @dw0 holds work the flush joins
+
+    @staticmethod
+    def _carver(pool):
+        """-> take(*shape): consecutive views of the flat ``pool`` (the gradient accumulators a step zeroes in one launch)."""
+        o = [0]
+
+        def take(*shape):
+            o.append(o[-1] + int(np.prod(shape)))
+            return pool[o[-2]:o[-1]].view(*shape)
+        return take
 
     def _train_step(self, f, apply):
         hp, P, Gd = self.hp, self.P, self.Gd
-        self._cur_feed = f
+        step = self._step = _StepState(f)
         B, T = f["B"], f["T"]
         G = self.G_train if self.dedup else 1
         if B % G:
@@ -2210,10 +2231,10 @@ class CLSRNet(object):
             zr = [(self.stats24.data_ptr(), 24 * 8), (zpool.data_ptr(), zpool.numel() * 4)]
             counts = self._sort_counts()[0]
             zr.append((counts.data_ptr(), counts.numel() * 4))
-            self._counts_zeroed = True
+            step.counts_zeroed = True
             if "user_long" in self.tables:
                 zr.append((self.ucount.data_ptr(), 4))
-                self._ucount_zeroed = True
+                step.ucount_zeroed = True
             if heads_fused:
                 zr.append((self._heads_ws().data_ptr(), int(query("clsr_heads_fused_counter_bytes"))))
             if self._att_qh("st") and G > 1:
@@ -2238,20 +2259,14 @@ class CLSRNet(object):
                 # regulariser).  Not under data parallelism: the count is over the EXCHANGED byte map.
                 call("clsr_count_flags_tick", fl["user_long"], self.dims["Vu"], self.ucount, self.adam_state,
                      float(hp.learning_rate), 0.9, 0.999)
-                self._ticked = True
+                step.ticked = True
             if apply and self.dp_hooks is None:
                 # ... and so do the ascending lists of the touched rows of the big tables (lazy Adam): one single-workgroup
                 # scan over the 100M-row byte map of BASELINE configs[4] is 0.33 ms + 0.15 ms of list writing -- under the
                 # forward here, they were the first half millisecond of the update phase
-                self._early_lists = {k: self._involved_list(k) for k, t in self.tables.items()
+                step.early_lists = {k: self._involved_list(k) for k, t in self.tables.items()
                                      if t.numel() > self.rowlist_min_elems}
-        o = [0]
-
-        def take(*shape):
-            n = int(np.prod(shape))
-            t = zpool[o[0]:o[0] + n].view(*shape)
-            o[0] += n
-            return t
+        take = self._carver(zpool)
         dhist, drnn, dhist_lt = take(Hn, T, D), take(Hn, T, H), take(Hn, T, D)
         dtarget, dS = take(B, D), take(B, D)
         dL, dM, dR = take(Hn, D), take(Hn, D), take(Hn, D)
@@ -2267,13 +2282,9 @@ class CLSRNet(object):
         lscale = 1.0 / ((B // Gl) * self.dp_world)
         # output layer of the logit MLP + data loss + their backward as ONE launch at the turn of the step
         fused_tail = B % Gl == 0 and bool(query("clsr_mlp_tail_softmax_supported", Gl, self.L1))
-        self._defer_logit_out = fused_tail
-        self._heads_defer = heads_fused
-        try:
-            out = self._forward(f, True, contrastive, zero_and_mark)
-        finally:
-            self._defer_logit_out = False
-            self._heads_defer = False
+        step.defer_logit_out, step.heads_defer = fused_tail, heads_fused
+        out = self._forward(f, True, contrastive, zero_and_mark)
+        step.defer_logit_out = step.heads_defer = False      # (a scoring pass before a deferred _apply_updates computes its heads)
         assert self.last_shape == (B, T, G, Hn)
         # ---- losses on the forward outputs
         dlogit = self._buf("dlogit", B)
@@ -2332,14 +2343,13 @@ class CLSRNet(object):
         if scat_early:
             self._scatter_rows_early(f, dul, None, dtarget, Hn, B, hs, fork)
             self._scatter_rows_early(f, None, dushort, None, Hn, B, hs, self._fork_point())
-            if (self.early_user_update and apply and self._ticked and self.dp_hooks is None and not self.capture_grads
+            if (self.early_user_update and apply and step.ticked and self.dp_hooks is None and not self.capture_grads
                     and "user_long" in self.tables):
                 # (same stream as the two scatters: ordered behind them; a branch name of its own -- only the end of the update
                 #  phase waits for it)
                 with self._branch("@aux", after=self._fork_point(), name="@uupd"):
                     self._update_user_tables_early()
-        self._folded = False
-        self._fold_args = (dhist_lt, dM, dR, seq_len, ls) if (self.det_grads and dhist.dtype == F32) else None
+        step.fold_args = (dhist_lt, dM, dR, seq_len, ls) if (self.det_grads and dhist.dtype == F32) else None
         if self._enc_bwd_fused_ok(dpin_h):
             self._enc_bwd_fused(f, hist, dPinAll, dhist, Hn, T, hs)
         else:
@@ -2370,13 +2380,13 @@ class CLSRNet(object):
             fork_dense = self._fork_point()
             # (only the step that applies its own update right away keeps the dense update on this stream: under data
             # parallelism the gradients are exchanged first, and the update must be ordered behind THAT, not behind this event)
-            self._dense_fork = fork_dense if (apply and self.dp_hooks is None) else None
+            step.dense_fork = fork_dense if (apply and self.dp_hooks is None) else None
             with self._branch("@dw0", after=fork_dense, name="@dense"):
                 self._dense_grads_final()
         else:
             self._dense_grads_final()
         # d(hist) = dhist + dhist_lt (the long-term branch's share): the segmented sums add the two on the fly
-        if self._folded:       # (the fused encoder tail added the long-term share and the prologue's shares to d(hist))
+        if step.folded:       # (the fused encoder tail added the long-term share and the prologue's shares to d(hist))
             dhist_lt = dM = dR = None
         # ---- embedding gradients (IndexedSlices values -> dense grad tables + squared norms)
         ss = self.sumsq_tab
@@ -2398,7 +2408,6 @@ class CLSRNet(object):
         self._dp_hook("table_ready", "item")
         if apply:
             self._apply_updates()
-            self._dense_fork = None
         elif self.dp_hooks is None:
             self._join()              # callers that read the gradients themselves: everything back on this stream
         return out
@@ -2426,9 +2435,9 @@ class CLSRNet(object):
         if self.det_grads:
             return self._sort_ids_stable(f, Hn, T, hs)
         counts, bits = self._sort_counts()
-        if not self._counts_zeroed:      # (the training step clears them with its other accumulators)
+        if not self._step.counts_zeroed:      # (the training step clears them with its other accumulators)
             call("clsr_zero_floats", counts.view(F32), counts.numel())
-        self._counts_zeroed = False
+        self._step.counts_zeroed = False
         rows, o = [], 0
         for (name, fkey, V, _, _, _), b in zip(tabs, bits):
             keys = self._buf("sort.keys." + name, n, dtype=torch.int32)
@@ -2551,7 +2560,7 @@ class CLSRNet(object):
         k = self.hp.contrastive_recent_k
         if self.det_grads:
             rows = []
-            merged = self._det_merged(self._cur_feed) if dtarget is not None else {}
+            merged = self._det_merged(self._step.cur_feed) if dtarget is not None else {}
             for name, _, V, col0, C, slot in self._sort_tables():
                 if only is not None and name != only:
                     continue
@@ -2652,36 +2661,34 @@ class CLSRNet(object):
         ops.multi("clsr_tables_reg_multi" + self._th, ops.TableDesc, rows, float(hp.embed_l2), float(hp.embed_l1), self.ucount,
                   self.losses[1:])
         self._tables_update_multi(rows, clip)
-        self._updated_early = {sp[0] for sp in spec}
+        self._step.updated_early = {sp[0] for sp in spec}
 
     def _apply_updates(self):
         hp = self.hp
+        step, self._step = self._step, _StepState()     # (the step ends here: idle from now on, whatever happens below)
         ss = self.sumsq_tab
         Vu, Vi, Vc = self.dims["Vu"], self.dims["Vi"], self.dims["Vc"]
         l2e, l1e = float(hp.embed_l2), float(hp.embed_l1)
         tb, tg, fl = self.tables, self.tab_grad, self.tab_flags
-        if "user_long" in tb:      # number of distinct users of the batch: the discrepancy loss is a mean over them
-            if not self._ucount_zeroed:      # (the training step clears it with its other accumulators)
-                call("clsr_zero_floats", self.ucount, 1)
-            self._ucount_zeroed = False
+        # number of distinct users of the batch: the discrepancy loss is a mean over them
+        if "user_long" in tb and not step.ucount_zeroed:      # (the training step clears it with its other accumulators)
+            call("clsr_zero_floats", self.ucount, 1)
         # the Adam clock ticks in the FIRST launch of the update phase (with the user count when there is one): the table
         # path and the dense path both only read it afterwards, so neither waits for the other (the clock used to tick
         # on the dense path, and the table Adam launches waited for the whole weight-gradient reduction: 50 us)
         tick_early = not self.capture_grads
         lr = float(hp.learning_rate)
-        if self._ticked:        # (count + clock went out with the row marks at the start of the step)
-            self._ticked = False
-        elif "user_long" in tb:
-            call("clsr_count_flags_tick", fl["user_long"], Vu, self.ucount, self.adam_state if tick_early else None, lr,
-                 0.9, 0.999)
-        elif tick_early:
+        # (step.ticked: count + clock went out with the row marks at the start of the step)
+        if "user_long" in tb and not step.ticked:
+            call("clsr_count_flags_tick", fl["user_long"], Vu, self.ucount, self.adam_state if tick_early else None, lr, 0.9, 0.999)
+        elif tick_early and not step.ticked:
             call("clsr_adam_tick", self.adam_state, lr, 0.9, 0.999)
         clip = float(hp.max_grad_norm) if hp.is_clip_norm else 0.0
         # dense variables (regulariser + norms, Adam clock, Adam) on the @aux stream beside the table regulariser
         # (single-GPU step with the dense path on the weight-gradient stream: the dense update STAYS on that stream, behind the
         # batched reduction -- on @aux it started two stream hops, ~25 us, after the reduction had finished, and the dense
         # Adam launch was the last kernel of the step)
-        fork = getattr(self, "_dense_fork", None)
+        fork = step.dense_fork
         on_dw = fork is not None and not self.capture_grads
         with (self._branch("@dw0", after=fork, name="@denseupd") if on_dw else
               self._branch("@main" if self.capture_grads else "@aux")):
@@ -2692,11 +2699,10 @@ class CLSRNet(object):
                  None if (self.capture_grads or tick_early) else self.adam_state, lr, 0.9, 0.999, self.dense_reg_threads)
             if not self.capture_grads:
                 self._dense_update(clip)
-        lists, self._early_lists = self._early_lists, None
+        lists = step.early_lists
         if lists is None:
             lists = {k: self._involved_list(k) for k, t in tb.items() if t.numel() > self.rowlist_min_elems}
-        done_early, self._updated_early = self._updated_early, set()
-        spec = [sp for sp in self._update_spec() if sp[0] not in done_early]
+        spec = [sp for sp in self._update_spec() if sp[0] not in step.updated_early]
         sweep = []
         for key, partner, slot, dscale, dloss_scale, dloss, base, nsum in spec:
             V, C = tb[key].shape
@@ -2856,8 +2862,7 @@ class CLSRNet(object):
                 why.append("a grid barrier of the fused heads launches timed out (the device could not hold every workgroup "
                            "of the launch at once, or a peer rank never pushed its statistics; CLSR_NO_HEADS_FUSED=1 runs "
                            "the launch chain instead)")
-            comm = getattr(self, "dp_comm", None)
-            if comm and query("clsr_comm_error", comm) != 0:
+            if self.dp_comm and query("clsr_comm_error", self.dp_comm) != 0:
                 why.append("a small all-reduce gave up waiting for a peer rank (%.1f s: CLSR_P2P_TIMEOUT_S)"
                            % (query("clsr_p2p_timeout_ms") * 1e-3))
             self._aborted = "; ".join(why) or "abort flag %g" % flag
@@ -2879,7 +2884,7 @@ class CLSRNet(object):
         self.dense_grad.zero_()
         self.stats24.zero_()
         self.ucount.zero_()
-        self._counts_zeroed = self._ucount_zeroed = self._ticked = False
+        self._drop_step()
         self._aborted = None
 
     def read_losses(self):

@@ -21,7 +21,7 @@ import numpy as np
 import torch
 
 from clsr_amd import ops
-from clsr_amd.net import CLSRNet, _pad4
+from clsr_amd.net import CLSRNet, _StepState, _pad4
 from clsr_amd.ops import call, query
 from clsr_amd.params import SIB_TABLES, UNUSED_TABLE, sibling_kind, sibling_scopes, sibling_specs
 
@@ -277,6 +277,7 @@ class SeqNet(CLSRNet):
     # ------------------------------------------------------------------ training step
     def _train_step(self, f, apply):
         hp, P, Gd, kind, sc = self.hp, self.P, self.Gd, self.kind, self.sc
+        self._step = _StepState()      # (these graphs set none of its fields: the shared phases read an idle one)
         B, T = f["B"], f["T"]
         G = self.G_train if self.dedup else 1
         Hn = B // G
@@ -296,13 +297,7 @@ class SeqNet(CLSRNet):
                 (f["items"].data_ptr(), fl["item"].data_ptr(), B, 1, 1, 0),
                 (f["item_cate_history"].data_ptr(), fl["cate"].data_ptr(), Hn, hs * T, T, 0),
                 (f["cates"].data_ptr(), fl["cate"].data_ptr(), B, 1, 1, 0)])
-        o = [0]
-
-        def take(*shape):
-            n = int(np.prod(shape))
-            t_ = zpool[o[0]:o[0] + n].view(*shape)
-            o[0] += n
-            return t_
+        take = self._carver(zpool)
         dhist, drnn = take(Hn, T, D), take(Hn, T, H)
         dtarget, dS, datt = take(B, D), take(B, D), take(B, D)
         dL, dM, dR, dhT = take(Hn, D), take(Hn, D), take(Hn, D), take(Hn, H)

@@ -238,3 +238,68 @@ def test_row_list_optimizer_path_equals_sweep(golden_dir, golden_hparams):
     for k in fl0:   # both paths leave the flags and gradient tables cleared for the next step
         assert int(fl1[k].sum()) == 0 and int(fl0[k].sum()) == 0
         assert float(tg1[k].abs().max()) == 0.0 and float(tg0[k].abs().max()) == 0.0
+
+
+def _step_is_idle(net):
+    fresh = type(net._step)()
+    return all(getattr(net._step, k) == getattr(fresh, k) for k in fresh.__slots__)
+
+
+def _fail_a_step(net, f, monkeypatch):
+    """One training step that raises on the HOST between the forward and the backward of the heads (nothing faults on the
+    device); the monkeypatch is undone before returning."""
+    def boom(*a, **kw):
+        raise RuntimeError("host exception inside a step")
+
+    with monkeypatch.context() as m:
+        m.setattr(net, "_heads_fused_step", boom)
+        m.setattr(net, "_heads_bwd_launches", boom)
+        with pytest.raises(RuntimeError, match="host exception inside a step"):
+            net.train_step(f)
+
+
+@pytest.mark.parametrize("overlap", [True, False])
+def test_host_exception_in_a_step_leaves_no_step_state(golden_dir, golden_hparams, monkeypatch, overlap):
+    """A step that raises on the host leaves neither per-step state nor stream bookkeeping for the next step to trip over."""
+    _, net, _ = _setup(golden_hparams, True)
+    net.overlap = overlap
+    f = net.upload(_feed(golden_dir, "iterator_train_sa.npz", b=0), True)
+    net.train_step(f)
+    assert _step_is_idle(net)
+    _fail_a_step(net, f, monkeypatch)
+    torch.cuda.synchronize()
+    assert _step_is_idle(net)
+    assert net._joins == []
+    assert not any(net._dw_pending.values()) and not any(net._rp_pending.values())
+    assert net._dw_batch is None
+    assert net._ws_tag == ""
+    assert not net._dw_async
+
+
+def test_failed_step_does_not_change_the_next_update(golden_dir, golden_hparams, monkeypatch):
+    """Twin nets, one of which went through a step that raised on the host: restored from the same checkpoint, both make
+    the bit-identical next update the way the data-parallel stepper drives it (``train_step(apply=False)`` +
+    ``_apply_updates()``), and the Adam clock advances by one on both.  Two UNDISTURBED twins are bit-equal through this
+    sequence (deterministic embedding gradients, batched weight-gradient reduction; checked on the commit before this
+    test existed), so the comparison is exact.  A stale ``ticked`` left by the failed step made the update skip the clock
+    and the distinct-user count."""
+    from clsr_amd import ops
+
+    feed = _feed(golden_dir, "iterator_train_sa.npz", b=0)
+    (_, a, _), (_, b, _) = _setup(golden_hparams, True), _setup(golden_hparams, True)
+    ck = a.state_dict()
+    fa, fb = a.upload(feed, True), b.upload(feed, True)
+    _fail_a_step(b, fb, monkeypatch)
+    torch.cuda.synchronize()
+    for net, f in ((a, fa), (b, fb)):
+        net.load_state_dict(ck)
+        t0 = float(net.adam_state[0])
+        with ops.stream_scope():
+            net.train_step(f, apply=False)
+            net._apply_updates()
+        torch.cuda.synchronize()
+        assert float(net.adam_state[0]) == t0 + 1.0
+    sa, sb = a.state_dict(), b.state_dict()
+    assert sa.keys() == sb.keys()
+    for k in sa:
+        assert torch.equal(sa[k], sb[k]), k
