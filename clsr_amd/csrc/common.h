@@ -175,6 +175,50 @@ template <bool H> __device__ __forceinline__ void tbl_st4(void* p, long e, f32x4
   else *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(p) + e) = v;
 }
 
+// bf16 table with an exact fp32 master in the same bytes as an fp32 table: next to the bf16 bits `hi` a 16-bit residual `lo`
+// such that the 32 bits of the master are  b = (hi << 16) + sign_extend(lo)  (mod 2^32).  hi = (b + 0x8000) >> 16 is b rounded
+// to the nearest bf16 in magnitude, ties away from zero (nearest-even cannot be encoded: an even hi would have 65 537
+// preimages), lo = b - (hi << 16) in [-0x8000, 0x7fff].  A non-finite master keeps its top half (NaN: quiet bit set, the
+// integer add would wrap 0xffffxxxx to zero) and lo = 0, so hm_unpack needs no special case.  The forward pass reads hi only;
+// the `_hm` optimiser kernels (csrc/optim.hip, csrc/multi.hip) read and write both.
+typedef unsigned short u16x4_t __attribute__((ext_vector_type(4)));
+typedef short i16x4_t __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ void hm_pack(float x, unsigned short& hi, short& lo) {
+  const unsigned b = __float_as_uint(x);
+  if ((b & 0x7f800000u) == 0x7f800000u) {
+    hi = (unsigned short)((b >> 16) | ((b & 0x007fffffu) ? 0x0040u : 0u));
+    lo = 0;
+    return;
+  }
+  const unsigned h = (b + 0x8000u) >> 16;
+  hi = (unsigned short)h;
+  lo = (short)(unsigned short)(b - (h << 16));
+}
+__device__ __forceinline__ float hm_unpack(unsigned short hi, short lo) {
+  return __uint_as_float(((unsigned)hi << 16) + (unsigned)(int)lo);
+}
+// four consecutive elements (8-byte accesses of both halves; element index e: multiple of 4, both pointers 8-byte aligned)
+__device__ __forceinline__ f32x4 hm_unpack4(u16x4_t hi, i16x4_t lo) {
+  f32x4 r;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) r[k] = hm_unpack(hi[k], lo[k]);
+  return r;
+}
+__device__ __forceinline__ void hm_st4(void* hi, void* lo, long e, f32x4 w) {
+  u16x4_t h;
+  i16x4_t l;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    unsigned short hk;
+    short lk;
+    hm_pack(w[k], hk, lk);
+    h[k] = hk;
+    l[k] = lk;
+  }
+  *reinterpret_cast<u16x4_t*>(reinterpret_cast<unsigned short*>(hi) + e) = h;
+  *reinterpret_cast<i16x4_t*>(reinterpret_cast<short*>(lo) + e) = l;
+}
+
 // Wave priority of the kernels on the step's dependency chain (everything except the weight-gradient partial-sum
 // kernels, which run beside it on their own stream): their waves issue ahead of the MFMA-saturated weight-gradient waves
 // that share their SIMDs.  In-step kernel times on the chain summed to 3.47 ms against 2.77 ms for the same kernels

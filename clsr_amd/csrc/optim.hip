@@ -586,6 +586,172 @@ extern "C" int clsr_table_adam_rows(float* table, float* grad_table, float* m, f
   return CLSR_OK;
 }
 
+// ---- bf16 tables with an exact fp32 master (common.h: hm_pack / hm_unpack): the table is the pair (hi = the bf16 values
+// every other kernel reads, lo = 16-bit residual); the update rebuilds the fp32 master from both halves, updates it exactly
+// as the fp32 kernels do and stores both halves back -- no update is lost to the bf16 rounding, and a step stays
+// deterministic.  Per element g, m, v (4 + 4 bytes each) + hi (2 + 2) + lo (2 + 2) = 32 bytes: the fp32 update's traffic.
+//
+// The row-list form: table_adam_rows_h_kernel<2> with a second 8-byte stream per piece.
+template <int UN>
+__global__ void __launch_bounds__(256) table_adam_rows_hm_kernel(
+    unsigned short* __restrict__ hi, short* __restrict__ lo, float* __restrict__ grad_table, float* __restrict__ m,
+    float* __restrict__ v, unsigned char* __restrict__ flags, const int* __restrict__ ids, const int* __restrict__ count,
+    int C, const double* __restrict__ sumsq, int sumsq_stride, int nsum, float clip_norm,
+    const double* __restrict__ adam_state, float b1, float b2, float eps) {
+  double tot = 0.0;
+  for (int i = 0; i < nsum; ++i) tot += sumsq[(long)i * sumsq_stride];
+  const float factor = clip_factor(tot, clip_norm);
+  if (adam_state[4] != 0.0) return;      // the step was aborted (a collective / grid barrier gave up): touch nothing
+  const float lr_t = (float)adam_state[3];
+  const int QC = C / 4;
+  const long total = (long)count[0] * QC;
+  const long stride = (long)gridDim.x * blockDim.x;
+  for (long i0 = (long)blockIdx.x * blockDim.x + threadIdx.x; i0 < total; i0 += stride * UN) {
+    long e[UN], row[UN];
+    int q[UN];
+    bool ok[UN];
+    f32x4 g[UN], mo[UN], vo[UN];
+    u16x4_t ph[UN];
+    i16x4_t pl[UN];
+#pragma unroll
+    for (int u = 0; u < UN; ++u) {
+      const long i = i0 + u * stride;
+      ok[u] = i < total;
+      const long ic = ok[u] ? i : i0;
+      const long r = ic / QC;
+      q[u] = (int)(ic - r * QC);
+      row[u] = ids[r];
+      e[u] = row[u] * C + (long)q[u] * 4;
+    }
+#pragma unroll
+    for (int u = 0; u < UN; ++u) {
+      g[u] = ld4(grad_table + e[u]);
+      mo[u] = ld4(m + e[u]);
+      vo[u] = ld4(v + e[u]);
+      ph[u] = *reinterpret_cast<const u16x4_t*>(hi + e[u]);
+      pl[u] = *reinterpret_cast<const i16x4_t*>(lo + e[u]);
+    }
+#pragma unroll
+    for (int u = 0; u < UN; ++u) {
+      f32x4 po = hm_unpack4(ph[u], pl[u]);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const float gg = g[u][k] * factor;
+        const float mm = b1 * mo[u][k] + (1.0f - b1) * gg;
+        const float vv = b2 * vo[u][k] + (1.0f - b2) * gg * gg;
+        mo[u][k] = mm;
+        vo[u][k] = vv;
+        po[k] -= lr_t * mm / (sqrtf(vv) + eps);
+      }
+      if (ok[u]) {
+        const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+        st4(m + e[u], mo[u]);
+        st4(v + e[u], vo[u]);
+        hm_st4(hi, lo, e[u], po);
+        st4(grad_table + e[u], z);
+        if (q[u] == 0) flags[row[u]] = 0;
+      }
+    }
+  }
+}
+
+extern "C" int clsr_table_adam_rows_hm(void* hi, void* lo, float* grad_table, float* m, float* v, unsigned char* flags,
+                                       const int* ids, const int* count, int cap, int C, const double* sumsq,
+                                       int sumsq_stride, int nsum, float clip_norm, const double* adam_state,
+                                       float beta1, float beta2, float eps, void* stream) {
+  CLSR_CHECK_ARG(hi && lo && grad_table && m && v && flags && ids && count && sumsq && adam_state && cap > 0 && C > 0);
+  CLSR_CHECK_ARG(nsum > 0);
+  CLSR_CHECK_SUPPORTED(C % 4 == 0 && ((uintptr_t)hi % 8) == 0 && ((uintptr_t)lo % 8) == 0);
+  int blocks = clsr_cdiv((long)cap * C, 256 * 4 * 2);
+  if (blocks > 4096) blocks = 4096;
+  hipLaunchKernelGGL(table_adam_rows_hm_kernel<2>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (unsigned short*)hi,
+                     (short*)lo, grad_table, m, v, flags, ids, count, C, sumsq, sumsq_stride, nsum, clip_norm, adam_state,
+                     beta1, beta2, eps);
+  CLSR_CHECK_LAUNCH();
+  return CLSR_OK;
+}
+
+// The sweep of one table (table_adam_kernel), dense or lazy; clears gradient rows and flags like the other forms.
+__global__ void __launch_bounds__(256) table_adam_hm_kernel(
+    unsigned short* __restrict__ hi, short* __restrict__ lo, float* __restrict__ grad_table, float* __restrict__ m,
+    float* __restrict__ v, const unsigned char* __restrict__ flags, long V, int C, const double* __restrict__ sumsq,
+    int sumsq_stride, int nsum, float clip_norm, const double* __restrict__ adam_state, float b1, float b2, float eps,
+    int lazy) {
+  double tot = 0.0;
+  for (int i = 0; i < nsum; ++i) tot += sumsq[(long)i * sumsq_stride];
+  const float factor = clip_factor(tot, clip_norm);
+  if (adam_state[4] != 0.0) return;      // the step was aborted (a collective / grid barrier gave up): touch nothing
+  const float lr_t = (float)adam_state[3];
+  const long total = V * C;
+  for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
+    const long row = e / C;
+    const float g = grad_table[e] * factor;
+    if (lazy && !flags[row]) continue;  // every row that got gradient is also flagged as involved
+    const float mm = b1 * m[e] + (1.0f - b1) * g;
+    const float vv = b2 * v[e] + (1.0f - b2) * g * g;
+    m[e] = mm;
+    v[e] = vv;
+    unsigned short h;
+    short l;
+    hm_pack(hm_unpack(hi[e], lo[e]) - lr_t * mm / (sqrtf(vv) + eps), h, l);
+    hi[e] = h;
+    lo[e] = l;
+    grad_table[e] = 0.f;
+  }
+}
+
+extern "C" int clsr_table_adam_hm(void* hi, void* lo, float* grad_table, float* m, float* v, unsigned char* flags, long V,
+                                  int C, const double* sumsq, int sumsq_stride, int nsum, float clip_norm,
+                                  const double* adam_state, float beta1, float beta2, float eps, int lazy, void* stream) {
+  CLSR_CHECK_ARG(hi && lo && grad_table && m && v && flags && sumsq && adam_state && V > 0 && C > 0 && nsum > 0);
+  int blocks = clsr_cdiv(V * C, 256);
+  if (blocks > 4096) blocks = 4096;
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(table_adam_hm_kernel, dim3(blocks), dim3(256), 0, s, (unsigned short*)hi, (short*)lo, grad_table, m, v,
+                     flags, V, C, sumsq, sumsq_stride, nsum, clip_norm, adam_state, beta1, beta2, eps, lazy);
+  CLSR_CHECK_LAUNCH();
+  int cb = clsr_cdiv(V, 256);
+  if (cb > 1024) cb = 1024;
+  hipLaunchKernelGGL(clear_bytes_kernel, dim3(cb), dim3(256), 0, s, flags, V);
+  CLSR_CHECK_LAUNCH();
+  return CLSR_OK;
+}
+
+// fp32 values -> (hi, lo) and back (construction, checkpoints); n elements, any alignment
+__global__ void __launch_bounds__(256) table_split_hm_kernel(const float* __restrict__ src, unsigned short* __restrict__ hi,
+                                                             short* __restrict__ lo, long n) {
+  for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (long)gridDim.x * blockDim.x) {
+    unsigned short h;
+    short l;
+    hm_pack(src[e], h, l);
+    hi[e] = h;
+    lo[e] = l;
+  }
+}
+__global__ void __launch_bounds__(256) table_merge_hm_kernel(const unsigned short* __restrict__ hi,
+                                                             const short* __restrict__ lo, float* __restrict__ dst, long n) {
+  for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (long)gridDim.x * blockDim.x)
+    dst[e] = hm_unpack(hi[e], lo[e]);
+}
+extern "C" int clsr_table_split_hm(const float* src, void* hi, void* lo, long n, void* stream) {
+  CLSR_CHECK_ARG(src && hi && lo && n > 0);
+  int blocks = clsr_cdiv(n, 256);
+  if (blocks > 4096) blocks = 4096;
+  hipLaunchKernelGGL(table_split_hm_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, src, (unsigned short*)hi,
+                     (short*)lo, n);
+  CLSR_CHECK_LAUNCH();
+  return CLSR_OK;
+}
+extern "C" int clsr_table_merge_hm(const void* hi, const void* lo, float* dst, long n, void* stream) {
+  CLSR_CHECK_ARG(hi && lo && dst && n > 0);
+  int blocks = clsr_cdiv(n, 256);
+  if (blocks > 4096) blocks = 4096;
+  hipLaunchKernelGGL(table_merge_hm_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const unsigned short*)hi,
+                     (const short*)lo, dst, n);
+  CLSR_CHECK_LAUNCH();
+  return CLSR_OK;
+}
+
 // p[0..n) = 0 (doubles)
 __global__ void zero_d_kernel(double* p, int n) {
   const int e = blockIdx.x * blockDim.x + threadIdx.x;

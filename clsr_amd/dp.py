@@ -267,6 +267,8 @@ class DataParallel(object):
         net, dist = self.net, self.dist
         tensors = [net.dense, net.dense_m, net.dense_v, net.adam_state]
         tensors += list(net.tables.values()) + list(net.tab_m.values()) + list(net.tab_v.values())
+        # (table_master: the residual halves of the fp32 masters; as bytes -- not every backend broadcasts int16)
+        tensors += [t.view(torch.uint8) for t in getattr(net, "tab_lo", {}).values()]     # (tests/test_dp_cpu.py drives this with a stub net)
         tensors.append(net.bn_moving)
         tensors = [t for t in tensors if t is not None]     # (optimisers with fewer than two slots allocate fewer)
         for t in tensors:

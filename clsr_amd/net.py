@@ -103,7 +103,8 @@ class _StepState(object):
 
 
 class CLSRNet(object):
-    def __init__(self, hp, dims, device="cuda:0", seed=None, dedup_histories=True, precision="fp32", table_dtype="fp32"):
+    def __init__(self, hp, dims, device="cuda:0", seed=None, dedup_histories=True, precision="fp32", table_dtype="fp32",
+                 table_master=False):
         self.hp = hp
         self.dims = dict(dims)
         self.device = torch.device(device)
@@ -113,7 +114,8 @@ class CLSRNet(object):
         self.precision = precision
         # embedding tables stored as bf16 (SURVEY 8d configs 2, 3, 5 "bf16 tables"): the lookups widen the 2-byte rows, the
         # gradients / Adam moments stay fp32, the (lazy-)Adam update widens a row, updates it in fp32 and writes it back
-        # rounded to nearest-even (no fp32 master copy: an update below half a bf16 ulp of the weight is lost)
+        # rounded to nearest-even (no fp32 master copy: an update below half a bf16 ulp of the weight is lost -- unless
+        # table_master, below)
         if table_dtype not in ("fp32", "bf16"):
             raise ValueError("table_dtype must be 'fp32' or 'bf16'")
         self.table_bf16 = table_dtype == "bf16"
@@ -122,6 +124,14 @@ class CLSRNet(object):
         if self.table_bf16 and (hp.item_embedding_dim % 8 or hp.cate_embedding_dim % 8 or hp.user_embedding_dim % 4):
             raise NotImplementedError("table_dtype='bf16' needs item / cate embedding dims that are multiples of 8")
         self._th = "_h" if self.table_bf16 else ""          # suffix of the table kernels' entry points
+        # table_master: next to every bf16 table (hi) a 16-bit residual table (tab_lo) such that (hi, lo) is one exact fp32
+        # master value (include/clsr_hip.h: the `_hm` kernels) -- optimiser state, as in any mixed-precision trainer: the
+        # model's weights stay the bf16 values (lookups, regulariser, discrepancy term read hi only), the (lazy-)Adam update
+        # reads and writes both halves, so that no update is lost to the bf16 rounding.  Same bytes as fp32 tables.
+        self.table_master = bool(table_master)
+        if self.table_master and not self.table_bf16:
+            raise ValueError("table_master=True keeps an fp32 master for bf16 tables: it needs table_dtype='bf16'")
+        self._tu = "_hm" if self.table_master else self._th     # ... of the Adam updates of the tables
         self._check_supported()
         self.optimizer = resolve_optimizer(hp.optimizer)
         # non-Adam optimisers: kernel code + slots (TF_OPTIMIZERS); None for (lazy)Adam
@@ -332,8 +342,8 @@ class CLSRNet(object):
     #: every attribute that can differ between two nets or be flipped on a live net (environment switches, tests) and that
     #: changes the recorded launch sequence: ONE tuple, so that flipping any of them records a new plan instead of silently
     #: replaying the old one
-    _SWITCHES = ("precision", "table_bf16", "exact_products", "x3", "bf16", "overlap", "defer_dw", "det_grads", "lazy",
-                 "use_plans", "heads_fused", "early_user_update", "fold_hist_shares", "enc_x6", "rnn_products", "rnn_fused_proj",
+    _SWITCHES = ("precision", "table_bf16", "table_master", "exact_products", "x3", "bf16", "overlap", "defer_dw", "det_grads",
+                 "lazy", "use_plans", "heads_fused", "early_user_update", "fold_hist_shares", "enc_x6", "rnn_products", "rnn_fused_proj",
                  "rnn_act_tiled", "att_bwd", "att_bwd_l0", "_l1x", "_l0x", "bf16_chain", "dw_wide", "dw_wide_entry", "split_query",
                  "split_query_min", "rowlist_min_elems", "att_hist_bwd_pieces", "proj_gate_pieces", "proj_bwd_pieces",
                  "proj_wide_pieces")
@@ -411,6 +421,7 @@ class CLSRNet(object):
         self.P, self.Gd = OrderedDict(), OrderedDict()
         host = torch.zeros(self.n_dense, dtype=F32)
         self.tables, self.tab_grad, self.tab_m, self.tab_v, self.tab_flags = {}, {}, {}, {}, {}
+        self.tab_lo, self._tab_key = {}, {}     # table_master: int16 residual per table | variable name -> table key
         # gradient tables and involved-row flags live in ONE flat buffer each (one collective per kind)
         tshape = {k: [tuple(sh) for n, sh, _ in specs if n == v][0] for k, v in TABLES.items()}
         goff, foff = {}, {}
@@ -437,7 +448,19 @@ class CLSRNet(object):
             big = name in table_names and int(np.prod(shape)) > (1 << 27)
             val = None if big else init_tensor(kind, tuple(shape), hp, gen)
             if name in table_names:
-                if big:   # 100M-item catalogues: initialise in place on the device (no 38 GB host copy)
+                master = self.table_master and name not in self._unused_tables()
+                if big and master:      # ... and no fp32 image of the whole table either: drawn and split in row chunks
+                    # (chunked draws: the master of such a table is NOT the values an fp32 / plain bf16 net of this seed
+                    #  draws in one piece -- that equality holds for the tables drawn on the host, below)
+                    t = torch.empty(tuple(shape), dtype=torch.bfloat16, device=dev)
+                    lo = torch.empty(tuple(shape), dtype=torch.int16, device=dev)
+                    v0 = float(hp.init_value)
+                    for r0, r1 in self._row_chunks(t):
+                        c = torch.empty((r1 - r0,) + tuple(shape[1:]), dtype=F32, device=dev)
+                        torch.nn.init.trunc_normal_(c, mean=0.0, std=v0, a=-2 * v0, b=2 * v0)
+                        self._split_master(t[r0:r1], lo[r0:r1], c)
+                        del c
+                elif big:   # 100M-item catalogues: initialise in place on the device (no 38 GB host copy)
                     t = torch.empty(tuple(shape), dtype=F32, device=dev)
                     v0 = float(hp.init_value)
                     torch.nn.init.trunc_normal_(t, mean=0.0, std=v0, a=-2 * v0, b=2 * v0)
@@ -446,7 +469,15 @@ class CLSRNet(object):
                 self.P[name] = t
                 if name not in self._unused_tables():
                     key = [k for k, v in TABLES.items() if v == name][0]
-                    if self.table_bf16:
+                    self._tab_key[name] = key
+                    if master:
+                        if not big:     # master = the fp32 values this seed draws: hi = t rounded, lo = what the rounding dropped
+                            src, t = t, torch.empty(tuple(shape), dtype=torch.bfloat16, device=dev)
+                            lo = torch.empty(tuple(shape), dtype=torch.int16, device=dev)
+                            self._split_master(t, lo, src)
+                        self.P[name] = t
+                        self.tab_lo[key] = lo
+                    elif self.table_bf16:
                         t = t.to(torch.bfloat16)
                         self.P[name] = t
                     self.tables[key] = t
@@ -464,6 +495,8 @@ class CLSRNet(object):
                 self.P[name] = self.dense[o:o + n].view(*shape)
                 self.Gd[name] = self.dense_grad[o:o + n].view(*shape)
         self.dense.copy_(host)
+        # (table_master: address of a table's bf16 half -> address of its residual half; neither is ever reallocated)
+        self._lo_of = {self.tables[k].data_ptr(): t.data_ptr() for k, t in self.tab_lo.items()}
         # batch-norm layers
         self.bn = {}
         for name in self.dense_names:
@@ -503,12 +536,43 @@ class CLSRNet(object):
                 t.fill_(v)
         self.adam_state[:4].copy_(torch.tensor([0.0, 1.0, 1.0, 0.0], dtype=torch.float64))
 
+    #: table_master: fp32 <-> (hi, lo) conversions of a table with more elements than this go through row chunks of at most
+    #: this many elements, so that no fp32 image of a whole 100M-item table is made on the device
+    master_chunk_elems = 1 << 27
+
+    def _row_chunks(self, t):
+        V = int(t.shape[0])
+        step = V if t.numel() <= self.master_chunk_elems else max(1, self.master_chunk_elems // (t.numel() // V))
+        return [(r, min(V, r + step)) for r in range(0, V, step)]
+
+    def _split_master(self, hi, lo, src):
+        """(hi, lo) <- the fp32 values ``src`` (host or device tensor of hi's shape), clsr_table_split_hm in row chunks."""
+        for r0, r1 in self._row_chunks(hi):
+            s = src[r0:r1].to(device=self.device, dtype=F32).contiguous()
+            call("clsr_table_split_hm", s, hi[r0:r1], lo[r0:r1], s.numel())
+
+    def master(self, key, device=None):
+        """The fp32 master of table ``key`` of a ``table_master`` net: the exact reconstruction of (tables[key], tab_lo[key]),
+        as a new tensor on ``device`` (default: the net's; anywhere else the table travels in row chunks)."""
+        hi, lo = self.tables[key], self.tab_lo[key]
+        out = torch.empty(hi.shape, dtype=F32, device=self.device if device is None else device)
+        for r0, r1 in self._row_chunks(hi):
+            buf = out[r0:r1] if out.device == hi.device else torch.empty((r1 - r0,) + tuple(hi.shape[1:]), dtype=F32,
+                                                                        device=self.device)
+            call("clsr_table_merge_hm", hi[r0:r1], lo[r0:r1], buf, buf.numel())
+            if buf.device != out.device:
+                out[r0:r1].copy_(buf)
+        return out
+
     def state_dict(self):
         """All variables under their TF names + BN moving stats + Adam slots (checkpoint payload).  Raises ``StepAborted``
         instead of handing out the state an aborted step left behind (check_abort)."""
         self.check_abort()
         sd = OrderedDict()
         for name, t in self.P.items():
+            if name in self._tab_key and self.table_master:      # the fp32 master, not its bf16 half
+                sd[name] = self.master(self._tab_key[name], device="cpu")
+                continue
             sd[name] = t.detach().float().cpu().clone()      # (bf16 tables: widened -- the payload is always fp32)
         for scope, bn in self.bn.items():
             sd[scope + "moving_mean"] = bn.moving_mean.cpu().clone()
@@ -554,7 +618,11 @@ class CLSRNet(object):
                 src = torch.as_tensor(np.asarray(sd[name]), dtype=F32)
                 if tuple(src.shape) != tuple(t.shape):
                     raise ValueError("shape mismatch for %s: %s vs %s" % (name, tuple(src.shape), tuple(t.shape)))
-                t.copy_(src)
+                if name in self._tab_key and self.table_master:
+                    # (not copy_ into the bf16 half: that rounds to nearest-even and would leave the residuals stale)
+                    self._split_master(t, self.tab_lo[self._tab_key[name]], src)
+                else:
+                    t.copy_(src)
             elif strict:
                 raise KeyError(name)
         for scope, bn in self.bn.items():
@@ -2628,11 +2696,18 @@ class CLSRNet(object):
                 ops._ptr(self.tab_v.get(key)), self.tab_flags[key].data_ptr(), ss[slot:].data_ptr(), ops._ptr(dloss),
                 ss[base:].data_ptr(), V, C, nsum, 2, dscale, dloss_scale, 0)
 
+    def _tab_halves(self, key):
+        """Leading arguments of a single-table Adam entry: the table -- with ``table_master`` its bf16 and residual halves."""
+        return (self.tables[key], self.tab_lo[key]) if self.table_master else (self.tables[key],)
+
     def _tables_update_multi(self, rows, clip):
         """Optimiser update of the small tables of ``rows`` (_sweep_row tuples) in one launch."""
         if self.tf_opt is not None:     # touched rows only (IndexedSlices), flags cleared by the launch
             ops.multi("clsr_tables_tf_multi", ops.TableDesc, rows, self.tf_opt[0], clip, self.adam_state,
                       float(self.hp.learning_rate))
+        elif self.table_master:         # (rows[i][0]: the bf16 half of the table; its residual half rides beside the descriptors)
+            ops.multi("clsr_tables_adam_multi_hm", ops.TableDesc, rows, clip, self.adam_state, 0.9, 0.999, 1e-8, self.lazy,
+                      lo=[self._lo_of[r[0]] for r in rows])
         else:
             ops.multi("clsr_tables_adam_multi" + self._th, ops.TableDesc, rows, clip, self.adam_state, 0.9, 0.999, 1e-8,
                       self.lazy)
@@ -2732,11 +2807,11 @@ class CLSRNet(object):
                      fl[key], ids, count, cap, C, ss[base:], 2, nsum, clip, self.adam_state, lr)
             elif key in lists and self.lazy:
                 ids, count, cap = lists[key]
-                call("clsr_table_adam_rows" + self._th, tb[key], tg[key], self.tab_m[key], self.tab_v[key], fl[key], ids, count,
-                     cap, C, ss[base:], 2, nsum, clip, self.adam_state, 0.9, 0.999, 1e-8)
+                call("clsr_table_adam_rows" + self._tu, *self._tab_halves(key), tg[key], self.tab_m[key], self.tab_v[key],
+                     fl[key], ids, count, cap, C, ss[base:], 2, nsum, clip, self.adam_state, 0.9, 0.999, 1e-8)
             elif key in lists:   # huge table with the reference's dense Adam: the O(vocabulary) sweep is inherent
-                call("clsr_table_adam" + self._th, tb[key], tg[key], self.tab_m[key], self.tab_v[key], fl[key], V, C, ss[base:],
-                     2, nsum, clip, self.adam_state, 0.9, 0.999, 1e-8, self.lazy)
+                call("clsr_table_adam" + self._tu, *self._tab_halves(key), tg[key], self.tab_m[key], self.tab_v[key], fl[key],
+                     V, C, ss[base:], 2, nsum, clip, self.adam_state, 0.9, 0.999, 1e-8, self.lazy)
             else:
                 rest.append(key)
         if rest:

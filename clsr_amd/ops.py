@@ -488,8 +488,9 @@ def _check_multi_sizes():
     _multi_checked = True
 
 
-def multi(name, cls, rows, *extra):
-    """Launch ``name`` (a clsr_*_multi entry point) on a list of descriptor field tuples (chunks of 16)."""
+def multi(name, cls, rows, *extra, lo=None):
+    """Launch ``name`` (a clsr_*_multi entry point) on a list of descriptor field tuples (chunks of 16).  ``lo``: one
+    device address per row, passed as a parallel pointer array behind the descriptors (clsr_tables_adam_multi_hm)."""
     _check_multi_sizes()
     lim = 4 if cls is TableDesc else 16
     for i in range(0, len(rows), lim):
@@ -499,7 +500,12 @@ def multi(name, cls, rows, *extra):
         for d, row in zip(arr, chunk):
             for (fname, _), val in zip(cls._fields_, row):
                 setattr(d, fname, val)
-        call(name, ctypes.addressof(arr), len(chunk), *extra)
+        if lo is None:
+            call(name, ctypes.addressof(arr), len(chunk), *extra)
+        else:
+            ptrs = (ctypes.c_void_p * len(chunk))(*lo[i:i + lim])
+            keep_alive(ptrs)
+            call(name, ctypes.addressof(arr), ctypes.addressof(ptrs), len(chunk), *extra)
 
 
 def kp_for(K):

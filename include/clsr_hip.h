@@ -811,6 +811,22 @@ int clsr_table_adam_rows_h(void* table_bf16, float* grad_table, float* m, float*
                            const int* ids, const int* count, int cap, int C, const double* sumsq,
                            int sumsq_stride, int nsum, float clip_norm, const double* adam_state,
                            float beta1, float beta2, float eps, void* stream);
+/* bf16 tables with an exact fp32 master (the `_hm` forms): next to the bf16 table hi [V, C] a 16-bit residual table
+ * lo [V, C] (int16) such that the 32 bits of the fp32 master are  b = (hi << 16) + sign_extend(lo)  mod 2^32, with
+ * hi = (b + 0x8000) >> 16 (nearest bf16 in magnitude, ties away from zero) and lo = b - (hi << 16) in [-0x8000, 0x7fff];
+ * a non-finite master is stored as hi = its top 16 bits (NaN: | 0x0040), lo = 0.  The forward pass, the regulariser and the
+ * discrepancy term read hi with the `_h` kernels; the updates below rebuild the master, update it as the fp32 kernels do
+ * and store both halves (32 bytes per element: the fp32 update's traffic).  Same clearing of gradient rows / flags and the
+ * same abort rule as the fp32 forms.  clsr_table_adam_rows_hm: C % 4 == 0, hi and lo 8-byte aligned. */
+int clsr_table_split_hm(const float* src, void* hi, void* lo, long n, void* stream);
+int clsr_table_merge_hm(const void* hi, const void* lo, float* dst, long n, void* stream);
+int clsr_table_adam_hm(void* hi, void* lo, float* grad_table, float* m, float* v, unsigned char* flags, long V,
+                       int C, const double* sumsq, int sumsq_stride, int nsum, float clip_norm,
+                       const double* adam_state, float beta1, float beta2, float eps, int lazy, void* stream);
+int clsr_table_adam_rows_hm(void* hi, void* lo, float* grad_table, float* m, float* v, unsigned char* flags,
+                            const int* ids, const int* count, int cap, int C, const double* sumsq,
+                            int sumsq_stride, int nsum, float clip_norm, const double* adam_state,
+                            float beta1, float beta2, float eps, void* stream);
 int clsr_zero_doubles(double* p, int n, void* stream);
 int clsr_add_doubles(double* dst, const double* src, int n, void* stream);
 int clsr_zero_floats(float* p, long n, void* stream);
@@ -911,6 +927,10 @@ int clsr_tables_adam_multi(const clsr_table_desc* descs_host, int n, float clip_
                            float beta1, float beta2, float eps, int lazy, void* stream);
 int clsr_tables_adam_multi_h(const clsr_table_desc* descs_host, int n, float clip_norm, const double* adam_state,
                              float beta1, float beta2, float eps, int lazy, void* stream);
+/* bf16 tables with an fp32 master (see clsr_table_adam_hm): desc.table is the bf16 half, lo_ptrs_host[i] (host array of n
+ * device pointers) the int16 residual table of descriptor i */
+int clsr_tables_adam_multi_hm(const clsr_table_desc* descs_host, void* const* lo_ptrs_host, int n, float clip_norm,
+                              const double* adam_state, float beta1, float beta2, float eps, int lazy, void* stream);
 /* ---- the reference's other optimisers (csrc/optim_tf.hip, base_model.py:249-279, TF 1.15 defaults):
  *      opt 0 = GradientDescent (sgd, gd, pgd), 1 = Adagrad, 2 = ProximalAdagrad, 3 = RMSProp, 4 = Adadelta, 5 = Ftrl.
  *      s1 / s2 are the optimiser's slots in TF's order (adagrad: accumulator; rmsprop: rms, momentum; adadelta: accum,
