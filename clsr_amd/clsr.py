@@ -482,7 +482,7 @@ class SequentialBaseModel(BaseModel):
         synchronisation, scores never leave HBM.  None when a requested metric has no device form (host path then)."""
         from clsr_amd import device_metrics as DM
 
-        if os.environ.get("CLSR_HOST_METRICS") or not DM.supported(self.hparams, self.user_vocab_length):
+        if os.environ.get("CLSR_HOST_METRICS") or not DM.supported(self.hparams, self.user_vocab_length, num_ngs + 1):
             return None
         with self._stream_ctx():
             acc = DM.DeviceScores(self.net.device)

@@ -198,6 +198,20 @@ __device__ __forceinline__ float hm_unpack(unsigned short hi, short lo) {
   return __uint_as_float(((unsigned)hi << 16) + (unsigned)(int)lo);
 }
 // four consecutive elements (8-byte accesses of both halves; element index e: multiple of 4, both pointers 8-byte aligned)
+// One Adam element update of a master (m, v, w in place; g already clipped), the SAME bits in every `_hm` kernel that
+// inlines it: left to the compiler, `b1 * m + (1 - b1) * g` is contracted into a fused multiply-add in one kernel and not
+// in another, and from the second step on (moments no longer zero) the sweep launches and the row-list launches of one
+// table stored masters one ulp apart.  Contraction is off in here and the two fused operations are spelled out; every
+// other operation is correctly rounded, hence unique.
+__device__ __forceinline__ void hm_adam_elem(float g, float& m, float& v, float& w, float b1, float b2, float eps,
+                                             float lr_t) {
+#pragma clang fp contract(off)
+  const float gm = (1.0f - b1) * g;
+  const float gv = (1.0f - b2) * g * g;
+  m = __builtin_fmaf(b1, m, gm);
+  v = __builtin_fmaf(b2, v, gv);
+  w = w - lr_t * m / (sqrtf(v) + eps);
+}
 __device__ __forceinline__ f32x4 hm_unpack4(u16x4_t hi, i16x4_t lo) {
   f32x4 r;
 #pragma unroll

@@ -495,13 +495,13 @@ __global__ void __launch_bounds__(256) tables_adam_multi_hm_kernel(TablesArgsM a
     const long row = e / d.C;
     if (a.lazy && !d.flags[row]) continue;  // every row that got gradient is also flagged as involved
     const float g = d.grad[e] * factor;
-    const float mm = b1 * d.m[e] + (1.0f - b1) * g;
-    const float vv = b2 * d.v[e] + (1.0f - b2) * g * g;
+    float mm = d.m[e], vv = d.v[e], w = hm_unpack(hi[e], lo[e]);
+    hm_adam_elem(g, mm, vv, w, b1, b2, a.eps, lr_t);
     d.m[e] = mm;
     d.v[e] = vv;
     unsigned short h;
     short l;
-    hm_pack(hm_unpack(hi[e], lo[e]) - lr_t * mm / (sqrtf(vv) + a.eps), h, l);
+    hm_pack(w, h, l);
     hi[e] = h;
     lo[e] = l;
     d.grad[e] = 0.f;
@@ -545,10 +545,11 @@ __global__ void __launch_bounds__(256) tables_adam_multi_hm_v4_kernel(TablesArgs
       f32x4 mm, vv, ww;
 #pragma unroll
       for (int c = 0; c < 4; ++c) {
-        const float gc = g[u][c] * factor;
-        mm[c] = b1 * m[u][c] + (1.0f - b1) * gc;
-        vv[c] = b2 * v[u][c] + (1.0f - b2) * gc * gc;
-        ww[c] = w[c] - lr_t * mm[c] / (sqrtf(vv[c]) + a.eps);
+        float mc = m[u][c], vc = v[u][c], wc = w[c];
+        hm_adam_elem(g[u][c] * factor, mc, vc, wc, b1, b2, a.eps, lr_t);
+        mm[c] = mc;
+        vv[c] = vc;
+        ww[c] = wc;
       }
       st4(d.m + e, mm);
       st4(d.v + e, vv);

@@ -636,12 +636,11 @@ __global__ void __launch_bounds__(256) table_adam_rows_hm_kernel(
       f32x4 po = hm_unpack4(ph[u], pl[u]);
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
-        const float gg = g[u][k] * factor;
-        const float mm = b1 * mo[u][k] + (1.0f - b1) * gg;
-        const float vv = b2 * vo[u][k] + (1.0f - b2) * gg * gg;
-        mo[u][k] = mm;
-        vo[u][k] = vv;
-        po[k] -= lr_t * mm / (sqrtf(vv) + eps);
+        float mk = mo[u][k], vk = vo[u][k], pk = po[k];
+        hm_adam_elem(g[u][k] * factor, mk, vk, pk, b1, b2, eps, lr_t);
+        mo[u][k] = mk;
+        vo[u][k] = vk;
+        po[k] = pk;
       }
       if (ok[u]) {
         const f32x4 z = {0.f, 0.f, 0.f, 0.f};
@@ -687,13 +686,13 @@ __global__ void __launch_bounds__(256) table_adam_hm_kernel(
     const long row = e / C;
     const float g = grad_table[e] * factor;
     if (lazy && !flags[row]) continue;  // every row that got gradient is also flagged as involved
-    const float mm = b1 * m[e] + (1.0f - b1) * g;
-    const float vv = b2 * v[e] + (1.0f - b2) * g * g;
+    float mm = m[e], vv = v[e], w = hm_unpack(hi[e], lo[e]);
+    hm_adam_elem(g, mm, vv, w, b1, b2, eps, lr_t);
     m[e] = mm;
     v[e] = vv;
     unsigned short h;
     short l;
-    hm_pack(hm_unpack(hi[e], lo[e]) - lr_t * mm / (sqrtf(vv) + eps), h, l);
+    hm_pack(w, h, l);
     hi[e] = h;
     lo[e] = l;
     grad_table[e] = 0.f;

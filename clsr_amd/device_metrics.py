@@ -5,8 +5,9 @@ Mirrors ``cal_metric`` / ``cal_weighted_metric`` of the reference (deeprec_utils
 ``SequentialBaseModel.run_eval`` / ``run_weighted_eval`` call them (sequential_base_model.py:204-292): same keys,
 same 4-decimal rounding, same ``ValueError`` when an AUC is undefined.  Supported: ``auc``, ``logloss`` (all lines);
 ``mean_mrr``, ``ndcg@k``, ``hit@k``, ``group_auc`` (groups of 1 + num_ngs consecutive lines); ``wauc`` (per user).
-Anything else -- or more than 2^18 users, whose grouping is not exact on the device -- makes :func:`supported` return
-False and the caller keeps the host path (clsr_amd/deeprec_utils.py)."""
+Anything else -- more than 2^18 users, whose grouping is not exact on the device, or groups of more than
+``MAX_GROUP`` lines, which the group kernel does not take -- makes :func:`supported` return False and the caller keeps
+the host path (clsr_amd/deeprec_utils.py)."""
 import ctypes
 
 import torch
@@ -15,9 +16,11 @@ from clsr_amd import ops
 from clsr_amd.deeprec_utils import _ks
 
 _POINT = {"auc", "logloss"}
+MAX_GROUP = 4096      # clsr_eval_group_metrics: one wave per group, the group's scores and labels in LDS (csrc/metrics.hip)
 
 
-def supported(hp, n_users):
+def supported(hp, n_users, group):
+    """``group``: lines per group of the pairwise metrics (1 + num_ngs)."""
     if any(m not in _POINT for m in (hp.metrics or [])):
         return False
     ks = set()
@@ -27,6 +30,8 @@ def supported(hp, n_users):
         elif m not in ("mean_mrr", "group_auc"):
             return False
     if len(ks) > 8:
+        return False
+    if (hp.pairwise_metrics or []) and group > MAX_GROUP:
         return False
     if any(m != "wauc" for m in (getattr(hp, "weighted_metrics", None) or [])):
         return False

@@ -514,7 +514,13 @@ def losses(params, out, feed, hp):
                  relu(dLM - dSM + mg).sum(-1), relu(dSR - dLR + mg).sum(-1)]
     else:
         raise ValueError(hp.contrastive_loss)
-    contrastive = sum((cmask * t).sum() / denom for t in terms) * hp.contrastive_loss_weight
+    if float(denom) == 0.0:
+        # no history longer than contrastive_length_threshold: the reference divides 0 by 0 here and trains on NaN; the
+        # HIP step returns 0 for the term (deliberate differences) -- and so does the oracle, so that such
+        # a batch is still compared (a NaN expectation passes every `err <= bar` test vacuously)
+        contrastive = denom * 0.0
+    else:
+        contrastive = sum((cmask * t).sum() / denom for t in terms) * hp.contrastive_loss_weight
     discrepancy = -hp.discrepancy_loss_weight * ((inv["user_long"].reshape(-1) - inv["user_short"].reshape(-1)) ** 2).mean()
     total = data_loss + reg + contrastive + discrepancy
     return dict(loss=total, data_loss=data_loss, regular_loss=reg, contrastive_loss=contrastive,

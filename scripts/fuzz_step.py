@@ -3,13 +3,21 @@
 
 Random small shapes -- embedding width D (= Du = H), history length T, positives P, rows per positive G, encoder
 kind, MLP widths, losses, sequence-length patterns incl. length-1 histories and P = 1 -- one training step and one
-scoring pass each, compared with oracle/clsr_oracle.py: logits, the five loss terms, every dense gradient.
+scoring pass each, compared with oracle/clsr_oracle.py: logits, the five loss terms, every dense gradient, and the
+embedding-table side of the step: the gradient table of every embedding, the IndexedSlices clip norms, the (lazy-)Adam
+update of the tables and, under lazyadam, bit equality of every row the step does not involve.
 
     python scripts/fuzz_step.py [n_cases] [seed] [clsr,gru4rec,din,sli_rec,a2svd,dien]
+
+FUZZ_F32=1 adds, to every failing gradient, how far the float32 ORACLE is from the float64 oracle on that tensor;
+FUZZ_F32=cpu needs no GPU: the float32 oracle takes the place of the HIP step and is held to the same gradient / norm /
+update bars (a case it misses is ill-conditioned in float32, whatever the kernels do).  Both end with the worst distance
+per check and variable (STATS).
 """
 import os
 import sys
 import traceback
+import types
 
 import numpy as np
 import torch
@@ -29,18 +37,158 @@ PRECISION = os.environ.get("FUZZ_PRECISION", "fp32")
 SIB_TYPES = {"gru4rec": "GRU4Rec", "din": "DIN", "sli_rec": "sli_rec", "a2svd": "A2SVD", "dien": "DIEN"}
 
 
-def close(got, exp, rtol, atol):
+STATS = {}     # (check, variable) -> [worst err / bar, worst abs err, largest |exp|] over the cases run so far
+
+
+def close(got, exp, rtol, atol, tag=None):
     got = torch.as_tensor(got).detach().double().cpu().reshape(-1)
     exp = torch.as_tensor(exp).detach().double().cpu().reshape(-1)
     if got.shape != exp.shape:
         return "shape %s vs %s" % (tuple(got.shape), tuple(exp.shape))
     err = (got - exp).abs()
+    if tag is not None:
+        st = STATS.setdefault(tag, [0.0, 0.0, 0.0])
+        ratio = float((err / (atol + rtol * exp.abs()).clamp_min(1e-300)).max())
+        st[:] = [max(st[0], ratio), max(st[1], float(err.max())), max(st[2], float(exp.abs().max()))]
+    if not bool(torch.isfinite(got).all() and torch.isfinite(exp).all()):      # (NaN passes every `err <= bar` below)
+        return "non-finite values: %d computed, %d expected" % (int((~torch.isfinite(got)).sum()), int((~torch.isfinite(exp)).sum()))
     if float((err - (atol + rtol * exp.abs())).max()) > 0:
         return "max abs err %.3e (max |exp| %.3e)" % (float(err.max()), float(exp.abs().max()))
     return None
 
 
-def one_case(rng, idx, kind="clsr"):
+def trace(name, got, exp, rtol, atol):
+    """FUZZ_TRACE: where a tensor misses its bar -- for a table [row, column], which narrows a failure to a width."""
+    gt, ex = torch.as_tensor(got).detach().double().cpu(), torch.as_tensor(exp).detach().double().cpu()
+    badm = ~((gt - ex).abs() <= (rtol * ex.abs() + atol))
+    idx_bad = badm.nonzero()
+    print(name, tuple(ex.shape), "mismatches", int(badm.sum()), "first", idx_bad[:4].tolist(), "last", idx_bad[-2:].tolist())
+    if ex.dim() == 2 and len(idx_bad):
+        print("    rows %d..%d (%d distinct), columns %d..%d (%d distinct)" % (
+            int(idx_bad[:, 0].min()), int(idx_bad[:, 0].max()), len(idx_bad[:, 0].unique()),
+            int(idx_bad[:, 1].min()), int(idx_bad[:, 1].max()), len(idx_bad[:, 1].unique())))
+    for ij in idx_bad[:4].tolist():
+        print("   ", ij, "got", float(gt[tuple(ij)]), "exp", float(ex[tuple(ij)]))
+
+
+def table_norms(table_sumsq):
+    """Clip norm per table from the step's squared-norm slots (``captured["table_sumsq"]``): the norm of the un-summed
+    IndexedSlices values of every lookup site of the table, the layout tests/test_step_gpu.py reads."""
+    ss = torch.as_tensor(table_sumsq).double().cpu().numpy()
+    return dict(item=(ss[0] + ss[2] + ss[4]) ** 0.5, cate=(ss[1] + ss[3] + ss[5]) ** 0.5,
+                user_long=(ss[6] + ss[8]) ** 0.5, user_short=(ss[7] + ss[9]) ** 0.5)
+
+
+def table_checks(pre, tmap, got_grad, got_norm, got_new, loaded, oracle, floor, hp, raw32=None):
+    """The embedding-table side of one step against the float64 oracle, at the bars of tests/test_step_gpu.py.
+    ``got_grad``: table key -> gradient table (pre-clip, regulariser included); ``got_norm``: key -> clip norm, or None where
+    the step does not keep the reference's IndexedSlices norm (de-duplicated histories); ``got_new`` / ``loaded``: variable
+    name -> float32 table after / before the step; ``oracle``: (params, new_p, grads, raw_grads, norms) of the float64 step."""
+    params, new_p, grads, raw, norms = oracle
+    problems = []
+    if set(got_grad) != set(tmap):
+        problems.append("%sgradient tables %s, expected %s" % (pre, sorted(got_grad), sorted(tmap)))
+    for key, name in tmap.items():
+        if key not in got_grad:
+            continue
+        # ---- the gradient table (dense equivalent of the IndexedSlices)
+        scale = float(raw[name].abs().max()) + 1e-12
+        rtol, atol = 2e-3, 2e-4 * scale + floor
+        e = close(got_grad[key], raw[name], rtol, atol, ("grad", key))
+        if e:
+            problems.append("%sgrad %s: %s" % (pre, name, e))
+            if raw32 is not None:
+                problems.append("      float32 oracle vs float64 oracle: max abs err %.3e" %
+                                float((raw32[name].double() - raw[name].double()).abs().max()))
+            if os.environ.get("FUZZ_TRACE"):
+                trace(name, got_grad[key], raw[name], rtol, atol)
+        # ---- tf.clip_by_norm's norm of the IndexedSlices
+        if got_norm is not None:
+            e = close([got_norm[key]], [norms[name]], 1e-3, 1e-7, ("norm", key))
+            if e:
+                problems.append("%sclip norm %s: %s (got %.6e, oracle %.6e)" % (pre, name, e, got_norm[key], norms[name]))
+        # ---- the applied update (clip + Adam / lazy Adam)
+        new = torch.as_tensor(got_new[name]).detach().cpu()
+        before = torch.as_tensor(loaded[name]).detach().cpu()
+        g_ = grads[name].double().reshape(-1)
+        sel = g_.abs() > 100 * floor      # Adam's first step is ~lr * sign(g): skip gradients at noise level
+        if int(sel.sum()):
+            upd_got = (new.double().reshape(-1) - params[name].reshape(-1))[sel]
+            upd_exp = (new_p[name].reshape(-1) - params[name].reshape(-1))[sel]
+            e = close(upd_got, upd_exp, 5e-3, 0.02 * hp.learning_rate, ("update", key))
+            if e:
+                problems.append("%sadam update %s: %s" % (pre, name, e))
+                if os.environ.get("FUZZ_TRACE"):
+                    full = torch.zeros_like(g_)
+                    full[sel] = 1.0
+                    trace("update of " + name, (new.double() - params[name]) * full.view_as(params[name]),
+                          (new_p[name] - params[name]) * full.view_as(params[name]), 5e-3, 0.02 * hp.learning_rate)
+        # ---- lazy Adam touches involved rows only: every row the oracle leaves alone keeps its bits
+        if str(hp.optimizer) == "lazyadam":
+            V = params[name].shape[0]
+            idle = (new_p[name] == params[name]).reshape(V, -1).all(1) & (grads[name] == 0).reshape(V, -1).all(1)
+            same = (new.float().view(torch.int32) == before.float().view(torch.int32)).reshape(V, -1).all(1)
+            STATS.setdefault(("idle rows", key), [0.0, 0.0, 0.0])[2] += float(idle.sum())
+            if not bool(same[idle].all()):
+                rows = (idle & ~same).nonzero().reshape(-1)
+                problems.append("%slazyadam %s: %d of %d untouched rows changed, first %s" % (
+                    pre, name, len(rows), int(idle.sum()), rows[:6].tolist()))
+    return problems
+
+
+def f32_step(orc, extra, params32, feed, hp):
+    p32 = type(params32)((k, v.float()) for k, v in params32.items())
+    return orc.train_step(p32, orc.init_bn_state(p32), orc.init_adam(p32), 1, orc.to_torch_feed(feed, dtype=torch.float32),
+                          hp, *extra)
+
+
+def f32_case(kind, idx, dims, hp, feed, P):
+    """FUZZ_F32=cpu: the float32 ORACLE in the place of the HIP step, against the float64 oracle at the gradient, clip-norm
+    and update bars of one_case (no GPU).  What misses a bar here is ill-conditioned in float32 whatever computes it."""
+    from clsr_amd.params import SIB_TABLES, TABLES
+
+    if P == 1:
+        return []
+    if kind == "clsr":
+        orc, extra, tmap = O, (), TABLES
+        params32 = O.init_params(dims, hp, seed=idx, scale_dense=8.0)
+    else:
+        orc, extra, tmap = SO, (kind,), SIB_TABLES
+        params32 = SO.init_params(dims, hp, kind, seed=idx, scale_dense=8.0)
+    params = type(params32)((k, v.double()) for k, v in params32.items())
+    new_p, _, _, _, grads, norms, out = orc.train_step(params, orc.init_bn_state(params), orc.init_adam(params), 1,
+                                                       orc.to_torch_feed(feed, dtype=torch.float64), hp, *extra)
+    new32, _, _, _, _, norms32, out32 = f32_step(orc, extra, params32, feed, hp)
+    raw, raw32 = out["raw_grads"], out32["raw_grads"]
+    dense = [n for n in raw if n not in set(tmap.values())]
+    floor = 4e-6 * max(float(raw[n].abs().max()) for n in dense)
+    problems = []
+    for name in dense:
+        scale = float(raw[name].abs().max()) + 1e-12
+        e = close(raw32[name], raw[name], 2e-3, 2e-4 * scale + floor, ("grad", "dense"))
+        if e:
+            problems.append("float32 oracle grad %s: %s" % (name, e))
+        sel = grads[name].double().reshape(-1).abs() > 100 * floor
+        if int(sel.sum()):
+            e = close((new32[name].double().reshape(-1) - params[name].reshape(-1))[sel],
+                      (new_p[name].reshape(-1) - params[name].reshape(-1))[sel], 5e-3, 0.02 * hp.learning_rate,
+                      ("update", "dense"))
+            if e:
+                problems.append("float32 oracle adam update %s: %s" % (name, e))
+    return problems + table_checks("float32 oracle ", tmap, {k: raw32[v] for k, v in tmap.items()},
+                                   {k: norms32[v] for k, v in tmap.items()}, new32, params32,
+                                   (params, new_p, grads, raw, norms), floor, hp)
+
+
+def print_stats():
+    for tag in sorted(STATS):
+        print("    worst %-10s %-10s err / bar %.3f   max abs err %.3e   (largest |exp| %.3e)" % (tag + tuple(STATS[tag])))
+
+
+def draw_case(rng, idx, kind="clsr", pin=None):
+    """Shape, hyper-parameters and feed recipe of one random case.  ``pin``: values that replace the drawn ones -- D, Dc, T,
+    P, G, lengths or any hyper-parameter -- while the random rest (and the random stream) stays what it is."""
+    pin = dict(pin or {})
     D = int(rng.choice([8, 12, 16, 20, 24, 32, 40, 48, 52, 64, 96, 128]))
     Dc = int(rng.choice([4, 8])) if D > 8 else 4
     T = int(rng.choice([1, 2, 3, 5, 8, 10, 17, 50]))
@@ -84,6 +232,10 @@ def one_case(rng, idx, kind="clsr"):
             over["hidden_size"] = D      # alpha mixes the A2SVD feature (D wide) with the encoder feature (H wide)
         if kind in ("sli_rec", "a2svd"):
             over["attention_size"] = D   # the A2SVD query is contracted with the projected history (base_model.py:622)
+    D, Dc, T, P, G = (int(pin.pop(k, v)) for k, v in (("D", D), ("Dc", Dc), ("T", T), ("P", P), ("G", G)))
+    over["train_num_ngs"] = G - 1
+    pin_lengths = pin.pop("lengths", None)
+    over.update(pin)
     cfg = dict(T=T, Di=D - Dc, Dc=Dc, Du=D, H=over.get("hidden_size", D), Vu=50, Vi=200, Vc=12)
     desc = "case %d %s: D=%d Dc=%d T=%d P=%d G=%d %s" % (idx, kind, D, Dc, T, P, G, over)
     one_case.desc = desc
@@ -91,18 +243,36 @@ def one_case(rng, idx, kind="clsr"):
     dims = dict(Vu=cfg["Vu"], Vi=cfg["Vi"], Vc=cfg["Vc"])
     lengths = str(rng.choice(["full", "uniform", "lognormal"])) if T > 1 else "full"
     feed_seed, short = int(rng.integers(1 << 30)), rng.random() < 0.5
-    only = os.environ.get("FUZZ_ONLY")   # "6,11": run these case numbers only (the random stream stays the same)
-    if only and str(idx) not in only.split(","):
-        return desc, None
-    feed = synthetic_feed(P, T, dims["Vu"], dims["Vi"], dims["Vc"], G=G, lengths=lengths,
-                          ids="uniform", seed=feed_seed)
-    if short and T > 1:     # force some length-1 histories
+    if pin_lengths and T > 1:
+        lengths = pin_lengths
+    return types.SimpleNamespace(desc=desc, hp=hp, dims=dims, cfg=cfg, D=D, Dc=Dc, T=T, P=P, G=G, lengths=lengths,
+                                 feed_seed=feed_seed, short=short)
+
+
+def make_feed(c, P=None, seed=None):
+    """The training feed of a drawn case (``P`` / ``seed``: another batch of the same shape family)."""
+    P = c.P if P is None else P
+    feed = synthetic_feed(P, c.T, c.dims["Vu"], c.dims["Vi"], c.dims["Vc"], G=c.G, lengths=c.lengths,
+                          ids="uniform", seed=c.feed_seed if seed is None else seed)
+    if c.short and c.T > 1:     # force some length-1 histories
         k = max(1, P // 3)
-        rows = np.arange(k * G)
+        rows = np.arange(k * c.G)
         for key in ("item_history", "item_cate_history", "mask", "time_diff", "time_from_first_action",
                     "time_to_now"):
             feed[key][rows, 1:] = 0
+    return feed
+
+
+def one_case(rng, idx, kind="clsr"):
+    c = draw_case(rng, idx, kind)
+    desc, hp, dims, P = c.desc, c.hp, c.dims, c.P
+    only = os.environ.get("FUZZ_ONLY")   # "6,11": run these case numbers only (the random stream stays the same)
+    if only and str(idx) not in only.split(","):
+        return desc, None
+    feed = make_feed(c)
     problems = []
+    if os.environ.get("FUZZ_F32") == "cpu":
+        return desc, f32_case(kind, idx, dims, hp, feed, P)
     for dedup in (True, False):
         if kind == "clsr":
             orc, extra = O, ()
@@ -126,7 +296,7 @@ def one_case(rng, idx, kind="clsr"):
         if e:
             problems.append("dedup=%s eval logit: %s" % (dedup, e))
         adam = orc.init_adam(params)
-        new_p, new_bn, _, ls, grads, _, out = orc.train_step(params, bn, adam, 1, tf, hp, *extra)
+        new_p, new_bn, _, ls, grads, norms, out = orc.train_step(params, bn, adam, 1, tf, hp, *extra)
         if os.environ.get("FUZZ_WARM"):  # diagnosis: allocate every workspace in a throw-away pass first (a deviation
             net.train_step(net.upload(feed, True), apply=False)   # that disappears is a first-step allocation race)
             torch.cuda.synchronize()
@@ -196,34 +366,35 @@ def one_case(rng, idx, kind="clsr"):
         raw = out["raw_grads"]
         raw32 = None
         if os.environ.get("FUZZ_F32"):   # conditioning check: how far is a float32 run of the ORACLE from its float64 run?
-            p32 = type(params32)((k, v.float()) for k, v in params32.items())
-            raw32 = orc.train_step(p32, orc.init_bn_state(p32), orc.init_adam(p32), 1,
-                                   orc.to_torch_feed(feed, dtype=torch.float32), hp, *extra)[6]["raw_grads"]
+            raw32 = f32_step(orc, extra, params32, feed, hp)[6]["raw_grads"]
         floor = 4e-6 * max(float(raw[n].abs().max()) for n in net.dense_names)
         for name in net.dense_names:
             scale = float(raw[name].abs().max()) + 1e-12
-            e = close(net.captured["dense"][name], raw[name], 2e-3, 2e-4 * scale + floor)
+            e = close(net.captured["dense"][name], raw[name], 2e-3, 2e-4 * scale + floor, ("grad", "dense"))
             if e:
                 problems.append("dedup=%s grad %s: %s" % (dedup, name, e))
                 if raw32 is not None:
                     problems.append("      float32 oracle vs float64 oracle: max abs err %.3e" %
                                     float((raw32[name].double() - raw[name].double()).abs().max()))
                 if os.environ.get("FUZZ_TRACE"):
-                    gt, ex = net.captured["dense"][name].double().cpu(), raw[name].double().cpu()
-                    badm = (gt - ex).abs() > (2e-3 * ex.abs() + 2e-4 * scale + floor)
-                    idx_bad = badm.nonzero()
-                    print(name, tuple(ex.shape), "mismatches", int(badm.sum()), "first", idx_bad[:4].tolist(), "last",
-                          idx_bad[-2:].tolist())
-                    for ij in idx_bad[:4].tolist():
-                        print("   ", ij, "got", float(gt[tuple(ij)]), "exp", float(ex[tuple(ij)]))
-        # the applied update (clip + Adam, dense variables) and the batch-norm moving statistics
+                    trace(name, net.captured["dense"][name], raw[name], 2e-3, 2e-4 * scale + floor)
+        # the embedding tables: gradient tables, IndexedSlices clip norms (replicated computation == the reference's
+        # semantics; de-duplicated histories sum a group's slices before the norm), (lazy-)Adam update
         sd = net.state_dict()
+        problems += table_checks("dedup=%s " % dedup, net._table_map(), net.captured["tables"],
+                                 None if dedup else table_norms(net.captured["table_sumsq"]), sd, params32,
+                                 (params, new_p, grads, raw, norms), floor, hp, raw32)
+        for name in net._unused_tables():     # created for checkpoint compatibility, never trained: an exactly-zero update
+            if not torch.equal(sd[name].view(torch.int32), params32[name].view(torch.int32)):
+                problems.append("dedup=%s unused table %s changed" % (dedup, name))
+        # the applied update (clip + Adam, dense variables) and the batch-norm moving statistics
         for name in net.dense_names:
             g_ = grads[name].double().reshape(-1)
             sel = g_.abs() > 100 * floor      # Adam's first step is ~lr * sign(g): skip gradients at noise level
             if int(sel.sum()):
                 e = close((sd[name].double().cpu().reshape(-1) - params[name].reshape(-1))[sel],
-                          (new_p[name].reshape(-1) - params[name].reshape(-1))[sel], 5e-3, 0.02 * hp.learning_rate)
+                          (new_p[name].reshape(-1) - params[name].reshape(-1))[sel], 5e-3, 0.02 * hp.learning_rate,
+                          ("update", "dense"))
                 if e:
                     problems.append("dedup=%s adam update %s: %s" % (dedup, name, e))
         for k, v in new_bn.items():
@@ -259,6 +430,7 @@ def main():
         else:
             print("ok   " + desc.split(" {")[0])
     print("%d of %d cases with problems" % (bad, n))
+    print_stats()
 
 
 if __name__ == "__main__":

@@ -9,6 +9,7 @@ parts in 10^7 of itself, and the stored master adds one fp32 rounding of w (6e-8
 import copy
 import os
 import pickle
+import sys
 
 import numpy as np
 import pytest
@@ -16,12 +17,13 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "scripts"))
+
 from clsr_amd import ops  # noqa: E402
 from clsr_amd.ops import call  # noqa: E402
-
-DEV = "cuda"
-BF = torch.bfloat16
-I16 = torch.int16
+# (shared with the random-shape differential of the table modes, tests/test_fuzz_tables_gpu.py)
+from fuzz_tables import BF, DEV, I16, bits16, merge, split  # noqa: E402
+from fuzz_tables import master_bar as _master_bar  # noqa: E402
 
 
 # ------------------------------------------------------------------------------------------- the encoding, restated
@@ -40,40 +42,11 @@ def np_merge(hi, lo):
     return b.astype(np.uint32).view(np.float32)
 
 
-def split(x):
-    hi = torch.empty(x.shape, dtype=BF, device=DEV)
-    lo = torch.empty(x.shape, dtype=I16, device=DEV)
-    call("clsr_table_split_hm", x.contiguous(), hi, lo, x.numel())
-    return hi, lo
-
-
-def merge(hi, lo):
-    out = torch.empty(hi.shape, dtype=torch.float32, device=DEV)
-    call("clsr_table_merge_hm", hi, lo, out, hi.numel())
-    return out
-
-
-def bits16(t):
-    return t.view(I16)
-
-
 def _close(got, exp, rtol, atol, name):
     got, exp = got.double().cpu().reshape(-1), exp.double().cpu().reshape(-1)
     err = (got - exp).abs()
     excess = float((err - (atol + rtol * exp.abs())).max())
     assert excess <= 0, "%s: max abs err %.3e (max |exp| %.3e)" % (name, float(err.max()), float(exp.abs().max()))
-
-
-def _master_bar(got, ref, before, name):
-    """|got - ref| <= 1e-6 |ref| + 1e-6 U, U = the largest |ref - before| (prints the measured maximum first)."""
-    got, ref, before = got.double().cpu(), ref.double().cpu(), before.double().cpu()
-    U = float((ref - before).abs().max())
-    err = (got - ref).abs()
-    bar = 1e-6 * ref.abs() + 1e-6 * U
-    print("%s: max |master - fp32| = %.3e, U = %.3e, worst err / bar = %.3f"
-          % (name, float(err.max()), U, float((err / bar.clamp_min(1e-300)).max())))
-    assert bool((err <= bar).all()), "%s: max err %.3e against U %.3e" % (name, float(err.max()), U)
-    return U
 
 
 def test_split_and_merge_against_the_restatement():

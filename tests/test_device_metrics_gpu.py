@@ -117,6 +117,171 @@ def test_device_metrics_equal_the_host_metrics(n_groups, group, n_users, ties):
         assert _same(got[k], exp[k], raw, k), (k, got[k], exp[k], raw[k])
 
 
+def _pair_counts(pos, neg):
+    """(#{p > n}, #{p == n}) over all pairs, as Python integers (float32 scores compared exactly)."""
+    pos, neg = np.sort(np.asarray(pos, dtype=np.float32)), np.sort(np.asarray(neg, dtype=np.float32))
+    below = np.searchsorted(neg, pos, side="left").astype(np.int64)        # negatives strictly below each positive
+    upto = np.searchsorted(neg, pos, side="right").astype(np.int64)
+    return int(below.sum()), int((upto - below).sum())
+
+
+@pytest.fixture(scope="module")
+def many_positives():
+    """Lines of six users with exactly 255 / 256 / 257 / 512 / 513 / 700 positives (the user kernel takes a user's
+    positives UA_PT = 256 at a time: one tile exactly, one short of it, one over, two tiles, ...) and 300-900 negatives each,
+    shuffled among the lines of 300 small users; scores rounded to 2 decimals: heavy ties."""
+    rng = np.random.default_rng(256)
+    ids = rng.choice(1 << 18, 306, replace=False)
+    users, labels = [], []
+    for u, npos in zip(ids[:6], (255, 256, 257, 512, 513, 700)):
+        nneg = int(rng.integers(300, 901))
+        users += [u] * (npos + nneg)
+        labels += [1.0] * npos + [0.0] * nneg
+    for u in ids[6:]:
+        npos, nneg = int(rng.integers(1, 5)), int(rng.integers(1, 9))
+        users += [u] * (npos + nneg)
+        labels += [1.0] * npos + [0.0] * nneg
+    order = rng.permutation(len(users))
+    users, labels = np.asarray(users, dtype=np.int64)[order], np.asarray(labels)[order]
+    preds = np.round(rng.random(len(users)), 2).astype(np.float32)
+    assert int(labels.sum()) > 2048       # (the global AUC kernel tiles the positives by AUC_PT = 2048)
+    return preds, labels, users
+
+
+def test_wauc_with_more_positives_per_user_than_one_tile(many_positives):
+    """wauc against integer pair counting, unrounded.  The kernel counts pairs in integers as well; its only inexact step
+    is the 2^-60 fixed-point rounding of ONE partial sum per wave (fx_add), at most 16 384 waves: below 2^-46 = 1.4e-14,
+    and the float64 sums of ~300 terms <= 1 on either side add a few 1e-16 each -- hence 1e-12 absolute."""
+    preds, labels, users = many_positives
+    N = len(preds)
+    exp, per_user_pos = 0.0, []
+    for u in np.unique(users):
+        m = users == u
+        pos, neg = preds[m & (labels == 1)], preds[m & (labels != 1)]
+        gt, eq = _pair_counts(pos, neg)
+        exp += (int(m.sum()) / N) * (gt + 0.5 * eq) / (len(pos) * len(neg))
+        per_user_pos.append(len(pos))
+    assert sorted(per_user_pos)[-6:] == [255, 256, 257, 512, 513, 700]
+    raw = {}
+    hp = _hp(metrics=[], pairwise_metrics=[], weighted_metrics=["wauc"])
+    got = _device(preds, labels, users, hp, 1, chunks=3, raw=raw)
+    print("wauc: device %.17g, pair counting %.17g, diff %.3e" % (raw["wauc"], exp, raw["wauc"] - exp))
+    assert abs(raw["wauc"] - exp) <= 1e-12
+    assert got["wauc"] == round(raw["wauc"], 4)
+    host = cal_weighted_metric(users, preds, labels, ["wauc"])
+    assert _same(got["wauc"], host["wauc"], raw, "wauc")
+
+
+def test_auc_with_more_positives_than_one_tile(many_positives):
+    preds, labels, users = many_positives
+    gt, eq = _pair_counts(preds[labels == 1], preds[labels != 1])
+    exp = (gt + 0.5 * eq) / (float(int((labels == 1).sum())) * float(int((labels != 1).sum())))
+    raw = {}
+    _device(preds, labels, users, _hp(metrics=["auc"], pairwise_metrics=[], weighted_metrics=[]), 1, chunks=3, raw=raw)
+    assert raw["auc"] == exp, (raw["auc"], exp)       # integer counts on both sides, the same float64 expression
+
+
+WIDE_KS = [1, 2, 3, 5, 10, 64, 100, 5000]      # GM_MAXK = 8 distinct k, three of them above some (or every) G
+
+
+def _wide_groups(G, n_groups):
+    """Tie-free float32 scores; 1-5 positives per group, from the second on one sits 64 lines behind the first (the same
+    lane of the wave that owns the group); every other group has its positives moved among the 8 best scores."""
+    rng = np.random.default_rng(G)
+    N = n_groups * G
+    preds = ((rng.permutation(N) + 0.5) / N).astype(np.float32).reshape(n_groups, G)
+    assert np.unique(preds).size == N
+    labels = np.zeros((n_groups, G))
+    for g in range(n_groups):
+        npos = 1 + g % 5
+        first = int(rng.integers(0, G - 64)) if G > 64 else int(rng.integers(0, G))
+        at = [first] + ([first + 64] if npos > 1 and G > 64 else [])
+        rest = [i for i in rng.permutation(G) if i not in at]
+        at += [int(i) for i in rest[:npos - len(at)]]
+        labels[g, at] = 1.0
+        if g % 2 == 0:
+            best = np.argsort(preds[g])[::-1][:8]
+            for i, j in zip(at, rng.permutation(best)[:npos]):
+                preds[g, [i, j]] = preds[g, [j, i]]
+    return preds, labels
+
+
+def _group_restatement(preds, labels, ks):
+    """mean_mrr / ndcg@k / hit@k / group_auc in float64 from the ranks (tie-free scores), deeprec_utils.py:554-620."""
+    out = {k: 0.0 for k in ["mean_mrr", "group_auc"] + ["ndcg@%d" % k for k in ks] + ["hit@%d" % k for k in ks]}
+    for p, l in zip(preds, labels):
+        pos = np.flatnonzero(l == 1)
+        ranks = np.array([1 + int((p > p[i]).sum()) for i in pos], dtype=np.float64)
+        out["mean_mrr"] += float((1.0 / ranks).sum()) / len(pos)
+        gt, eq = _pair_counts(p[l == 1], p[l != 1])
+        out["group_auc"] += (gt + 0.5 * eq) / (len(pos) * (len(p) - len(pos)))
+        for k in ks:
+            dcg = float((1.0 / np.log2(ranks[ranks <= k] + 1.0)).sum())
+            ideal = float((1.0 / np.log2(np.arange(1, min(k, len(pos), len(p)) + 1) + 1.0)).sum())
+            out["ndcg@%d" % k] += dcg / ideal
+            out["hit@%d" % k] += 1.0 if (ranks <= k).any() else 0.0
+    return {k: v / len(preds) for k, v in out.items()}
+
+
+@pytest.mark.parametrize("G,n_groups", [(64, 40), (65, 40), (128, 40), (1000, 40), (2048, 40), (4096, 8)])
+def test_group_metrics_on_wide_groups(G, n_groups):
+    """Groups up to the kernel's bound (G = 4096: 128 KB of dynamic LDS per workgroup), k above G, the maximum of 8 distinct
+    k, several positives on one lane.  Unrounded values: every wave adds ONE partial sum (here: one group) rounded to
+    2^-30 fixed point, so a mean over the groups is within 2^-31 of the float64 restatement (+ float64 noise)."""
+    preds, labels = _wide_groups(G, n_groups)
+    hp = _hp(metrics=[], weighted_metrics=[],
+             pairwise_metrics=["mean_mrr", "ndcg@1;2;5;64;100;5000", "hit@1;3;10", "group_auc"])
+    assert DM.supported(hp, 1, G)
+    raw = {}
+    got = _device(preds.reshape(-1), labels.reshape(-1), np.zeros(preds.size, dtype=np.int64), hp, G, raw=raw)
+    exp = cal_metric(labels, preds, hp.pairwise_metrics)
+    assert set(got) == set(exp) and len(exp) == 2 + 6 + 3
+    for k in exp:
+        assert _same(got[k], exp[k], raw, k), (k, got[k], exp[k], raw[k])
+    ref = _group_restatement(preds, labels, WIDE_KS)
+    for k in exp:
+        assert abs(raw[k] - ref[k]) <= 2.0 ** -31 + 1e-12, (k, raw[k], ref[k])
+    assert 0.0 < raw["hit@1"] < raw["hit@10"] <= 1.0 and raw["ndcg@5000"] < 1.0      # (the case is not degenerate)
+
+
+def test_groups_above_the_kernel_bound_keep_the_host_path(golden_dir, golden_hparams, tmp_path):
+    """``supported`` looks at the group size: above MAX_GROUP lines per group the model evaluates on the host instead of
+    raising out of the group kernel."""
+    from clsr_amd.clsr import CLSRModel
+    from clsr_amd.sequential_iterator import SASequentialIterator
+
+    hp = _hp()
+    assert DM.MAX_GROUP == 4096
+    assert DM.supported(hp, 100, DM.MAX_GROUP) and not DM.supported(hp, 100, DM.MAX_GROUP + 1)
+    assert DM.supported(_hp(pairwise_metrics=[]), 100, DM.MAX_GROUP + 1)      # (no group kernel without group metrics)
+    # one group of 4097 lines: a positive line of the committed validation file, then 4096 negative ones of that file
+    lines = open(os.path.join(golden_dir, "data", "valid_data")).read().splitlines()
+    pos = [ln for ln in lines if ln.startswith("1\t")]
+    neg = [ln for ln in lines if ln.startswith("0\t")]
+    G = DM.MAX_GROUP + 1
+    path = str(tmp_path / "wide_group")
+    with open(path, "w") as f:
+        user = pos[0].split("\t")[1]      # (all lines under one user: wauc needs both classes for every user)
+        rows = [pos[0]] + ["\t".join([ln.split("\t")[0], user] + ln.split("\t")[2:]) for ln in (neg * (G // len(neg) + 1))[:G - 1]]
+        f.write("\n".join(rows) + "\n")
+    model = CLSRModel(golden_hparams, SASequentialIterator, seed=2)
+    assert model._device_eval(path, G - 1, False) is None and model._device_eval(path, G - 1, True) is None
+    got = model.run_eval(path, num_ngs=G - 1)
+    users, preds, labels = [], [], []
+    for batch in model.iterator.load_data_from_file(path, min_seq_length=model.min_seq_length, batch_num_ngs=0):
+        if batch:
+            u, p, l = model.eval_with_user(model.sess, batch)
+            users.extend(np.reshape(u, -1)), preds.extend(np.reshape(p, -1)), labels.extend(np.reshape(l, -1))
+    assert len(preds) == G
+    exp = cal_metric(labels, preds, golden_hparams.metrics)
+    exp.update(cal_metric(np.reshape(labels, (-1, G)), np.reshape(preds, (-1, G)), golden_hparams.pairwise_metrics))
+    assert got == exp and "mean_mrr" in got
+    exp.update(cal_weighted_metric(users, preds, labels, golden_hparams.weighted_metrics))
+    assert model.run_weighted_eval(path, num_ngs=G - 1) == exp
+    # groups the kernel takes go through the device metrics
+    assert model._device_eval(os.path.join(golden_dir, "data", "valid_data"), 4, False) is not None
+
+
 def test_undefined_auc_raises_like_the_host_path():
     hp = _hp(pairwise_metrics=[], weighted_metrics=[])
     with pytest.raises(ValueError):
