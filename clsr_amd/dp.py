@@ -17,11 +17,12 @@ Tables whose touched rows are few compared with the vocabulary are exchanged SPA
 list, the listed rows are packed, (count, ids, rows) are all-gathered, and every rank adds the lists of
 all ranks in rank order into its cleared rows -- bit-identical sums on every replica, and the traffic is
 O(touched rows) instead of O(vocabulary).  ``sparse_tables="auto"`` picks per table and per batch shape
-(sparse when the table has at least 64 MB and  4 * rows_bound * world < vocabulary: a dense table rides in the ONE
-flat all-reduce, a sparse one
-costs three collectives of its own, so it has to save real traffic);  "all" / "none" force one path.
+(sparse when the table has at least 64 MB and 4 * rows_bound * world < vocabulary: a dense table rides in
+the ONE flat all-reduce, a sparse one costs three collectives of its own, so it has to save real traffic);
+"all" / "none" force one path, and a collection of table names (tuple, list, set, frozenset) sends exactly
+those tables through the sparse exchange.  The attribute may be reassigned between steps.
 
-and every rank applies the identical clip + Adam update, so replicas never diverge.  Loss
+After the exchange every rank applies the identical clip + Adam update, so replicas never diverge.  Loss
 normalisers are global: the softmax data loss is scaled by 1/(P * world) and the contrastive
 denominator (rows longer than the threshold) is summed over ranks before the step.
 
@@ -171,8 +172,7 @@ class DataParallel(object):
 
     def __init__(self, net, dist, sync_bn=True, group=None, sparse_tables="auto", overlap=True, sparse_mode="allgather",
                  p2p_stats=True):
-        if sparse_tables not in ("auto", "all", "none"):
-            raise ValueError("sparse_tables must be 'auto', 'all' or 'none'")
+        self._check_sparse_tables(sparse_tables, net.tables)
         if sparse_mode not in ("allgather", "owner"):
             raise ValueError("sparse_mode must be 'allgather' or 'owner'")
         self.sparse_mode = sparse_mode
@@ -269,6 +269,9 @@ class DataParallel(object):
         tensors += list(net.tables.values()) + list(net.tab_m.values()) + list(net.tab_v.values())
         # (table_master: the residual halves of the fp32 masters; as bytes -- not every backend broadcasts int16)
         tensors += [t.view(torch.uint8) for t in getattr(net, "tab_lo", {}).values()]     # (tests/test_dp_cpu.py drives this with a stub net)
+        # (variables of the reference graph that no step reads or trains are part of every checkpoint all the same)
+        if hasattr(net, "_unused_tables"):
+            tensors += [net.P[n] for n in net._unused_tables() if n in net.P]
         tensors.append(net.bn_moving)
         tensors = [t for t in tensors if t is not None]     # (optimisers with fewer than two slots allocate fewer)
         for t in tensors:
@@ -297,7 +300,22 @@ class DataParallel(object):
         self.dist.all_reduce(f["denom"], op=self.dist.ReduceOp.SUM, group=self.group)
         return f
 
+    @staticmethod
+    def _check_sparse_tables(value, tables):
+        """``sparse_tables``: "auto" | "all" | "none" | a collection of table names (exactly those go sparse)."""
+        if isinstance(value, str):
+            if value not in ("auto", "all", "none"):
+                raise ValueError("sparse_tables must be 'auto', 'all', 'none' or a collection of table names")
+        elif isinstance(value, (tuple, list, set, frozenset)):
+            unknown = sorted(str(n) for n in value if n not in tables)
+            if unknown:
+                raise ValueError("sparse_tables names unknown tables %s (known: %s)" % (unknown, sorted(tables)))
+        else:
+            raise ValueError("sparse_tables must be 'auto', 'all', 'none' or a collection of table names")
+
     def _is_sparse(self, name):
+        if not isinstance(self.sparse_tables, str):
+            return name in self.sparse_tables
         if self.sparse_tables != "auto":
             return self.sparse_tables == "all"
         V, C = self.net.tables[name].shape
@@ -311,6 +329,7 @@ class DataParallel(object):
     def flags_ready(self, stream):
         net = self.net
         self._done.add("flags")
+        self._check_sparse_tables(self.sparse_tables, net.tables)     # (the attribute may have been reassigned since the last step)
         names = list(net.tab_grad)
         sparse = [n for n in names if self._is_sparse(n)]
         self.last_sparse = sparse
@@ -483,8 +502,12 @@ class DataParallel(object):
                      flags, stream=s)
 
     # ---- the phases of a step
-    def _backward(self, f):
+    def _begin_step(self):
+        """Nothing of this step has been exchanged yet."""
         self._works, self._done = [], set()
+
+    def _backward(self, f):
+        self._begin_step()
         self.net.train_step(f, apply=False)
 
     def close(self):
@@ -540,19 +563,24 @@ class DataParallel(object):
         bn_done = False
         if (self.coalesce and flat is not None and len(runs) == 1 and runs[0][1] == 0 and "dense" not in self._done
                 and not any(k in self._done for k in runs[0][0]) and net.dense_grad.data_ptr() == flat.data_ptr()):
-            # every table is dense (BASELINE configs[1]-[3]): [dense gradients | gradient tables (| moving statistics of a
-            # per-rank batch-norm)] are ONE range of the flat gradient buffer and travel in ONE collective -- all of them are
+            # the dense tables at the FRONT of tab_grad_flat (every table: BASELINE configs[1]-[3]): [dense gradients | these
+            # gradient tables] are ONE range of the flat gradient buffer and travel in ONE collective -- all of them are
             # issued here, behind the backward pass, whatever their order: every collective costs a launch and the ring's
-            # latency whatever its size (world 1, CLSR_FORCE_DP: three stream hand-overs fewer at the end of the step)
+            # latency whatever its size (world 1, CLSR_FORCE_DP: three stream hand-overs fewer at the end of the step).
+            # The moving statistics of a per-rank batch-norm lie BEHIND the last table: the range runs on into them only
+            # when this run reaches the last table.  A sparse table behind it has been merged by its row exchange already
+            # (a second sum would double it, and a dense all-reduce of it is what the sparse route exists to avoid): then
+            # the range ends with the run and the moving statistics travel on their own below.
             names, g0, n = runs[0]
             t0 = (net.tab_grad_flat.data_ptr() - flat.data_ptr()) // flat.element_size()
-            end = flat.numel() if not self.sync_bn else t0 + g0 + n
+            to_end = not self.sync_bn and names[-1] == list(net.tab_grad)[-1]
+            end = flat.numel() if to_end else t0 + g0 + n
             ds = self._dense_stream if "dense-final" in self._done else None
             if ds is not None and stream is not None and ds is not stream:
                 stream.wait_stream(ds)                  # (the dense gradients became final on the weight-gradient stream)
             self._done.update(names)
             self._done.add("dense")
-            bn_done = not self.sync_bn
+            bn_done = to_end
             self._allreduce(flat[:end], dist.ReduceOp.SUM, stream, "dense+tables:" + "+".join(names))
         for names, g0, n in runs:
             if not all(k in self._done for k in names):     # (only a second _finish of the same step finds them done)
@@ -625,7 +653,8 @@ class DataParallel(object):
 
         def run():
             self._abort_check()
-            ops.graph_launch(g1)
+            self._begin_step()      # (a replay runs no ``_backward``: without this, every replay after the first found the
+            ops.graph_launch(g1)    #  pieces of the capture's step "done" and exchanged the 24 doubles only)
             self._exchange()
             ops.graph_launch(g2)
             self._abort_poll()

@@ -481,6 +481,22 @@ def forward(params, bn_state, feed, hp, training, new_bn=None, sites=None):
 
 
 # ----------------------------------------------------------------------------- losses
+def _regular_loss(params, inv, hp, zero):
+    """L2 / L1 of the involved embedding rows (``inv``: table key -> gathered rows) and of every dense variable."""
+    l2 = lambda t: (t ** 2).sum() / 2
+    reg = zero
+    for k in ("item", "cate", "user_long", "user_short"):
+        reg = reg + hp.embed_l2 * l2(inv[k]) + hp.embed_l1 * inv[k].abs().sum()
+    for name, p in params.items():
+        if not name.startswith(EMB):
+            reg = reg + hp.layer_l2 * l2(p) + hp.layer_l1 * p.abs().sum()
+    return reg
+
+
+def _discrepancy_loss(inv, hp):
+    return -hp.discrepancy_loss_weight * ((inv["user_long"].reshape(-1) - inv["user_short"].reshape(-1)) ** 2).mean()
+
+
 def losses(params, out, feed, hp):
     """data + regular + contrastive + discrepancy (clsr.py:22-82, base_model.py:118-159,215-247)."""
     group = hp.train_num_ngs + 1
@@ -490,14 +506,8 @@ def losses(params, out, feed, hp):
     pos = torch.where(labels == 1, sm, torch.ones_like(sm))
     data_loss = -group * torch.log(pos).mean()
 
-    l2 = lambda t: (t ** 2).sum() / 2
-    reg = out["logit"].new_zeros(())
     inv = out["involved"]
-    for k in ("item", "cate", "user_long", "user_short"):
-        reg = reg + hp.embed_l2 * l2(inv[k]) + hp.embed_l1 * inv[k].abs().sum()
-    for name, p in params.items():
-        if not name.startswith(EMB):
-            reg = reg + hp.layer_l2 * l2(p) + hp.layer_l1 * p.abs().sum()
+    reg = _regular_loss(params, inv, hp, out["logit"].new_zeros(()))
 
     cmask = (out["seq_len"] > hp.contrastive_length_threshold).to(out["logit"].dtype)
     L, S, M, R = out["att_fea_long"], out["att_fea_short"], out["hist_mean"], out["hist_recent"]
@@ -521,7 +531,7 @@ def losses(params, out, feed, hp):
         contrastive = denom * 0.0
     else:
         contrastive = sum((cmask * t).sum() / denom for t in terms) * hp.contrastive_loss_weight
-    discrepancy = -hp.discrepancy_loss_weight * ((inv["user_long"].reshape(-1) - inv["user_short"].reshape(-1)) ** 2).mean()
+    discrepancy = _discrepancy_loss(inv, hp)
     total = data_loss + reg + contrastive + discrepancy
     return dict(loss=total, data_loss=data_loss, regular_loss=reg, contrastive_loss=contrastive,
                 discrepancy_loss=discrepancy)
@@ -573,6 +583,49 @@ def gradients(params, bn_state, feed, hp):
         grads[name] = gr.detach()
     out["raw_grads"] = raw
     return {k: v.detach() for k, v in ls.items()}, grads, norms, new_bn, out
+
+
+def sharded_gradients(params, bn_state, feeds, hp):
+    """Losses / gradients / moving statistics of ONE data-parallel step with per-rank batch-norm (clsr_amd/dp.py,
+    ``sync_bn=False``) over the equal-sized shards ``feeds`` of a global batch, by linearity:
+      * every shard runs the forward pass on its own rows with its OWN batch statistics;
+      * data loss: the mean of the shard means (each rank scales by 1 / (P_shard * world));
+      * contrastive terms: every shard's sums over the GLOBAL denominator (rows longer than the threshold, all shards),
+        i.e. the shard's own term weighted by denom_shard / denom_global;
+      * regularisers and the discrepancy term: counted ONCE, over the union of the rows the shards involve (the step
+        computes them after the exchange, from the merged byte maps) and every dense variable;
+      * moving statistics: the average of the shards' updates.
+    Returns (loss dict, raw gradients per variable -- pre-clip, dense-equivalent for the tables --, moving statistics)."""
+    leaf = OrderedDict((k, v.detach().clone().requires_grad_(not k.endswith("/user_embedding")))
+                       for k, v in params.items())
+    world = len(feeds)
+    outs, bns, shard_ls = [], [], []
+    for feed in feeds:
+        new_bn = OrderedDict()
+        out = forward(leaf, bn_state, feed, hp, True, new_bn)
+        outs.append(out)
+        bns.append(new_bn)
+        shard_ls.append(losses(leaf, out, feed, hp))
+    thr = hp.contrastive_length_threshold
+    denoms = [float((out["seq_len"] > thr).sum()) for out in outs]
+    data_loss = sum(ls["data_loss"] for ls in shard_ls) / world
+    contrastive = data_loss * 0.0
+    if sum(denoms) > 0:
+        contrastive = sum(ls["contrastive_loss"] * (d / sum(denoms)) for ls, d in zip(shard_ls, denoms))
+    cat = lambda *keys: _unique(torch.cat([f[k].reshape(-1) for f in feeds for k in keys]))
+    users = cat("users")
+    inv = dict(item=leaf[TABLES["item"]][cat("item_history", "items")],
+               cate=leaf[TABLES["cate"]][cat("item_cate_history", "cates")],
+               user_long=leaf[TABLES["user_long"]][users], user_short=leaf[TABLES["user_short"]][users])
+    reg = _regular_loss(leaf, inv, hp, data_loss * 0.0)
+    discrepancy = _discrepancy_loss(inv, hp)
+    total = data_loss + reg + contrastive + discrepancy
+    total.backward()
+    raw = OrderedDict((k, (p.grad if p.grad is not None else torch.zeros_like(p)).detach().clone())
+                      for k, p in leaf.items() if not k.endswith("/user_embedding"))
+    moving = OrderedDict((k, sum(b[k] for b in bns).detach() / world) for k in bns[0])
+    ls = dict(loss=total, data_loss=data_loss, regular_loss=reg, contrastive_loss=contrastive, discrepancy_loss=discrepancy)
+    return {k: v.detach() for k, v in ls.items()}, raw, moving
 
 
 def init_adam(params):

@@ -170,7 +170,8 @@ class _StubNet(object):
 
     def train_step(self, f, apply=True):
         for name, args in self.script:             # the hooks a real step would fire, in the scripted order
-            getattr(self.dp_hooks, name)(None, *args)
+            if self.dp_hooks is not None:          # (overlap=False: the net reports nothing, like CLSRNet._dp_hook)
+                getattr(self.dp_hooks, name)(None, *args)
 
     def _apply_updates(self):
         self.updated += 1
@@ -272,3 +273,169 @@ def test_overlapped_exchange_bookkeeping_every_piece_exactly_once_and_waited_for
     dp.train_step({})
     assert any(e[0] == "all_reduce" and e[1] == net.bn_moving.data_ptr() for e in d.log)
     assert torch.allclose(net.bn_moving, torch.ones(8))
+
+
+class _ActingDist(object):
+    """World of two on paper whose collectives ACT: SUM doubles the tensor in place (what a peer holding the same values
+    would add), MAX is the identity; broadcast and wait() do nothing."""
+
+    class ReduceOp(object):
+        SUM, MAX = "sum", "max"
+
+    class _Work(object):
+        def wait(self):
+            pass
+
+    def get_world_size(self, group=None):
+        return 2
+
+    def get_rank(self, group=None):
+        return 0
+
+    def broadcast(self, t, src=0, group=None):
+        pass
+
+    def all_reduce(self, t, op=None, group=None, async_op=False):
+        if op == self.ReduceOp.SUM:
+            t.mul_(2)
+        return self._Work() if async_op else None
+
+
+_HOOK_SCRIPTS = [
+    [("flags_ready", ()), ("dense_ready", ()), ("table_ready", ("cate",)), ("table_ready", ("user_long",)),
+     ("table_ready", ("user_short",)), ("table_ready", ("item",))],
+    [("dense_ready", ()), ("table_ready", ("cate",))],
+    [],
+    [("table_ready", ("item",)), ("table_ready", ("item",))],
+]
+
+
+def _exactly_once_failures():
+    """Every (sparse subset, sync_bn, coalesce, overlap, hook script) whose step does NOT reduce every element of the
+    gradient state exactly once -> [(sorted sparse names, sync_bn, coalesce, overlap, script index, what)]."""
+    import itertools
+
+    from clsr_amd.dp import DataParallel
+
+    tables = list(_StubNet().tab_shape)
+    bad = []
+    for k in range(len(tables) + 1):
+        for sparse in itertools.combinations(tables, k):
+            for sync_bn, coalesce, overlap, si in itertools.product((True, False), (True, False), (True, False),
+                                                                    range(len(_HOOK_SCRIPTS))):
+                net = _StubNet()
+                dp = DataParallel(net, _ActingDist(), sync_bn=sync_bn, sparse_tables=frozenset(sparse), overlap=overlap)
+                dp.coalesce = coalesce
+                exchanged = []
+
+                def rows(name, net=net, exchanged=exchanged):      # the sparse route of one table: merged on every replica
+                    net.tab_grad[name].mul_(2)
+                    exchanged.append(name)
+
+                dp._compact_local = lambda name: None
+                dp._exchange_rows = rows
+                net.script = _HOOK_SCRIPTS[si]
+                net.grad_flat.copy_(torch.arange(net.grad_flat.numel(), dtype=torch.float32) + 1)    # (bn_moving included)
+                net.stats24.copy_(torch.arange(24, dtype=torch.float64) + 3)
+                g0, s0, bn0 = net.grad_flat.clone(), net.stats24.clone(), net.bn_moving.clone()
+                dp.train_step({})
+                n_d, n_t = net.dense_grad.numel(), net.tab_grad_flat.numel()
+                what = []
+                if not torch.equal(net.dense_grad, 2 * g0[:n_d]):
+                    what.append("dense_grad")
+                if not torch.equal(net.tab_grad_flat, 2 * g0[n_d:n_d + n_t]):
+                    what.append("tab_grad_flat")
+                if not torch.equal(net.stats24, 2 * s0):
+                    what.append("stats24")
+                if not torch.equal(net.bn_moving, bn0):      # sync BN: never touched | per-rank BN: summed, then * 1/world
+                    what.append("bn_moving")
+                if sorted(exchanged) != sorted(sparse):
+                    what.append("row exchanges %r" % (exchanged,))
+                if net.updated != 1:
+                    what.append("updated %d times" % net.updated)
+                if what:
+                    bad.append((sorted(sparse), sync_bn, coalesce, overlap, si, what))
+    return bad
+
+
+def test_every_routing_reduces_every_element_exactly_once():
+    """All 16 sparse / dense routings of the four tables x sync_bn x coalesce x overlap x the hook scripts of the
+    bookkeeping test, with collectives that act: afterwards every dense gradient, every gradient-table element and the 24
+    doubles hold exactly twice their start value, the moving statistics are back at their start value (per-rank BN: sum,
+    then 1/world) or untouched (sync BN), every sparse table went through the row exchange exactly once, and the update
+    ran once.  Small integers in fp32: exact, no tolerance.
+
+    Before ``_finish`` learned that a dense run starting at offset 0 need not reach the end of tab_grad_flat, this failed
+    for the sparse sets {user_short}, {user_long, user_short} and {cate, user_long, user_short} with sync_bn=False,
+    coalesce=True (either ``overlap``, every hook script): the whole flat buffer was all-reduced and the row-exchanged
+    tables came out 4x."""
+    bad = _exactly_once_failures()
+    assert not bad, "%d combinations reduce something twice or not at all, e.g. %r" % (len(bad), bad[:6])
+
+
+def test_sparse_tables_accepts_a_collection_of_names_and_rejects_unknown_ones():
+    from clsr_amd.dp import DataParallel
+
+    for names in (("cate",), ["item", "user_long"], {"user_short"}, frozenset(), ()):
+        net = _StubNet()
+        dp = DataParallel(net, _ActingDist(), sync_bn=True, sparse_tables=names)
+        dp._compact_local = lambda name: None
+        dp._exchange_rows = lambda name: None
+        dp.train_step({})
+        assert sorted(dp.last_sparse) == sorted(names)
+    dp.sparse_tables = ("item",)                   # a plain attribute: the next step routes by the new value
+    dp.train_step({})
+    assert dp.last_sparse == ["item"]
+    for word, expect in (("none", []), ("all", list(net.tab_shape))):
+        dp.sparse_tables = word
+        dp.train_step({})
+        assert dp.last_sparse == expect
+    for bad in (("items",), ["cate", "nope"], "some", 3, None):
+        try:
+            DataParallel(_StubNet(), _ActingDist(), sparse_tables=bad)
+            raise AssertionError("accepted sparse_tables=%r" % (bad,))
+        except ValueError:
+            pass
+    dp.sparse_tables = ("user",)                   # ... and a reassigned value is checked when the step routes by it
+    try:
+        dp.train_step({})
+        raise AssertionError("accepted a reassigned unknown name")
+    except ValueError:
+        pass
+
+
+def test_every_replay_of_a_captured_step_exchanges_everything(monkeypatch):
+    """``run = dp.capture(f)``: the graphs replay the backward pass and the update, the exchange between them is eager host
+    code -- and must start from "nothing exchanged yet" on EVERY replay (graph launches stubbed out: host logic only).
+    It used to keep the bookkeeping of the capture's own step, so that from the second replay on only the 24 doubles and
+    the moving statistics travelled and every rank applied its local gradients."""
+    from clsr_amd import dp as dp_mod
+
+    launched = []
+    monkeypatch.setattr(dp_mod.ops, "graph_begin", lambda: None)
+    monkeypatch.setattr(dp_mod.ops, "graph_end", lambda: len(launched))
+    monkeypatch.setattr(dp_mod.ops, "graph_launch", lambda g: launched.append(g))
+    for sparse in ((), ("user_long", "user_short")):
+        net = _StubNet()
+        dp = dp_mod.DataParallel(net, _ActingDist(), sync_bn=False, sparse_tables=sparse, overlap=False)
+        exchanged = []
+
+        def rows(name, net=net, exchanged=exchanged):
+            net.tab_grad[name].mul_(2)
+            exchanged.append(name)
+
+        dp._compact_local = lambda name: None
+        dp._exchange_rows = rows
+        run = dp.capture({})
+        assert dp._graphs is not None
+        for replay in range(3):
+            del exchanged[:]
+            net.grad_flat.copy_(torch.arange(net.grad_flat.numel(), dtype=torch.float32) + 1 + replay)
+            net.stats24.copy_(torch.arange(24, dtype=torch.float64) + 3)
+            g0, s0 = net.grad_flat.clone(), net.stats24.clone()
+            run()
+            n = net.dense_grad.numel() + net.tab_grad_flat.numel()
+            assert torch.equal(net.grad_flat[:n], 2 * g0[:n]), (sparse, replay)
+            assert torch.equal(net.bn_moving, g0[n:]) and torch.equal(net.stats24, 2 * s0), (sparse, replay)
+            assert sorted(exchanged) == sorted(sparse), (sparse, replay)
+    assert len(launched) == 2 * 3 * 2
