@@ -160,19 +160,11 @@ __device__ __forceinline__ f32x4 load4e(const void* base, long idx) {
   return *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(base) + idx);
 }
 
-// One element / four elements of an embedding table stored as fp32 or as bf16 (H): read widened to fp32, written rounded
-// to nearest-even (csrc/optim.hip, csrc/multi.hip: the bf16-table forms of the regulariser / Adam / row-gather kernels)
+// One element of an embedding table stored as fp32 or as bf16 (H), widened to fp32 (csrc/optim.hip, csrc/multi.hip: the
+// regulariser kernels; the optimiser kernels read and write a table through the storage policies of csrc/tableopt.h)
 template <bool H> __device__ __forceinline__ float tbl_ld(const void* p, long e) {
   if (H) return (float)reinterpret_cast<const __bf16*>(p)[e];
   return reinterpret_cast<const float*>(p)[e];
-}
-template <bool H> __device__ __forceinline__ void tbl_st(void* p, long e, float v) {
-  if (H) reinterpret_cast<__bf16*>(p)[e] = (__bf16)v;
-  else reinterpret_cast<float*>(p)[e] = v;
-}
-template <bool H> __device__ __forceinline__ void tbl_st4(void* p, long e, f32x4 v) {
-  if (H) *reinterpret_cast<bf16x4_t*>(reinterpret_cast<__bf16*>(p) + e) = __builtin_convertvector(v, bf16x4_t);
-  else *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(p) + e) = v;
 }
 
 // bf16 table with an exact fp32 master in the same bytes as an fp32 table: next to the bf16 bits `hi` a 16-bit residual `lo`
@@ -180,7 +172,7 @@ template <bool H> __device__ __forceinline__ void tbl_st4(void* p, long e, f32x4
 // to the nearest bf16 in magnitude, ties away from zero (nearest-even cannot be encoded: an even hi would have 65 537
 // preimages), lo = b - (hi << 16) in [-0x8000, 0x7fff].  A non-finite master keeps its top half (NaN: quiet bit set, the
 // integer add would wrap 0xffffxxxx to zero) and lo = 0, so hm_unpack needs no special case.  The forward pass reads hi only;
-// the `_hm` optimiser kernels (csrc/optim.hip, csrc/multi.hip) read and write both.
+// the `_hm` optimiser kernels (csrc/tableopt.h: TableBF16M) read and write both.
 typedef unsigned short u16x4_t __attribute__((ext_vector_type(4)));
 typedef short i16x4_t __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ void hm_pack(float x, unsigned short& hi, short& lo) {
@@ -196,41 +188,6 @@ __device__ __forceinline__ void hm_pack(float x, unsigned short& hi, short& lo) 
 }
 __device__ __forceinline__ float hm_unpack(unsigned short hi, short lo) {
   return __uint_as_float(((unsigned)hi << 16) + (unsigned)(int)lo);
-}
-// four consecutive elements (8-byte accesses of both halves; element index e: multiple of 4, both pointers 8-byte aligned)
-// One Adam element update of a master (m, v, w in place; g already clipped), the SAME bits in every `_hm` kernel that
-// inlines it: left to the compiler, `b1 * m + (1 - b1) * g` is contracted into a fused multiply-add in one kernel and not
-// in another, and from the second step on (moments no longer zero) the sweep launches and the row-list launches of one
-// table stored masters one ulp apart.  Contraction is off in here and the two fused operations are spelled out; every
-// other operation is correctly rounded, hence unique.
-__device__ __forceinline__ void hm_adam_elem(float g, float& m, float& v, float& w, float b1, float b2, float eps,
-                                             float lr_t) {
-#pragma clang fp contract(off)
-  const float gm = (1.0f - b1) * g;
-  const float gv = (1.0f - b2) * g * g;
-  m = __builtin_fmaf(b1, m, gm);
-  v = __builtin_fmaf(b2, v, gv);
-  w = w - lr_t * m / (sqrtf(v) + eps);
-}
-__device__ __forceinline__ f32x4 hm_unpack4(u16x4_t hi, i16x4_t lo) {
-  f32x4 r;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) r[k] = hm_unpack(hi[k], lo[k]);
-  return r;
-}
-__device__ __forceinline__ void hm_st4(void* hi, void* lo, long e, f32x4 w) {
-  u16x4_t h;
-  i16x4_t l;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    unsigned short hk;
-    short lk;
-    hm_pack(w[k], hk, lk);
-    h[k] = hk;
-    l[k] = lk;
-  }
-  *reinterpret_cast<u16x4_t*>(reinterpret_cast<unsigned short*>(hi) + e) = h;
-  *reinterpret_cast<i16x4_t*>(reinterpret_cast<short*>(lo) + e) = l;
 }
 
 // Wave priority of the kernels on the step's dependency chain (everything except the weight-gradient partial-sum

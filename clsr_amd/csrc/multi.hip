@@ -2,7 +2,8 @@
 // blockIdx.y = job, descriptors passed to the kernel BY VALUE (read from host memory at call time).
 // Same arithmetic as the single-job kernels in embedding.hip / attention.hip / optim.hip.
 #include <stdlib.h>
-#include "common.h"
+#include <type_traits>
+#include "tableopt.h"
 #include "clsr_hip.h"
 
 template <typename D>
@@ -200,6 +201,7 @@ struct TablesArgs {
   const double* adam_state;
   float b1, b2, eps;
   int lazy;
+  short* lo[4];          // the residual halves of TableBF16M tables (Adam)
 };
 
 template <bool H>
@@ -346,80 +348,18 @@ extern "C" int clsr_tables_reg_multi_h(const clsr_table_desc* descs, int n, floa
   return tables_reg_multi_launch(descs, n, 1, l2, l1, ucount, reg_loss, stream);
 }
 
-// ---- Adam sweep of several tables (optim.hip: table_adam_kernel); the flags are cleared by the same launch
-//      chain (second kernel: every element of the sweep has read its flag by then)
-__device__ __forceinline__ float clipf(double sumsq, float clip_norm) {
-  if (clip_norm <= 0.f) return 1.0f;
-  const float nrm = (float)sqrt(sumsq);
-  return clip_norm / fmaxf(nrm, clip_norm);
-}
-
-template <bool H>
+// ---- Adam sweep of several tables (optim.hip: table_adam_kernel), T = their storage format; the flags are cleared by the
+//      same launch chain (second kernel: every element of the sweep has read its flag by then).  V4: the 16-byte form
+//      (tableopt.h: adam_sweep_v4) with the wave priority of tables_reg_multi_v4_kernel, and like it without LDS.
+template <class T, bool V4>
 __global__ void __launch_bounds__(256) tables_adam_multi_kernel(TablesArgs a) {
+  if (V4) __builtin_amdgcn_s_setprio(3);
   const clsr_table_desc d = a.t[blockIdx.y];
-  double tot = 0.0;
-  for (int i = 0; i < d.nsum; ++i) tot += d.sumsq_adam[(long)i * d.sumsq_stride];
-  const float factor = clipf(tot, a.clip_norm);
-  if (a.adam_state[4] != 0.0) return;    // aborted step (csrc/p2p.hip, csrc/headsfused.hip): touch nothing
-  const float lr_t = (float)a.adam_state[3];
-  const float b1 = a.b1, b2 = a.b2;
-  const long total = d.V * d.C;
-  for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
-    const long row = e / d.C;
-    if (a.lazy && !d.flags[row]) continue;  // every row that got gradient is also flagged as involved
-    const float g = d.grad[e] * factor;
-    const float mm = b1 * d.m[e] + (1.0f - b1) * g;
-    const float vv = b2 * d.v[e] + (1.0f - b2) * g * g;
-    d.m[e] = mm;
-    d.v[e] = vv;
-    tbl_st<H>(d.table, e, tbl_ld<H>(d.table, e) - lr_t * mm / (sqrtf(vv) + a.eps));
-    d.grad[e] = 0.f;
-  }
-}
-
-template <bool H>
-__global__ void __launch_bounds__(256) tables_adam_multi_v4_kernel(TablesArgs a) {
-  __builtin_amdgcn_s_setprio(3);
-  const clsr_table_desc d = a.t[blockIdx.y];
-  double tot = 0.0;
-  for (int i = 0; i < d.nsum; ++i) tot += d.sumsq_adam[(long)i * d.sumsq_stride];
-  const float factor = clipf(tot, a.clip_norm);
-  if (a.adam_state[4] != 0.0) return;    // aborted step (csrc/p2p.hip, csrc/headsfused.hip): touch nothing
-  const float lr_t = (float)a.adam_state[3];
-  const float b1 = a.b1, b2 = a.b2;
-  const unsigned QC = (unsigned)d.C >> 2, total = (unsigned)d.V * QC;
-  const unsigned stride = gridDim.x * 256u;
-  for (unsigned q0 = blockIdx.x * 256u + threadIdx.x; q0 < total; q0 += 2u * stride) {
-    bool f[2];
-    f32x4 g[2], m[2], v[2], w[2];
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      const unsigned q = q0 + (unsigned)u * stride, qs = q < total ? q : 0u;
-      f[u] = q < total && (!a.lazy || d.flags[qs / QC]);
-      g[u] = ld4(d.grad + 4L * qs); m[u] = ld4(d.m + 4L * qs); v[u] = ld4(d.v + 4L * qs);
-      w[u] = load4e<H>(d.table, 4L * qs);
-      // dense Adam does not read the row flags: the thread of a row's first chunk clears the row's flag here and the
-      // separate clearing launch is dropped (lazy Adam: every chunk of a row reads the flag first -- the second launch stays)
-      if (!a.lazy && q < total && q % QC == 0) d.flags[q / QC] = 0;
-    }
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      if (!f[u]) continue;
-      const long e = 4L * (q0 + (unsigned)u * stride);
-      f32x4 mm, vv, ww;
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        const float gc = g[u][c] * factor;
-        mm[c] = b1 * m[u][c] + (1.0f - b1) * gc;
-        vv[c] = b2 * v[u][c] + (1.0f - b2) * gc * gc;
-        ww[c] = w[u][c] - lr_t * mm[c] / (sqrtf(vv[c]) + a.eps);
-      }
-      st4(d.m + e, mm);
-      st4(d.v + e, vv);
-      tbl_st4<H>(d.table, e, ww);
-      st4(d.grad + e, f32x4{0.f, 0.f, 0.f, 0.f});
-    }
-  }
+  const T tab(d.table, a.lo[blockIdx.y]);
+  AdamStep s;
+  if (!adam_begin(s, d.sumsq_adam, d.sumsq_stride, d.nsum, a.clip_norm, a.adam_state, a.b1, a.b2, a.eps)) return;
+  if (V4) adam_sweep_v4(tab, d.grad, d.m, d.v, d.flags, d.V, d.C, a.lazy, s);
+  else adam_sweep(tab, d.grad, d.m, d.v, d.flags, d.V, d.C, a.lazy, s);
 }
 
 __global__ void __launch_bounds__(256) tables_clear_flags_kernel(TablesArgs a) {
@@ -427,31 +367,37 @@ __global__ void __launch_bounds__(256) tables_clear_flags_kernel(TablesArgs a) {
   for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < d.V; e += (long)gridDim.x * blockDim.x) d.flags[e] = 0;
 }
 
-static int tables_adam_multi_launch(const clsr_table_desc* descs, int n, int bf16, float clip_norm,
+// lo_ptrs_host: the residual halves of TableBF16M (NULL for the other formats)
+template <class T>
+static int tables_adam_multi_launch(const clsr_table_desc* descs, void* const* lo_ptrs_host, int n, float clip_norm,
                                     const double* adam_state, float beta1, float beta2, float eps, int lazy,
                                     void* stream) {
   TablesArgs a = {};
   long mx = 0;
   int rc = fill_tables(a, descs, n, &mx);
   if (rc) return rc;
-  CLSR_CHECK_ARG(adam_state);
+  const bool hm = std::is_same<T, TableBF16M>::value;
+  CLSR_CHECK_ARG(adam_state && (!hm || lo_ptrs_host));
   long mxv = 1;
+  bool v4 = tables_v4_ok(descs, n, true);
   for (int i = 0; i < n; ++i) {
     CLSR_CHECK_ARG(descs[i].m && descs[i].v && descs[i].sumsq_adam && descs[i].nsum > 0);
+    if (hm) {
+      CLSR_CHECK_ARG(lo_ptrs_host[i] && ((uintptr_t)lo_ptrs_host[i] & 1) == 0 && ((uintptr_t)descs[i].table & 1) == 0);
+      a.lo[i] = (short*)lo_ptrs_host[i];
+      if ((uintptr_t)lo_ptrs_host[i] % T::align4) v4 = false;
+    }
     mxv = descs[i].V > mxv ? descs[i].V : mxv;
   }
   a.clip_norm = clip_norm; a.adam_state = adam_state; a.b1 = beta1; a.b2 = beta2; a.eps = eps; a.lazy = lazy;
   int blocks = clsr_cdiv(mx, 256);
   if (blocks > 2048) blocks = 2048;
   hipStream_t s = (hipStream_t)stream;
-  const bool v4 = tables_v4_ok(descs, n, true);
   if (v4) {
     blocks = clsr_cdiv(mx / 4, 256 * 2);
     if (blocks > 2048) blocks = 2048;
-    if (bf16) hipLaunchKernelGGL(tables_adam_multi_v4_kernel<true>, dim3(blocks, n), dim3(256), 0, s, a);
-    else hipLaunchKernelGGL(tables_adam_multi_v4_kernel<false>, dim3(blocks, n), dim3(256), 0, s, a);
-  } else if (bf16) hipLaunchKernelGGL(tables_adam_multi_kernel<true>, dim3(blocks, n), dim3(256), 0, s, a);
-  else hipLaunchKernelGGL(tables_adam_multi_kernel<false>, dim3(blocks, n), dim3(256), 0, s, a);
+    hipLaunchKernelGGL((tables_adam_multi_kernel<T, true>), dim3(blocks, n), dim3(256), 0, s, a);
+  } else hipLaunchKernelGGL((tables_adam_multi_kernel<T, false>), dim3(blocks, n), dim3(256), 0, s, a);
   CLSR_CHECK_LAUNCH();
   if (v4 && !lazy) return CLSR_OK;          // (the sweep cleared the flags itself)
   int cb = clsr_cdiv(mxv, 256);
@@ -463,134 +409,19 @@ static int tables_adam_multi_launch(const clsr_table_desc* descs, int n, int bf1
 extern "C" int clsr_tables_adam_multi(const clsr_table_desc* descs, int n, float clip_norm,
                                       const double* adam_state, float beta1, float beta2, float eps, int lazy,
                                       void* stream) {
-  return tables_adam_multi_launch(descs, n, 0, clip_norm, adam_state, beta1, beta2, eps, lazy, stream);
+  return tables_adam_multi_launch<TableF32>(descs, nullptr, n, clip_norm, adam_state, beta1, beta2, eps, lazy, stream);
 }
 // the tables of the descriptors are bf16 [V, C]: widened, updated in fp32, rounded to nearest-even
 extern "C" int clsr_tables_adam_multi_h(const clsr_table_desc* descs, int n, float clip_norm,
                                         const double* adam_state, float beta1, float beta2, float eps, int lazy,
                                         void* stream) {
-  return tables_adam_multi_launch(descs, n, 1, clip_norm, adam_state, beta1, beta2, eps, lazy, stream);
+  return tables_adam_multi_launch<TableBF16>(descs, nullptr, n, clip_norm, adam_state, beta1, beta2, eps, lazy, stream);
 }
-
-// ---- the same sweep for bf16 tables with an exact fp32 master (common.h: hm_pack / hm_unpack; csrc/optim.hip): desc.table
-//      is the bf16 half, the 16-bit residuals come as a parallel pointer array (clsr_table_desc keeps its layout)
-struct TablesArgsM {
-  TablesArgs a;
-  short* lo[4];
-};
-
-__global__ void __launch_bounds__(256) tables_adam_multi_hm_kernel(TablesArgsM am) {
-  const TablesArgs& a = am.a;
-  const clsr_table_desc d = a.t[blockIdx.y];
-  unsigned short* hi = reinterpret_cast<unsigned short*>(d.table);
-  short* lo = am.lo[blockIdx.y];
-  double tot = 0.0;
-  for (int i = 0; i < d.nsum; ++i) tot += d.sumsq_adam[(long)i * d.sumsq_stride];
-  const float factor = clipf(tot, a.clip_norm);
-  if (a.adam_state[4] != 0.0) return;    // aborted step (csrc/p2p.hip, csrc/headsfused.hip): touch nothing
-  const float lr_t = (float)a.adam_state[3];
-  const float b1 = a.b1, b2 = a.b2;
-  const long total = d.V * d.C;
-  for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
-    const long row = e / d.C;
-    if (a.lazy && !d.flags[row]) continue;  // every row that got gradient is also flagged as involved
-    const float g = d.grad[e] * factor;
-    float mm = d.m[e], vv = d.v[e], w = hm_unpack(hi[e], lo[e]);
-    hm_adam_elem(g, mm, vv, w, b1, b2, a.eps, lr_t);
-    d.m[e] = mm;
-    d.v[e] = vv;
-    unsigned short h;
-    short l;
-    hm_pack(w, h, l);
-    hi[e] = h;
-    lo[e] = l;
-    d.grad[e] = 0.f;
-  }
-}
-
-__global__ void __launch_bounds__(256) tables_adam_multi_hm_v4_kernel(TablesArgsM am) {
-  __builtin_amdgcn_s_setprio(3);
-  const TablesArgs& a = am.a;
-  const clsr_table_desc d = a.t[blockIdx.y];
-  unsigned short* hi = reinterpret_cast<unsigned short*>(d.table);
-  short* lo = am.lo[blockIdx.y];
-  double tot = 0.0;
-  for (int i = 0; i < d.nsum; ++i) tot += d.sumsq_adam[(long)i * d.sumsq_stride];
-  const float factor = clipf(tot, a.clip_norm);
-  if (a.adam_state[4] != 0.0) return;    // aborted step (csrc/p2p.hip, csrc/headsfused.hip): touch nothing
-  const float lr_t = (float)a.adam_state[3];
-  const float b1 = a.b1, b2 = a.b2;
-  const unsigned QC = (unsigned)d.C >> 2, total = (unsigned)d.V * QC;
-  const unsigned stride = gridDim.x * 256u;
-  for (unsigned q0 = blockIdx.x * 256u + threadIdx.x; q0 < total; q0 += 2u * stride) {
-    bool f[2];
-    f32x4 g[2], m[2], v[2];
-    u16x4_t wh[2];
-    i16x4_t wl[2];
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      const unsigned q = q0 + (unsigned)u * stride, qs = q < total ? q : 0u;
-      f[u] = q < total && (!a.lazy || d.flags[qs / QC]);
-      g[u] = ld4(d.grad + 4L * qs); m[u] = ld4(d.m + 4L * qs); v[u] = ld4(d.v + 4L * qs);
-      wh[u] = *reinterpret_cast<const u16x4_t*>(hi + 4L * qs);
-      wl[u] = *reinterpret_cast<const i16x4_t*>(lo + 4L * qs);
-      // (dense Adam: the thread of a row's first chunk clears the row's flag, as in tables_adam_multi_v4_kernel)
-      if (!a.lazy && q < total && q % QC == 0) d.flags[q / QC] = 0;
-    }
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      if (!f[u]) continue;
-      const long e = 4L * (q0 + (unsigned)u * stride);
-      const f32x4 w = hm_unpack4(wh[u], wl[u]);
-      f32x4 mm, vv, ww;
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        float mc = m[u][c], vc = v[u][c], wc = w[c];
-        hm_adam_elem(g[u][c] * factor, mc, vc, wc, b1, b2, a.eps, lr_t);
-        mm[c] = mc;
-        vv[c] = vc;
-        ww[c] = wc;
-      }
-      st4(d.m + e, mm);
-      st4(d.v + e, vv);
-      hm_st4(hi, lo, e, ww);
-      st4(d.grad + e, f32x4{0.f, 0.f, 0.f, 0.f});
-    }
-  }
-}
-
+// bf16 tables with an exact fp32 master (tableopt.h: TableBF16M): desc.table is the bf16 half, the 16-bit residuals come as
+// a parallel pointer array (clsr_table_desc keeps its layout)
 extern "C" int clsr_tables_adam_multi_hm(const clsr_table_desc* descs, void* const* lo_ptrs_host, int n, float clip_norm,
                                          const double* adam_state, float beta1, float beta2, float eps, int lazy,
                                          void* stream) {
-  TablesArgsM am = {};
-  TablesArgs& a = am.a;
-  long mx = 0;
-  int rc = fill_tables(a, descs, n, &mx);
-  if (rc) return rc;
-  CLSR_CHECK_ARG(adam_state && lo_ptrs_host);
-  long mxv = 1;
-  bool v4 = tables_v4_ok(descs, n, true);
-  for (int i = 0; i < n; ++i) {
-    CLSR_CHECK_ARG(descs[i].m && descs[i].v && descs[i].sumsq_adam && descs[i].nsum > 0 && lo_ptrs_host[i]);
-    CLSR_CHECK_ARG(((uintptr_t)lo_ptrs_host[i] & 1) == 0 && ((uintptr_t)descs[i].table & 1) == 0);
-    am.lo[i] = (short*)lo_ptrs_host[i];
-    if ((uintptr_t)lo_ptrs_host[i] & 7) v4 = false;
-    mxv = descs[i].V > mxv ? descs[i].V : mxv;
-  }
-  a.clip_norm = clip_norm; a.adam_state = adam_state; a.b1 = beta1; a.b2 = beta2; a.eps = eps; a.lazy = lazy;
-  int blocks = clsr_cdiv(mx, 256);
-  if (blocks > 2048) blocks = 2048;
-  hipStream_t s = (hipStream_t)stream;
-  if (v4) {
-    blocks = clsr_cdiv(mx / 4, 256 * 2);
-    if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(tables_adam_multi_hm_v4_kernel, dim3(blocks, n), dim3(256), 0, s, am);
-  } else hipLaunchKernelGGL(tables_adam_multi_hm_kernel, dim3(blocks, n), dim3(256), 0, s, am);
-  CLSR_CHECK_LAUNCH();
-  if (v4 && !lazy) return CLSR_OK;          // (the sweep cleared the flags itself)
-  int cb = clsr_cdiv(mxv, 256);
-  if (cb > 512) cb = 512;
-  hipLaunchKernelGGL(tables_clear_flags_kernel, dim3(cb, n), dim3(256), 0, s, a);
-  CLSR_CHECK_LAUNCH();
-  return CLSR_OK;
+  return tables_adam_multi_launch<TableBF16M>(descs, lo_ptrs_host, n, clip_norm, adam_state, beta1, beta2, eps, lazy,
+                                              stream);
 }

@@ -12,7 +12,7 @@
 // Dense parameters live in ONE flat fp32 buffer (param, grad, m, v) with a per-element tensor id
 // map, so the whole dense update is three launches regardless of the number of tensors.
 #include <stdlib.h>
-#include "common.h"
+#include "tableopt.h"
 #include <cstdlib>
 
 // state[0]=step, [1]=beta1^t, [2]=beta2^t, [3]=lr_t, [4]=abort flag of the step   (doubles, device resident so graph
@@ -119,12 +119,6 @@ extern "C" int clsr_dense_reg_norm_tick_t(const float* param, float* grad, const
 extern "C" int clsr_dense_reg_norm(const float* param, float* grad, const int* seg_off, int nseg,
                                    float l2, float l1, double* sumsq, double* reg_loss, void* stream) {
   return clsr_dense_reg_norm_tick(param, grad, seg_off, nseg, l2, l1, sumsq, reg_loss, nullptr, 0.0, 0.0, 0.0, stream);
-}
-
-__device__ __forceinline__ float clip_factor(double sumsq, float clip_norm) {
-  if (clip_norm <= 0.f) return 1.0f;
-  const float nrm = (float)sqrt(sumsq);
-  return clip_norm / fmaxf(nrm, clip_norm);
 }
 
 // Flat dense Adam: g = grad[e] * clip_factor(sumsq[seg_of[e]]); grad is zeroed for the next step.
@@ -265,48 +259,30 @@ extern "C" int clsr_table_reg_h(const void* table, const void* partner, const un
 // Pass B: Adam sweep of one table.  sumsq[i * sumsq_stride], i < nsum, are the squared norms of this table's
 // IndexedSlices pieces (lookup sites + involved rows); lazy != 0 restricts the update to rows whose
 // flag is set or that received gradient through a lookup (LazyAdam).  Clears grad rows and flags.
-template <bool H>
+// T: the storage format of the table (tableopt.h, with the loop and the element update that every table Adam kernel shares).
+template <class T>
 __global__ void __launch_bounds__(256) table_adam_kernel(
-    void* __restrict__ table, float* __restrict__ grad_table, float* __restrict__ m,
-    float* __restrict__ v, unsigned char* __restrict__ flags, long V, int C,
-    const double* __restrict__ sumsq, int sumsq_stride, int nsum, float clip_norm,
-    const double* __restrict__ adam_state, float b1, float b2, float eps, int lazy) {
-  double tot = 0.0;
-  for (int i = 0; i < nsum; ++i) tot += sumsq[(long)i * sumsq_stride];
-  const float factor = clip_factor(tot, clip_norm);
-  if (adam_state[4] != 0.0) return;      // the step was aborted (a collective / grid barrier gave up): touch nothing
-  const float lr_t = (float)adam_state[3];
-  const long total = V * C;
-  for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
-    const long row = e / C;
-    const float g = grad_table[e] * factor;
-    if (lazy && !flags[row]) continue;  // every row that got gradient is also flagged as involved
-    const float mm = b1 * m[e] + (1.0f - b1) * g;
-    const float vv = b2 * v[e] + (1.0f - b2) * g * g;
-    m[e] = mm;
-    v[e] = vv;
-    tbl_st<H>(table, e, tbl_ld<H>(table, e) - lr_t * mm / (sqrtf(vv) + eps));
-    grad_table[e] = 0.f;
-  }
+    const T tab, float* __restrict__ grad_table, float* __restrict__ m, float* __restrict__ v,
+    const unsigned char* __restrict__ flags, long V, int C, const double* __restrict__ sumsq, int sumsq_stride, int nsum,
+    float clip_norm, const double* __restrict__ adam_state, float b1, float b2, float eps, int lazy) {
+  AdamStep s;
+  if (adam_begin(s, sumsq, sumsq_stride, nsum, clip_norm, adam_state, b1, b2, eps))
+    adam_sweep(tab, grad_table, m, v, flags, V, C, lazy, s);
 }
 
 __global__ void clear_bytes_kernel(unsigned char* p, long n) {
   for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (long)gridDim.x * blockDim.x) p[e] = 0;
 }
 
-static int table_adam_launch(void* table, int bf16, float* grad_table, float* m, float* v, unsigned char* flags, long V,
-                             int C, const double* sumsq, int sumsq_stride, int nsum, float clip_norm,
-                             const double* adam_state, float beta1, float beta2, float eps, int lazy, void* stream) {
-  CLSR_CHECK_ARG(table && grad_table && m && v && flags && sumsq && adam_state && V > 0 && C > 0 && nsum > 0);
+template <class T>
+static int table_adam_launch(T tab, float* grad_table, float* m, float* v, unsigned char* flags, long V, int C,
+                             const double* sumsq, int sumsq_stride, int nsum, float clip_norm, const double* adam_state,
+                             float beta1, float beta2, float eps, int lazy, void* stream) {
   int blocks = clsr_cdiv(V * C, 256);
   if (blocks > 4096) blocks = 4096;
   hipStream_t s = (hipStream_t)stream;
-  if (bf16)
-    hipLaunchKernelGGL(table_adam_kernel<true>, dim3(blocks), dim3(256), 0, s, table, grad_table, m, v, flags, V, C,
-                       sumsq, sumsq_stride, nsum, clip_norm, adam_state, beta1, beta2, eps, lazy);
-  else
-    hipLaunchKernelGGL(table_adam_kernel<false>, dim3(blocks), dim3(256), 0, s, table, grad_table, m, v, flags, V, C,
-                       sumsq, sumsq_stride, nsum, clip_norm, adam_state, beta1, beta2, eps, lazy);
+  hipLaunchKernelGGL(table_adam_kernel<T>, dim3(blocks), dim3(256), 0, s, tab, grad_table, m, v, flags, V, C, sumsq,
+                     sumsq_stride, nsum, clip_norm, adam_state, beta1, beta2, eps, lazy);
   CLSR_CHECK_LAUNCH();
   int cb = clsr_cdiv(V, 256);
   if (cb > 1024) cb = 1024;
@@ -318,17 +294,28 @@ extern "C" int clsr_table_adam(float* table, float* grad_table, float* m, float*
                                long V, int C, const double* sumsq, int sumsq_stride, int nsum,
                                float clip_norm, const double* adam_state, float beta1, float beta2,
                                float eps, int lazy, void* stream) {
-  return table_adam_launch(table, 0, grad_table, m, v, flags, V, C, sumsq, sumsq_stride, nsum, clip_norm, adam_state, beta1,
-                           beta2, eps, lazy, stream);
+  CLSR_CHECK_ARG(table && grad_table && m && v && flags && sumsq && adam_state && V > 0 && C > 0 && nsum > 0);
+  return table_adam_launch(TableF32(table), grad_table, m, v, flags, V, C, sumsq, sumsq_stride, nsum, clip_norm, adam_state,
+                           beta1, beta2, eps, lazy, stream);
 }
 // bf16 table: widened, updated in fp32 (fp32 moments / gradients), rounded to nearest-even
 extern "C" int clsr_table_adam_h(void* table_bf16, float* grad_table, float* m, float* v, unsigned char* flags,
                                  long V, int C, const double* sumsq, int sumsq_stride, int nsum,
                                  float clip_norm, const double* adam_state, float beta1, float beta2,
                                  float eps, int lazy, void* stream) {
-  return table_adam_launch(table_bf16, 1, grad_table, m, v, flags, V, C, sumsq, sumsq_stride, nsum, clip_norm, adam_state,
-                           beta1, beta2, eps, lazy, stream);
+  CLSR_CHECK_ARG(table_bf16 && grad_table && m && v && flags && sumsq && adam_state && V > 0 && C > 0 && nsum > 0);
+  return table_adam_launch(TableBF16(table_bf16), grad_table, m, v, flags, V, C, sumsq, sumsq_stride, nsum, clip_norm,
+                           adam_state, beta1, beta2, eps, lazy, stream);
 }
+// bf16 table with an exact fp32 master, the pair (hi, lo): rebuilt, updated as an fp32 table, both halves stored back
+extern "C" int clsr_table_adam_hm(void* hi, void* lo, float* grad_table, float* m, float* v, unsigned char* flags, long V,
+                                  int C, const double* sumsq, int sumsq_stride, int nsum, float clip_norm,
+                                  const double* adam_state, float beta1, float beta2, float eps, int lazy, void* stream) {
+  CLSR_CHECK_ARG(hi && lo && grad_table && m && v && flags && sumsq && adam_state && V > 0 && C > 0 && nsum > 0);
+  return table_adam_launch(TableBF16M(hi, lo), grad_table, m, v, flags, V, C, sumsq, sumsq_stride, nsum, clip_norm,
+                           adam_state, beta1, beta2, eps, lazy, stream);
+}
+
 
 // ---- row-list variants for huge vocabularies (100M-item catalogues): the same math as table_reg / lazy
 // table_adam, but driven by the compacted id list of the involved rows (clsr_flags_compact) instead of a sweep
@@ -415,156 +402,21 @@ extern "C" int clsr_table_reg_rows_h(const void* table, const void* partner, con
                                sumsq, reg_loss, disc_loss, stream);
 }
 
-// LazyAdam over the listed rows; clears their gradient rows and flags.
-// UN pieces per lane and trip: their 4 * UN loads are issued before the first one is used (random 384-byte rows of a
-// 38 GB table: the update is bound by how many row reads are in flight; UN = 1 ran at 4.4-4.7 TB/s)
-template <int VW, int UN>
-__global__ void __launch_bounds__(256) table_adam_rows_kernel(
-    float* __restrict__ table, float* __restrict__ grad_table, float* __restrict__ m, float* __restrict__ v,
-    unsigned char* __restrict__ flags, const int* __restrict__ ids, const int* __restrict__ count, int C,
-    const double* __restrict__ sumsq, int sumsq_stride, int nsum, float clip_norm,
-    const double* __restrict__ adam_state, float b1, float b2, float eps) {
-  double tot = 0.0;
-  for (int i = 0; i < nsum; ++i) tot += sumsq[(long)i * sumsq_stride];
-  const float factor = clip_factor(tot, clip_norm);
-  if (adam_state[4] != 0.0) return;      // the step was aborted (a collective / grid barrier gave up): touch nothing
-  const float lr_t = (float)adam_state[3];
-  const int QC = C / VW;
-  const long total = (long)count[0] * QC;
-  const long stride = (long)gridDim.x * blockDim.x;
-  for (long i0 = (long)blockIdx.x * blockDim.x + threadIdx.x; i0 < total; i0 += stride * UN) {
-    long e[UN], row[UN];
-    int q[UN];
-    bool ok[UN];
-    float g[UN][VW], mo[UN][VW], vo[UN][VW], po[UN][VW];
-#pragma unroll
-    for (int u = 0; u < UN; ++u) {
-      const long i = i0 + u * stride;
-      ok[u] = i < total;
-      const long ic = ok[u] ? i : i0;
-      const long r = ic / QC;
-      q[u] = (int)(ic - r * QC);
-      row[u] = ids[r];
-      e[u] = row[u] * C + (long)q[u] * VW;
-    }
-#pragma unroll
-    for (int u = 0; u < UN; ++u) {
-      if (VW == 4) {
-        *reinterpret_cast<f32x4*>(g[u]) = ld4(grad_table + e[u]);
-        *reinterpret_cast<f32x4*>(mo[u]) = ld4(m + e[u]);
-        *reinterpret_cast<f32x4*>(vo[u]) = ld4(v + e[u]);
-        *reinterpret_cast<f32x4*>(po[u]) = ld4(table + e[u]);
-      } else {
-        g[u][0] = grad_table[e[u]]; mo[u][0] = m[e[u]]; vo[u][0] = v[e[u]]; po[u][0] = table[e[u]];
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < UN; ++u) {
-#pragma unroll
-      for (int k = 0; k < VW; ++k) {
-        const float gg = g[u][k] * factor;
-        const float mm = b1 * mo[u][k] + (1.0f - b1) * gg;
-        const float vv = b2 * vo[u][k] + (1.0f - b2) * gg * gg;
-        mo[u][k] = mm;
-        vo[u][k] = vv;
-        po[u][k] -= lr_t * mm / (sqrtf(vv) + eps);
-      }
-      if (ok[u]) {
-        if (VW == 4) {
-          const f32x4 z = {0.f, 0.f, 0.f, 0.f};
-          st4(m + e[u], *reinterpret_cast<f32x4*>(mo[u]));
-          st4(v + e[u], *reinterpret_cast<f32x4*>(vo[u]));
-          st4(table + e[u], *reinterpret_cast<f32x4*>(po[u]));
-          st4(grad_table + e[u], z);
-        } else {
-          m[e[u]] = mo[u][0]; v[e[u]] = vo[u][0]; table[e[u]] = po[u][0]; grad_table[e[u]] = 0.f;
-        }
-        if (q[u] == 0) flags[row[u]] = 0;
-      }
-    }
-  }
-}
-
-// The same update for a table stored as bf16 (SURVEY 8d "bf16 tables"): the row is widened, updated in fp32 with fp32
-// moments and gradients, and rounded to nearest-even when written back (6 + 2 x 2 bytes per element instead of 8 x 4:
-// 28 against 32).  Without an fp32 master copy an update smaller than half a bf16 ulp of the weight (2^-9 relative) is
-// lost; the parity test pins exactly this arithmetic.
-template <int UN>
-__global__ void __launch_bounds__(256) table_adam_rows_h_kernel(
-    __bf16* __restrict__ table, float* __restrict__ grad_table, float* __restrict__ m, float* __restrict__ v,
-    unsigned char* __restrict__ flags, const int* __restrict__ ids, const int* __restrict__ count, int C,
-    const double* __restrict__ sumsq, int sumsq_stride, int nsum, float clip_norm,
-    const double* __restrict__ adam_state, float b1, float b2, float eps) {
-  double tot = 0.0;
-  for (int i = 0; i < nsum; ++i) tot += sumsq[(long)i * sumsq_stride];
-  const float factor = clip_factor(tot, clip_norm);
-  if (adam_state[4] != 0.0) return;      // the step was aborted (a collective / grid barrier gave up): touch nothing
-  const float lr_t = (float)adam_state[3];
-  const int QC = C / 4;
-  const long total = (long)count[0] * QC;
-  const long stride = (long)gridDim.x * blockDim.x;
-  for (long i0 = (long)blockIdx.x * blockDim.x + threadIdx.x; i0 < total; i0 += stride * UN) {
-    long e[UN], row[UN];
-    int q[UN];
-    bool ok[UN];
-    f32x4 g[UN], mo[UN], vo[UN];
-    bf16x4_t ph[UN];
-#pragma unroll
-    for (int u = 0; u < UN; ++u) {
-      const long i = i0 + u * stride;
-      ok[u] = i < total;
-      const long ic = ok[u] ? i : i0;
-      const long r = ic / QC;
-      q[u] = (int)(ic - r * QC);
-      row[u] = ids[r];
-      e[u] = row[u] * C + (long)q[u] * 4;
-    }
-#pragma unroll
-    for (int u = 0; u < UN; ++u) {
-      g[u] = ld4(grad_table + e[u]);
-      mo[u] = ld4(m + e[u]);
-      vo[u] = ld4(v + e[u]);
-      ph[u] = *reinterpret_cast<const bf16x4_t*>(table + e[u]);
-    }
-#pragma unroll
-    for (int u = 0; u < UN; ++u) {
-      f32x4 po = __builtin_convertvector(ph[u], f32x4);
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const float gg = g[u][k] * factor;
-        const float mm = b1 * mo[u][k] + (1.0f - b1) * gg;
-        const float vv = b2 * vo[u][k] + (1.0f - b2) * gg * gg;
-        mo[u][k] = mm;
-        vo[u][k] = vv;
-        po[k] -= lr_t * mm / (sqrtf(vv) + eps);
-      }
-      if (ok[u]) {
-        const f32x4 z = {0.f, 0.f, 0.f, 0.f};
-        st4(m + e[u], mo[u]);
-        st4(v + e[u], vo[u]);
-        *reinterpret_cast<bf16x4_t*>(table + e[u]) = __builtin_convertvector(po, bf16x4_t);
-        st4(grad_table + e[u], z);
-        if (q[u] == 0) flags[row[u]] = 0;
-      }
-    }
-  }
-}
-
-extern "C" int clsr_table_adam_rows_h(void* table_bf16, float* grad_table, float* m, float* v, unsigned char* flags,
-                                      const int* ids, const int* count, int cap, int C, const double* sumsq,
-                                      int sumsq_stride, int nsum, float clip_norm, const double* adam_state,
-                                      float beta1, float beta2, float eps, void* stream) {
-  CLSR_CHECK_ARG(table_bf16 && grad_table && m && v && flags && ids && count && sumsq && adam_state && cap > 0 && C > 0);
-  CLSR_CHECK_ARG(nsum > 0);
-  CLSR_CHECK_SUPPORTED(C % 4 == 0 && ((uintptr_t)table_bf16 % 8) == 0);
-  int blocks = clsr_cdiv((long)cap * C, 256 * 4 * 2);
+// LazyAdam over the listed rows; clears their gradient rows and flags (tableopt.h: table_adam_rows_kernel<T, VW, UN>,
+// VW values per piece, UN pieces per lane and trip)
+template <class T, int VW, int UN>
+static int table_adam_rows_launch(T tab, float* grad_table, float* m, float* v, unsigned char* flags, const int* ids,
+                                  const int* count, int cap, int C, const double* sumsq, int sumsq_stride, int nsum,
+                                  float clip_norm, const double* adam_state, float beta1, float beta2, float eps,
+                                  void* stream) {
+  int blocks = clsr_cdiv((long)cap * C, 256 * 4 * UN);
   if (blocks > 4096) blocks = 4096;
-  hipLaunchKernelGGL(table_adam_rows_h_kernel<2>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (__bf16*)table_bf16,
-                     grad_table, m, v, flags, ids, count, C, sumsq, sumsq_stride, nsum, clip_norm, adam_state, beta1, beta2,
-                     eps);
+  hipLaunchKernelGGL((table_adam_rows_kernel<T, VW, UN>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, tab, grad_table,
+                     m, v, flags, ids, count, C, sumsq, sumsq_stride, nsum, clip_norm, adam_state, beta1, beta2, eps);
   CLSR_CHECK_LAUNCH();
   return CLSR_OK;
 }
+#define ROWS_ARGS grad_table, m, v, flags, ids, count, cap, C, sumsq, sumsq_stride, nsum, clip_norm, adam_state, beta1, beta2, eps, stream
 
 extern "C" int clsr_table_adam_rows(float* table, float* grad_table, float* m, float* v, unsigned char* flags,
                                     const int* ids, const int* count, int cap, int C, const double* sumsq,
@@ -572,149 +424,28 @@ extern "C" int clsr_table_adam_rows(float* table, float* grad_table, float* m, f
                                     float beta1, float beta2, float eps, void* stream) {
   CLSR_CHECK_ARG(table && grad_table && m && v && flags && ids && count && sumsq && adam_state && cap > 0 && C > 0);
   CLSR_CHECK_ARG(nsum > 0);
-  const bool vec = C % 4 == 0;
-  int blocks = clsr_cdiv((long)cap * C, 256 * 4 * (vec ? 2 : 1));
-  constexpr int cap_blocks = 4096;
-  if (blocks > cap_blocks) blocks = cap_blocks;
-  if (vec)
-    hipLaunchKernelGGL((table_adam_rows_kernel<4, 2>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, table, grad_table,
-                       m, v, flags, ids, count, C, sumsq, sumsq_stride, nsum, clip_norm, adam_state, beta1, beta2, eps);
-  else
-    hipLaunchKernelGGL((table_adam_rows_kernel<1, 1>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, table, grad_table,
-                       m, v, flags, ids, count, C, sumsq, sumsq_stride, nsum, clip_norm, adam_state, beta1, beta2, eps);
-  CLSR_CHECK_LAUNCH();
-  return CLSR_OK;
+  if (C % 4 == 0) return table_adam_rows_launch<TableF32, 4, 2>(TableF32(table), ROWS_ARGS);
+  return table_adam_rows_launch<TableF32, 1, 1>(TableF32(table), ROWS_ARGS);
 }
-
-// ---- bf16 tables with an exact fp32 master (common.h: hm_pack / hm_unpack): the table is the pair (hi = the bf16 values
-// every other kernel reads, lo = 16-bit residual); the update rebuilds the fp32 master from both halves, updates it exactly
-// as the fp32 kernels do and stores both halves back -- no update is lost to the bf16 rounding, and a step stays
-// deterministic.  Per element g, m, v (4 + 4 bytes each) + hi (2 + 2) + lo (2 + 2) = 32 bytes: the fp32 update's traffic.
-//
-// The row-list form: table_adam_rows_h_kernel<2> with a second 8-byte stream per piece.
-template <int UN>
-__global__ void __launch_bounds__(256) table_adam_rows_hm_kernel(
-    unsigned short* __restrict__ hi, short* __restrict__ lo, float* __restrict__ grad_table, float* __restrict__ m,
-    float* __restrict__ v, unsigned char* __restrict__ flags, const int* __restrict__ ids, const int* __restrict__ count,
-    int C, const double* __restrict__ sumsq, int sumsq_stride, int nsum, float clip_norm,
-    const double* __restrict__ adam_state, float b1, float b2, float eps) {
-  double tot = 0.0;
-  for (int i = 0; i < nsum; ++i) tot += sumsq[(long)i * sumsq_stride];
-  const float factor = clip_factor(tot, clip_norm);
-  if (adam_state[4] != 0.0) return;      // the step was aborted (a collective / grid barrier gave up): touch nothing
-  const float lr_t = (float)adam_state[3];
-  const int QC = C / 4;
-  const long total = (long)count[0] * QC;
-  const long stride = (long)gridDim.x * blockDim.x;
-  for (long i0 = (long)blockIdx.x * blockDim.x + threadIdx.x; i0 < total; i0 += stride * UN) {
-    long e[UN], row[UN];
-    int q[UN];
-    bool ok[UN];
-    f32x4 g[UN], mo[UN], vo[UN];
-    u16x4_t ph[UN];
-    i16x4_t pl[UN];
-#pragma unroll
-    for (int u = 0; u < UN; ++u) {
-      const long i = i0 + u * stride;
-      ok[u] = i < total;
-      const long ic = ok[u] ? i : i0;
-      const long r = ic / QC;
-      q[u] = (int)(ic - r * QC);
-      row[u] = ids[r];
-      e[u] = row[u] * C + (long)q[u] * 4;
-    }
-#pragma unroll
-    for (int u = 0; u < UN; ++u) {
-      g[u] = ld4(grad_table + e[u]);
-      mo[u] = ld4(m + e[u]);
-      vo[u] = ld4(v + e[u]);
-      ph[u] = *reinterpret_cast<const u16x4_t*>(hi + e[u]);
-      pl[u] = *reinterpret_cast<const i16x4_t*>(lo + e[u]);
-    }
-#pragma unroll
-    for (int u = 0; u < UN; ++u) {
-      f32x4 po = hm_unpack4(ph[u], pl[u]);
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        float mk = mo[u][k], vk = vo[u][k], pk = po[k];
-        hm_adam_elem(g[u][k] * factor, mk, vk, pk, b1, b2, eps, lr_t);
-        mo[u][k] = mk;
-        vo[u][k] = vk;
-        po[k] = pk;
-      }
-      if (ok[u]) {
-        const f32x4 z = {0.f, 0.f, 0.f, 0.f};
-        st4(m + e[u], mo[u]);
-        st4(v + e[u], vo[u]);
-        hm_st4(hi, lo, e[u], po);
-        st4(grad_table + e[u], z);
-        if (q[u] == 0) flags[row[u]] = 0;
-      }
-    }
-  }
+extern "C" int clsr_table_adam_rows_h(void* table_bf16, float* grad_table, float* m, float* v, unsigned char* flags,
+                                      const int* ids, const int* count, int cap, int C, const double* sumsq,
+                                      int sumsq_stride, int nsum, float clip_norm, const double* adam_state,
+                                      float beta1, float beta2, float eps, void* stream) {
+  CLSR_CHECK_ARG(table_bf16 && grad_table && m && v && flags && ids && count && sumsq && adam_state && cap > 0 && C > 0);
+  CLSR_CHECK_ARG(nsum > 0);
+  CLSR_CHECK_SUPPORTED(C % 4 == 0 && ((uintptr_t)table_bf16 % TableBF16::align4) == 0);
+  return table_adam_rows_launch<TableBF16, 4, 2>(TableBF16(table_bf16), ROWS_ARGS);
 }
-
 extern "C" int clsr_table_adam_rows_hm(void* hi, void* lo, float* grad_table, float* m, float* v, unsigned char* flags,
                                        const int* ids, const int* count, int cap, int C, const double* sumsq,
                                        int sumsq_stride, int nsum, float clip_norm, const double* adam_state,
                                        float beta1, float beta2, float eps, void* stream) {
   CLSR_CHECK_ARG(hi && lo && grad_table && m && v && flags && ids && count && sumsq && adam_state && cap > 0 && C > 0);
   CLSR_CHECK_ARG(nsum > 0);
-  CLSR_CHECK_SUPPORTED(C % 4 == 0 && ((uintptr_t)hi % 8) == 0 && ((uintptr_t)lo % 8) == 0);
-  int blocks = clsr_cdiv((long)cap * C, 256 * 4 * 2);
-  if (blocks > 4096) blocks = 4096;
-  hipLaunchKernelGGL(table_adam_rows_hm_kernel<2>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (unsigned short*)hi,
-                     (short*)lo, grad_table, m, v, flags, ids, count, C, sumsq, sumsq_stride, nsum, clip_norm, adam_state,
-                     beta1, beta2, eps);
-  CLSR_CHECK_LAUNCH();
-  return CLSR_OK;
+  CLSR_CHECK_SUPPORTED(C % 4 == 0 && ((uintptr_t)hi % TableBF16M::align4) == 0 && ((uintptr_t)lo % TableBF16M::align4) == 0);
+  return table_adam_rows_launch<TableBF16M, 4, 2>(TableBF16M(hi, lo), ROWS_ARGS);
 }
-
-// The sweep of one table (table_adam_kernel), dense or lazy; clears gradient rows and flags like the other forms.
-__global__ void __launch_bounds__(256) table_adam_hm_kernel(
-    unsigned short* __restrict__ hi, short* __restrict__ lo, float* __restrict__ grad_table, float* __restrict__ m,
-    float* __restrict__ v, const unsigned char* __restrict__ flags, long V, int C, const double* __restrict__ sumsq,
-    int sumsq_stride, int nsum, float clip_norm, const double* __restrict__ adam_state, float b1, float b2, float eps,
-    int lazy) {
-  double tot = 0.0;
-  for (int i = 0; i < nsum; ++i) tot += sumsq[(long)i * sumsq_stride];
-  const float factor = clip_factor(tot, clip_norm);
-  if (adam_state[4] != 0.0) return;      // the step was aborted (a collective / grid barrier gave up): touch nothing
-  const float lr_t = (float)adam_state[3];
-  const long total = V * C;
-  for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
-    const long row = e / C;
-    const float g = grad_table[e] * factor;
-    if (lazy && !flags[row]) continue;  // every row that got gradient is also flagged as involved
-    float mm = m[e], vv = v[e], w = hm_unpack(hi[e], lo[e]);
-    hm_adam_elem(g, mm, vv, w, b1, b2, eps, lr_t);
-    m[e] = mm;
-    v[e] = vv;
-    unsigned short h;
-    short l;
-    hm_pack(w, h, l);
-    hi[e] = h;
-    lo[e] = l;
-    grad_table[e] = 0.f;
-  }
-}
-
-extern "C" int clsr_table_adam_hm(void* hi, void* lo, float* grad_table, float* m, float* v, unsigned char* flags, long V,
-                                  int C, const double* sumsq, int sumsq_stride, int nsum, float clip_norm,
-                                  const double* adam_state, float beta1, float beta2, float eps, int lazy, void* stream) {
-  CLSR_CHECK_ARG(hi && lo && grad_table && m && v && flags && sumsq && adam_state && V > 0 && C > 0 && nsum > 0);
-  int blocks = clsr_cdiv(V * C, 256);
-  if (blocks > 4096) blocks = 4096;
-  hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(table_adam_hm_kernel, dim3(blocks), dim3(256), 0, s, (unsigned short*)hi, (short*)lo, grad_table, m, v,
-                     flags, V, C, sumsq, sumsq_stride, nsum, clip_norm, adam_state, beta1, beta2, eps, lazy);
-  CLSR_CHECK_LAUNCH();
-  int cb = clsr_cdiv(V, 256);
-  if (cb > 1024) cb = 1024;
-  hipLaunchKernelGGL(clear_bytes_kernel, dim3(cb), dim3(256), 0, s, flags, V);
-  CLSR_CHECK_LAUNCH();
-  return CLSR_OK;
-}
+#undef ROWS_ARGS
 
 // fp32 values -> (hi, lo) and back (construction, checkpoints); n elements, any alignment
 __global__ void __launch_bounds__(256) table_split_hm_kernel(const float* __restrict__ src, unsigned short* __restrict__ hi,

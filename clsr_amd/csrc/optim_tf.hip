@@ -17,7 +17,7 @@
 // instantiation loads and stores its own slots only (bytes per element: sgd 16, adagrad 24, the two-slot ones 32).
 // Every kernel returns without touching anything while state[4] (the abort flag of the step) is raised.
 #include <stdlib.h>
-#include "common.h"
+#include "tableopt.h"
 #include "clsr_hip.h"
 
 enum { TF_SGD = 0, TF_ADAGRAD = 1, TF_PADAGRAD = 2, TF_RMSPROP = 3, TF_ADADELTA = 4, TF_FTRL = 5, TF_NOPT = 6 };
@@ -27,12 +27,6 @@ __host__ __device__ constexpr int tf_slots(int o) {
 }
 
 extern "C" int clsr_tf_opt_slots(int opt) { return opt >= 0 && opt < TF_NOPT ? tf_slots(opt) : CLSR_EINVAL; }
-
-__device__ __forceinline__ float tf_clip(double sumsq, float clip_norm) {
-  if (clip_norm <= 0.f) return 1.0f;
-  const float nrm = (float)sqrt(sumsq);
-  return clip_norm / fmaxf(nrm, clip_norm);
-}
 
 // one element: g already clipped; p, s1, s2 updated in place (s1 / s2 unused by the optimisers that lack them)
 template <int O>
@@ -80,7 +74,7 @@ __global__ void __launch_bounds__(256) dense_tf_kernel(float* __restrict__ param
   for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < n; e += gridDim.x * blockDim.x) {
     const int seg = seg_of[e];
     if (!(skip && skip[seg])) {
-      const float g = grad[e] * tf_clip(sumsq[seg], clip_norm);
+      const float g = grad[e] * clip_factor(sumsq[seg], clip_norm);
       float p = param[e], a = NS > 0 ? s1[e] : 0.f, b = NS > 1 ? s2[e] : 0.f;
       tf_update<O>(g, lr, p, a, b);
       param[e] = p;
@@ -136,16 +130,10 @@ struct TfTablesArgs {
   int clear_flags;       // the v4 sweep clears the flags itself (every chunk of a row lies in one wave)
 };
 
-__device__ __forceinline__ float table_factor(const clsr_table_desc& d, float clip_norm) {
-  double tot = 0.0;
-  for (int i = 0; i < d.nsum; ++i) tot += d.sumsq_adam[(long)i * d.sumsq_stride];
-  return tf_clip(tot, clip_norm);
-}
-
 template <int O>
 __global__ void __launch_bounds__(256) tables_tf_multi_kernel(TfTablesArgs a) {
   const clsr_table_desc d = a.t[blockIdx.y];
-  const float factor = table_factor(d, a.clip_norm);
+  const float factor = clip_factor(d.sumsq_adam, d.sumsq_stride, d.nsum, a.clip_norm);
   if (a.state[4] != 0.0) return;    // aborted step: touch nothing
   constexpr int NS = tf_slots(O);
   const long total = d.V * d.C;
@@ -161,7 +149,7 @@ __global__ void __launch_bounds__(256) tables_tf_multi_kernel(TfTablesArgs a) {
 }
 
 // Rows of 4 k values, 16-byte aligned operands: one 16-byte access per operand and lane, the loads of two grid strides
-// issued together from clamped addresses and selected by the row flags afterwards (as tables_adam_multi_v4_kernel).
+// issued together from clamped addresses and selected by the row flags afterwards (as adam_sweep_v4 of tableopt.h).
 // No LDS: this launch runs beside the fused encoder tail (csrc/encbwd.hip), which owns every CU's LDS.
 // When the chunks of a row count divides 64 (a.clear_flags), all chunks of a row lie in ONE wave and the same unroll
 // slot -- the flag is read by one load instruction of that wave before the row's first lane clears it: the flags are
@@ -170,7 +158,7 @@ template <int O>
 __global__ void __launch_bounds__(256) tables_tf_multi_v4_kernel(TfTablesArgs a) {
   __builtin_amdgcn_s_setprio(3);
   const clsr_table_desc d = a.t[blockIdx.y];
-  const float factor = table_factor(d, a.clip_norm);
+  const float factor = clip_factor(d.sumsq_adam, d.sumsq_stride, d.nsum, a.clip_norm);
   if (a.state[4] != 0.0) return;    // aborted step: touch nothing
   constexpr int NS = tf_slots(O);
   const unsigned QC = (unsigned)d.C >> 2, total = (unsigned)d.V * QC;
@@ -268,9 +256,7 @@ __global__ void __launch_bounds__(256) table_tf_rows_kernel(
     unsigned char* __restrict__ flags, const int* __restrict__ ids, const int* __restrict__ count, int C,
     const double* __restrict__ sumsq, int sumsq_stride, int nsum, float clip_norm, const double* __restrict__ state,
     float lr) {
-  double tot = 0.0;
-  for (int i = 0; i < nsum; ++i) tot += sumsq[(long)i * sumsq_stride];
-  const float factor = tf_clip(tot, clip_norm);
+  const float factor = clip_factor(sumsq, sumsq_stride, nsum, clip_norm);
   if (state[4] != 0.0) return;      // aborted step: touch nothing
   constexpr int NS = tf_slots(O);
   const int QC = C / VW;

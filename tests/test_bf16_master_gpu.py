@@ -2,10 +2,10 @@
 include/clsr_hip.h: the ``_hm`` kernels).  The table is the pair (hi = the bf16 values every lookup reads, lo = a 16-bit
 residual) with  bits(master) = (hi << 16) + sign_extend(lo)  mod 2^32,  hi = (bits + 0x8000) >> 16.
 
-The updates are compared with the fp32 kernels run on the merged master at  1e-6 |w| + 1e-6 U  (U: the largest |delta w| of
-the case).  The two sides are separate compilations whose fused-multiply-add contractions can differ by one ulp in the
-moments (the bar of tests/test_bf16_tables_gpu.py on m and v, 1e-6 relative, is kept here): that perturbs an update by a few
-parts in 10^7 of itself, and the stored master adds one fp32 rounding of w (6e-8 |w|)."""
+Every `_hm` kernel inlines the element update of the fp32 kernel on the same launch path (csrc/tableopt.h: adam_elem): its
+moments equal the fp32 kernel's and merge(hi, lo) equals the fp32 table, bit for bit.  Where a whole step is compared
+with the fp32 net (other gradients' norms come from float64 atomics) the bar is  1e-6 |w| + 1e-6 U  (U: the largest
+|delta w| of the case)."""
 import copy
 import os
 import pickle
@@ -40,13 +40,6 @@ def np_split(x):
 def np_merge(hi, lo):
     b = ((hi.astype(np.int64) << 16) + lo.astype(np.int64)) & 0xFFFFFFFF
     return b.astype(np.uint32).view(np.float32)
-
-
-def _close(got, exp, rtol, atol, name):
-    got, exp = got.double().cpu().reshape(-1), exp.double().cpu().reshape(-1)
-    err = (got - exp).abs()
-    excess = float((err - (atol + rtol * exp.abs())).max())
-    assert excess <= 0, "%s: max abs err %.3e (max |exp| %.3e)" % (name, float(err.max()), float(exp.abs().max()))
 
 
 def test_split_and_merge_against_the_restatement():
@@ -112,9 +105,8 @@ def _check_update(c, hi, lo, gr, m, v, fl, tf, gf, mf, vf, ff, touched, name):
     assert torch.equal(bits16(hi)[untouched], bits16(hi0)[untouched]) and torch.equal(lo[untouched], lo0[untouched])
     assert torch.equal(gr, gf) and torch.equal(fl, ff), "gradient rows and flags cleared as by the fp32 kernel"
     assert float(gr[touched].abs().max()) == 0.0
-    _close(m, mf, 1e-6, 2e-9, name + ": first moments")
-    _close(v, vf, 1e-6, 1e-12, name + ": second moments")
-    _master_bar(merge(hi, lo), tf, c["w"], name)
+    assert torch.equal(m, mf) and torch.equal(v, vf), name + ": the moments of the fp32 kernel"
+    assert torch.equal(merge(hi, lo), tf), name + ": the master is the fp32 kernel's table"
     assert not torch.equal(tf[touched], c["w"][touched])
 
 

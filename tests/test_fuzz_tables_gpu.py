@@ -19,7 +19,7 @@ import fuzz_tables  # noqa: E402
 
 # case 0 is a regression case (FUZZ_CASE 16,8,1,64,2,time4lstm, dense adam): on its second step the master net through the
 # sweep launches and the one through the single-table / row-list launches stored item masters one ulp apart -- the Adam
-# moment updates were contracted into fused multiply-adds differently from kernel to kernel (common.h: hm_adam_elem)
+# moment updates were contracted into fused multiply-adds differently from kernel to kernel (csrc/tableopt.h: adam_elem)
 IDS = ["regression_16_8_1_64_2_time4lstm_adam_second_step"] + ["case%d" % i for i in range(1, len(fuzz_tables.CASES))]
 
 
