@@ -477,9 +477,10 @@ class SequentialBaseModel(BaseModel):
         return self
 
     # ------------------------------------------------------------------ evaluation on the device
-    def _device_eval(self, filename, num_ngs, weighted):
+    def _device_eval(self, filename, num_ngs, weighted, mean_alpha=False):
         """Score ``filename`` and compute the metrics on the device (clsr_amd/device_metrics.py): no per-batch host
-        synchronisation, scores never leave HBM.  None when a requested metric has no device form (host path then)."""
+        synchronisation, scores never leave HBM.  None when a requested metric has no device form (host path then).
+        ``mean_alpha``: keep the net's fusion weight of every line as well and return ``mean_alpha``."""
         from clsr_amd import device_metrics as DM
 
         if os.environ.get("CLSR_HOST_METRICS") or not DM.supported(self.hparams, self.user_vocab_length, num_ngs + 1):
@@ -494,7 +495,8 @@ class SequentialBaseModel(BaseModel):
                 key, f, _ = self._static_feed(feed, False)
                 out = self.net.forward(f, False)
                 pred = torch.sigmoid(out["logit"]) if self.hparams.method == "classification" else out["logit"]
-                acc.append(pred, f["labels"], f["users_rows"] if "users_rows" in f else f["users"])
+                acc.append(pred, f["labels"], f["users_rows"] if "users_rows" in f else f["users"],
+                           out["alpha"] if mean_alpha else None)
 
             # the iterator's batches (hparams.batch_size LINES each) are scored several at a time: a forward pass is
             # ~100 launches whatever its size, and nothing here waits for the device between batches
@@ -515,7 +517,8 @@ class SequentialBaseModel(BaseModel):
                     pend, rows = [], 0
             if pend:
                 score(pend)
-            return DM.compute(acc, self.hparams, num_ngs + 1, weighted)
+            return DM.compute(acc, self.hparams, num_ngs + 1, weighted, n_users=self.user_vocab_length,
+                              mean_alpha=mean_alpha)
 
     def run_eval(self, filename, num_ngs):
         """auc/logloss + pairwise metrics over groups of ``num_ngs + 1`` lines
@@ -546,8 +549,8 @@ class SequentialBaseModel(BaseModel):
     def run_weighted_eval(self, filename, num_ngs, calc_mean_alpha=False, manual_alpha=False):
         """run_eval + user-weighted metrics (wauc == the README's GAUC)
         (reference sequential_base_model.py:244-292)."""
-        if not calc_mean_alpha:
-            res = self._device_eval(filename, num_ngs, True)
+        if not (calc_mean_alpha and manual_alpha):      # (manual_alpha reads one batch's alpha only: host path)
+            res = self._device_eval(filename, num_ngs, True, mean_alpha=calc_mean_alpha)
             if res is not None:
                 return res
         users, preds, labels, alphas = [], [], [], []

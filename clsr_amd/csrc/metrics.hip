@@ -4,10 +4,12 @@
 // Reference: reco_utils/recommender/deeprec/deeprec_utils.py:554-821 (mrr_score, ndcg_score, hit_score, cal_metric,
 // cal_weighted_metric) as called by SequentialBaseModel.run_eval / run_weighted_eval
 // (models/sequential/sequential_base_model.py:204-292): auc + logloss over all lines, mean_mrr / ndcg@k / hit@k /
-// group_auc over groups of 1 + num_ngs consecutive lines, wauc = per-user roc_auc weighted by the user's line count.
+// group_auc over groups of 1 + num_ngs consecutive lines, rmse / acc / f1 and the mean fusion weight from one reduction
+// over all lines, and the user-weighted wauc / wmrr / whit@k / wndcg@k: per-user values weighted by the user's line count.
 //
-// No sort anywhere: ROC-AUC with averaged tie ranks equals (#{pos > neg} + 0.5 #{pos == neg}) / (n_pos n_neg) -- integer
-// pair counts, exact -- and a positive's rank inside its group is a count as well.  Pair counting is P x N work for
+// No sort of the scores anywhere (the lines are grouped by user id with the stable radix sort of csrc/segsum.hip, any
+// non-negative int32 id): ROC-AUC with averaged tie ranks equals (#{pos > neg} + 0.5 #{pos == neg}) / (n_pos n_neg) --
+// integer pair counts, exact -- and a positive's rank inside its group is a count as well.  Pair counting is P x N work for
 // the global AUC (1e10 compare-and-count operations for a 1M-line test file: milliseconds on 256 CUs) and
 // P_u x n_u inside a user / a group.  Rank ties (equal scores inside a group) break like a STABLE ascending sort read
 // backwards: among equal scores the LATER line ranks first.  (numpy's default argsort, which the reference uses, is
@@ -37,6 +39,9 @@ static void fx_finalize(double* out, int n, double scale, hipStream_t s) {
 #define FX_LOGLOSS 67108864.0              // 2^26: the sum is at most 27 N (N < 2^31 lines)
 #define FX_GROUP 1073741824.0              // 2^30: sums of per-group values in [0, 1]
 #define FX_WAUC 1152921504606846976.0      // 2^60: the weighted sum is at most 1
+// 2^32: sums over the lines of terms in [0, 1] -- a squared error (predictions are sigmoid outputs and labels 0 / 1: the
+// net refuses `method: regression`), alpha * label, label -- are at most N < 2^31, so the scaled sum stays below 2^63
+#define FX_POINT 4294967296.0
 
 // out[0] = sum over lines of -(y log p + (1 - y) log(1 - p)), p clipped to [1e-11, 1 - 1e-11] (cal_metric "logloss")
 __global__ void __launch_bounds__(256) eval_logloss_kernel(const float* __restrict__ pred,
@@ -255,8 +260,9 @@ extern "C" int clsr_eval_group_metrics(const float* pred, const float* labels, l
   return CLSR_OK;
 }
 
-// ---- wauc: lines grouped by user (clsr_sort_ids_multi on the user ids: perm + the end offset of every user's
-// segment), one wave per user: out[0] += (n_u / N) * roc_auc(user u); err[0] += users whose lines are all one class
+// ---- wauc over the buckets of the COUNTING sort (clsr_sort_ids_multi on the user ids: perm + the end offset of every
+// bucket; one bucket = one user only for ids below 2^18 -- device_metrics.py uses clsr_eval_user_metrics below), one
+// wave per user: out[0] += (n_u / N) * roc_auc(user u); err[0] += users whose lines are all one class
 #define UA_PT 256
 __global__ void __launch_bounds__(256) eval_user_auc_kernel(const float* __restrict__ pred,
                                                             const float* __restrict__ labels,
@@ -329,6 +335,276 @@ extern "C" int clsr_eval_user_auc(const float* pred, const float* labels, const 
   hipLaunchKernelGGL(eval_user_auc_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, pred, labels, perm, ends,
                      nb, N, out, err);
   fx_finalize(out, 1, FX_WAUC, (hipStream_t)stream);
+  CLSR_CHECK_LAUNCH();
+  return CLSR_OK;
+}
+
+// ---- user segments: keys = the user ids of the lines in ascending order (clsr_sort_ids_stable_multi: equal ids stay in
+// line order).  starts[0 .. count[0]) = the entries e with e == 0 or keys[e] != keys[e - 1], in ANY order; count[0] must be
+// zero on entry and never travels to the host: the consumer strides over it.
+__global__ void __launch_bounds__(256) eval_user_segments_kernel(const int* __restrict__ keys, long N,
+                                                                 int* __restrict__ starts, int* __restrict__ count) {
+  const int lane = threadIdx.x & 63;
+  for (long e0 = (long)blockIdx.x * 256; e0 < N; e0 += (long)gridDim.x * 256) {
+    const long e = e0 + threadIdx.x;
+    const bool on = e < N && (e == 0 || keys[e] != keys[e - 1]);
+    const u64 m = __ballot(on);
+    int base = 0;
+    if (lane == 0 && m) base = atomicAdd(count, __popcll(m));
+    base = __shfl(base, 0, 64);
+    if (on) starts[base + __popcll(m & ((1ull << lane) - 1ull))] = (int)e;
+  }
+}
+
+extern "C" int clsr_eval_user_segments(const int* keys, long N, int* starts, int* count, void* stream) {
+  CLSR_CHECK_ARG(keys && starts && count && N > 0);
+  CLSR_CHECK_SUPPORTED(N < (1L << 31) - 2048);
+  int blocks = clsr_cdiv(N, 256 * 4);
+  if (blocks > 2048) blocks = 2048;
+  hipLaunchKernelGGL(eval_user_segments_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, keys, N, starts, count);
+  CLSR_CHECK_LAUNCH();
+  return CLSR_OK;
+}
+
+// ---- user-weighted metrics: one wave per user segment.  With w = n_u / N, P_u positives and the rank of a positive line
+// i = 1 + #{j in u: s_j > s_i or (s_j == s_i and line_j > line_i)} (line = the index in the file = perm, so the rule does
+// not depend on the order inside the segment; the group kernel's rule):
+//   out[0] += w roc_auc(u)   out[1] += w (sum 1 / rank) / P_u   out[2 + i] += w dcg@ks[i] / ideal dcg@ks[i]
+//   out[2 + GM_MAXK + i] += w [any rank <= ks[i]];   err[0] += users whose lines are all one class (want_auc only),
+//   err[1] += users without a positive line (they add nothing to out[1 ..]; the host path yields NaN for mrr / ndcg there).
+// The wave takes the user's positives 64 at a time, one per lane (a cursor walks the segment once), and streams ALL lines
+// of the user past them through an LDS tile of 64 lines: a positive's rank count (RANK: ONE 64-bit compare per line, key =
+// order-preserving score bits above the line index) and its (positive > negative, positive == negative) pair counts (AUC:
+// a positive line of the tile holds +inf) come out of the same loop; a wauc-only request pays for the pair counts alone.
+// The tile after next is already on its way while a tile is compared (a user with very many lines is ONE wave: nothing
+// else hides the two dependent trips perm -> pred / labels).  P_u x n_u / 64 steps per user, any n_u and P_u.  Every
+// user's values are rounded to fixed point on their own and added as integers: which wave meets which user (the start
+// list is unordered) does not show.
+struct UserMetricArgs {
+  const float* pred; const float* labels; const int* perm; const int* keys; const int* starts; const int* count;
+  long N; int nk; int ks[GM_MAXK];
+  double* out; int* err;
+};
+__device__ __forceinline__ u64 fx_wauc(double v) { return (u64)__double2ll_rn(v * FX_WAUC); }
+// s > t or (s == t and line_s > line_t)  <=>  um_key(s, line_s) > um_key(t, line_t)   (finite scores, -0 == +0)
+__device__ __forceinline__ u64 um_key(float s, int line) {
+  const unsigned b = __float_as_uint(s + 0.0f);
+  return ((u64)(b ^ ((b >> 31) ? 0xffffffffu : 0x80000000u)) << 32) | (unsigned)line;
+}
+// LDS written by one lane of the wave and read by another: LDS operations of a wave execute in order, so only the
+// compiler has to be held (no wait for the global loads in flight, which a workgroup fence would add)
+__device__ __forceinline__ void um_wave_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+template <bool AUC, bool RANK>
+__global__ void __launch_bounds__(256) eval_user_metrics_kernel(UserMetricArgs a) {
+  __shared__ float tn[4][64];   // tile: score of a NEGATIVE line, +inf for a positive one (hand-over: a positive's score)
+  __shared__ u64 tk[4][64];     // tile: rank key of a line (hand-over: a positive's line)
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  float* sn = tn[wave];
+  u64* sk = tk[wave];
+  const int nseg = a.count[0];
+  const u64 below = (1ull << lane) - 1ull;
+  u64 acc[2 + 2 * GM_MAXK];
+#pragma unroll
+  for (int i = 0; i < 2 + 2 * GM_MAXK; ++i) acc[i] = 0;
+  int bad = 0, nopos = 0;
+  for (long b = (long)blockIdx.x * 4 + wave; b < nseg; b += (long)gridDim.x * 4) {
+    const int lo = __builtin_amdgcn_readfirstlane(a.starts[b]);      // (the same in every lane: scalar loop bounds)
+    const int key = a.keys[lo];
+    int hi = (int)a.N;        // the segment ends at the first later entry with another key
+    for (long i0 = (long)lo + 1; i0 < a.N; i0 += 64) {
+      const long i = i0 + lane;
+      const u64 m = __ballot(i < a.N && a.keys[i] != key);
+      if (m) { hi = (int)(i0 + (__ffsll((long long)m) - 1)); break; }
+    }
+    const int n = __builtin_amdgcn_readfirstlane(hi - lo);
+    u64 gt = 0, eq = 0;
+    double mrr = 0.0, dcg[GM_MAXK];
+#pragma unroll
+    for (int k = 0; k < GM_MAXK; ++k) dcg[k] = 0.0;
+    int hits = 0, npos = 0;     // hits: bit k = a positive of this lane ranks within ks[k]
+    int cur = 0, skip = 0;      // cursor of the positive scan: chunk start in the segment, positives of it already taken
+    while (true) {
+      // the next (up to) 64 positives of the segment, in segment order: number t of them -> lane t
+      um_wave_sync();
+      int got = 0;
+      while (cur < n && got < 64) {
+        const int i = cur + lane;
+        int row = 0;
+        bool on = false;
+        if (i < n) { row = a.perm[lo + i]; on = a.labels[row] == 1.0f; }
+        const u64 m = __ballot(on);
+        const int before = __popcll(m & below), idx = got + before - skip;
+        if (on && before >= skip && idx < 64) { sn[idx] = a.pred[row]; sk[idx] = (u64)(unsigned)row; }
+        const int avail = __popcll(m) - skip;
+        if (got + avail > 64) { skip += 64 - got; got = 64; }      // the rest of this chunk: next round
+        else { got += avail; skip = 0; cur += 64; }
+      }
+      if (got == 0) break;
+      npos += got;
+      um_wave_sync();
+      const bool have = lane < got;
+      const float v = have ? sn[lane] + 0.0f : 0.0f;
+      const u64 kv = um_key(v, have ? (int)sk[lane] : 0);
+      int above = 0;
+      unsigned g = 0, q = 0;
+      // lines of the segment, 64 (one per lane) at a time: rowB = the rows of the tile after next,
+      // (rowA, pA, yA) = the next tile
+      int rowA = lane < n ? a.perm[lo + lane] : -1;
+      int rowB = 64 + lane < n ? a.perm[lo + 64 + lane] : -1;
+      float pA = 0.0f, yA = 0.0f;
+      if (rowA >= 0) { pA = a.pred[rowA]; yA = a.labels[rowA]; }
+      for (int j0 = 0; j0 < n; j0 += 64) {
+        const int cnt = min(64, n - j0);
+        um_wave_sync();
+        if (lane < cnt) {
+          if (AUC) sn[lane] = yA == 1.0f ? INFINITY : pA + 0.0f;
+          if (RANK) sk[lane] = um_key(pA, rowA);
+        }
+        rowA = rowB;
+        rowB = j0 + 128 + lane < n ? a.perm[lo + j0 + 128 + lane] : -1;
+        if (rowA >= 0) { pA = a.pred[rowA]; yA = a.labels[rowA]; }
+        um_wave_sync();
+        if (have) {
+          if (cnt == 64) {      // a whole tile: wide LDS reads, compares of several lines in flight
+#pragma unroll 16
+            for (int j = 0; j < 64; ++j) {
+              if (RANK) above += sk[j] > kv ? 1 : 0;
+              if (AUC) { const float t = sn[j]; g += v > t ? 1u : 0u; q += v == t ? 1u : 0u; }
+            }
+          } else {
+            for (int j = 0; j < cnt; ++j) {
+              if (RANK) above += sk[j] > kv ? 1 : 0;
+              if (AUC) { const float t = sn[j]; g += v > t ? 1u : 0u; q += v == t ? 1u : 0u; }
+            }
+          }
+        }
+      }
+      if (have) {
+        gt += g; eq += q;
+        if (RANK) {
+          const int rank = above + 1;
+          mrr += 1.0 / (double)rank;
+#pragma unroll
+          for (int k = 0; k < GM_MAXK; ++k)
+            if (k < a.nk && rank <= a.ks[k]) { dcg[k] += 1.0 / log2((double)rank + 1.0); hits |= 1 << k; }
+        }
+      }
+      if (got < 64) break;      // (the scan reached the end of the segment)
+    }
+    const double w = (double)n / (double)a.N;
+    const int nneg = n - npos;
+    if (AUC) {
+      const double gtd = wave_sum_d((double)gt), eqd = wave_sum_d((double)eq);
+      if (npos == 0 || nneg == 0) ++bad;
+      else acc[0] += fx_wauc(w * ((gtd + 0.5 * eqd) / ((double)npos * (double)nneg)));
+    }
+    if (npos == 0) { ++nopos; continue; }
+    if (RANK) {
+      acc[1] += fx_wauc(w * (wave_sum_d(mrr) / (double)npos));
+#pragma unroll
+      for (int k = 0; k < GM_MAXK; ++k) {
+        if (k < a.nk) {
+          const double d = wave_sum_d(dcg[k]);
+          double ideal = 0.0;
+          const int kk = min(min(a.ks[k], n), npos);
+          for (int r = 1 + lane; r <= kk; r += 64) ideal += 1.0 / log2((double)r + 1.0);
+          ideal = wave_sum_d(ideal);
+          acc[2 + k] += fx_wauc(w * (d / ideal));
+          if (__ballot((hits >> k) & 1)) acc[2 + GM_MAXK + k] += fx_wauc(w);
+        }
+      }
+    }
+  }
+  if (lane == 0) {
+#pragma unroll
+    for (int i = 0; i < 2 + 2 * GM_MAXK; ++i)
+      if (acc[i]) atomicAdd(reinterpret_cast<u64*>(a.out) + i, acc[i]);
+    if (bad) atomicAdd(a.err, bad);
+    if (nopos) atomicAdd(a.err + 1, nopos);
+  }
+}
+
+extern "C" int clsr_eval_user_metrics(const float* pred, const float* labels, const int* perm, const int* keys,
+                                      const int* starts, const int* count, long N, const int* ks_host, int nk,
+                                      int want_auc, int want_rank, double* out, int* err, void* stream) {
+  CLSR_CHECK_ARG(pred && labels && perm && keys && starts && count && out && err && N > 0 && nk >= 0 &&
+                 (nk == 0 || ks_host) && (want_auc || want_rank) && (want_rank || nk == 0));
+  CLSR_CHECK_SUPPORTED(nk <= GM_MAXK && N < (1L << 31) - 2048);
+  UserMetricArgs a;
+  a.pred = pred; a.labels = labels; a.perm = perm; a.keys = keys; a.starts = starts; a.count = count;
+  a.N = N; a.nk = nk; a.out = out; a.err = err;
+  for (int i = 0; i < GM_MAXK; ++i) {
+    CLSR_CHECK_ARG(i >= nk || ks_host[i] > 0);
+    a.ks[i] = i < nk ? ks_host[i] : 0;
+  }
+  int blocks = clsr_cdiv(N, 4);      // at most one wave per line: the number of users stays on the device
+  if (blocks > 4096) blocks = 4096;
+  hipStream_t s = (hipStream_t)stream;
+  if (want_auc && want_rank) hipLaunchKernelGGL((eval_user_metrics_kernel<true, true>), dim3(blocks), dim3(256), 0, s, a);
+  else if (want_auc) hipLaunchKernelGGL((eval_user_metrics_kernel<true, false>), dim3(blocks), dim3(256), 0, s, a);
+  else hipLaunchKernelGGL((eval_user_metrics_kernel<false, true>), dim3(blocks), dim3(256), 0, s, a);
+  fx_finalize(out, 2 + 2 * GM_MAXK, FX_WAUC, s);
+  CLSR_CHECK_LAUNCH();
+  return CLSR_OK;
+}
+
+// ---- point statistics in one pass over the lines (cal_metric "rmse" / "acc" / "f1", cal_mean_alpha_metric):
+// outd[0] += sum (label - pred)^2, outd[1] += sum alpha * label, outd[2] += sum label (the last two only with alpha);
+// outu[0] += #{(pred >= 0.5) == label}, outu[1 .. 3] += TP, FP, FN at the threshold 0.5 (positive: label == 1)
+__global__ void __launch_bounds__(256) eval_point_stats_kernel(const float* __restrict__ pred,
+                                                               const float* __restrict__ labels,
+                                                               const float* __restrict__ alpha, long N,
+                                                               double* __restrict__ outd, u64* __restrict__ outu) {
+  __shared__ double red[3][4];
+  __shared__ u64 redu[4][4];
+  double s[3] = {0.0, 0.0, 0.0};
+  u64 c[4] = {0, 0, 0, 0};
+  for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < N; e += (long)gridDim.x * 256) {
+    const float p = pred[e], y = labels[e];
+    const double d = (double)y - (double)p;
+    s[0] += d * d;
+    const bool pp = p >= 0.5f, lab = y == 1.0f;
+    c[0] += (pp ? 1.0f : 0.0f) == y ? 1 : 0;
+    c[1] += pp && lab ? 1 : 0;
+    c[2] += pp && !lab ? 1 : 0;
+    c[3] += !pp && lab ? 1 : 0;
+    if (alpha) { s[1] += (double)alpha[e] * (double)y; s[2] += (double)y; }
+  }
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) s[k] = block256_sum_d(s[k], red[k]);
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) c[k] += __shfl_xor(c[k], o, 64);
+    if (lane == 0) redu[k][wave] = c[k];
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+      if (s[k] != 0.0) fx_add(outd + k, s[k], FX_POINT);
+  }
+  if (threadIdx.x < 4) {
+    const u64 t = redu[threadIdx.x][0] + redu[threadIdx.x][1] + redu[threadIdx.x][2] + redu[threadIdx.x][3];
+    if (t) atomicAdd(outu + threadIdx.x, t);
+  }
+}
+
+extern "C" int clsr_eval_point_stats(const float* pred, const float* labels, const float* alpha, long N, double* out_d3,
+                                     void* out_u64x4, void* stream) {
+  CLSR_CHECK_ARG(pred && labels && out_d3 && out_u64x4 && N > 0);
+  CLSR_CHECK_SUPPORTED(N < (1L << 31));
+  int blocks = clsr_cdiv(N, 256 * 8);
+  if (blocks > 2048) blocks = 2048;
+  hipLaunchKernelGGL(eval_point_stats_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, pred, labels, alpha, N,
+                     out_d3, (u64*)out_u64x4);
+  fx_finalize(out_d3, 3, FX_POINT, (hipStream_t)stream);
   CLSR_CHECK_LAUNCH();
   return CLSR_OK;
 }

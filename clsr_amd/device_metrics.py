@@ -1,26 +1,42 @@
 """Evaluation metrics computed on the device (csrc/metrics.hip) -- the scores of a whole validation / test file stay
 in HBM, no per-batch synchronisation, and a handful of doubles comes back at the end.
 
-Mirrors ``cal_metric`` / ``cal_weighted_metric`` of the reference (deeprec_utils.py:621-806) as
-``SequentialBaseModel.run_eval`` / ``run_weighted_eval`` call them (sequential_base_model.py:204-292): same keys,
-same 4-decimal rounding, same ``ValueError`` when an AUC is undefined.  Supported: ``auc``, ``logloss`` (all lines);
-``mean_mrr``, ``ndcg@k``, ``hit@k``, ``group_auc`` (groups of 1 + num_ngs consecutive lines); ``wauc`` (per user).
-Anything else -- more than 2^18 users, whose grouping is not exact on the device, or groups of more than
-``MAX_GROUP`` lines, which the group kernel does not take -- makes :func:`supported` return False and the caller keeps
-the host path (clsr_amd/deeprec_utils.py)."""
+Mirrors ``cal_metric`` / ``cal_weighted_metric`` / ``cal_mean_alpha_metric`` of the reference (deeprec_utils.py:621-813)
+as ``SequentialBaseModel.run_eval`` / ``run_weighted_eval`` call them (sequential_base_model.py:204-292): same keys,
+same 4-decimal rounding, same ``ValueError`` when an AUC is undefined, NaN where the reference divides 0 by 0 (``wmrr`` /
+``wndcg@k`` with a user who has no positive line).  Supported: ``auc``, ``logloss``, ``rmse``, ``acc``, ``f1`` (all
+lines); ``mean_mrr``, ``ndcg@k``, ``hit@k``, ``group_auc`` (groups of 1 + num_ngs consecutive lines); ``wauc``, ``wmrr``,
+``whit@k``, ``wndcg@k`` (per user: any non-negative int32 id, any number of users -- the lines are grouped with the stable
+radix sort of csrc/segsum.hip); ``mean_alpha``.  Rank ties break towards the later line of the file, in groups and in
+users alike.  What stays on the host (:func:`supported` returns False, the caller keeps clsr_amd/deeprec_utils.py): more
+than 8 distinct k over the pairwise or over the weighted metrics, and groups of more than ``MAX_GROUP`` lines."""
 import ctypes
+import math
 
 import torch
 
 from clsr_amd import ops
 from clsr_amd.deeprec_utils import _ks
 
-_POINT = {"auc", "logloss"}
+_POINT = {"auc", "logloss", "rmse", "acc", "f1"}
 MAX_GROUP = 4096      # clsr_eval_group_metrics: one wave per group, the group's scores and labels in LDS (csrc/metrics.hip)
+MAX_K = 8             # distinct k of one kernel launch (GM_MAXK, csrc/metrics.hip)
+
+
+def _weighted_ks(wm):
+    """Sorted distinct k over the whit@ / wndcg@ entries of ``wm``; None when an entry has no device form."""
+    ks = set()
+    for m in wm:
+        if m.startswith("whit") or m.startswith("wndcg"):
+            ks.update(_ks(m))
+        elif m not in ("wauc", "wmrr"):
+            return None
+    return sorted(ks)
 
 
 def supported(hp, n_users, group):
-    """``group``: lines per group of the pairwise metrics (1 + num_ngs)."""
+    """``group``: lines per group of the pairwise metrics (1 + num_ngs).  ``n_users`` does not matter any more (the
+    user grouping is exact for every id); the argument stays for the callers."""
     if any(m not in _POINT for m in (hp.metrics or [])):
         return False
     ks = set()
@@ -29,56 +45,73 @@ def supported(hp, n_users, group):
             ks.update(_ks(m))
         elif m not in ("mean_mrr", "group_auc"):
             return False
-    if len(ks) > 8:
+    if len(ks) > MAX_K:
         return False
     if (hp.pairwise_metrics or []) and group > MAX_GROUP:
         return False
-    if any(m != "wauc" for m in (getattr(hp, "weighted_metrics", None) or [])):
-        return False
-    return n_users <= (1 << 18)
+    wks = _weighted_ks(getattr(hp, "weighted_metrics", None) or [])
+    return wks is not None and len(wks) <= MAX_K and all(k > 0 for k in wks)
 
 
 class DeviceScores(object):
-    """Growing device buffers of (pred, label, user) per scored line; appends are stream-ordered copies."""
+    """Growing device buffers of (pred, label, user[, alpha]) per scored line; appends are stream-ordered copies.  The
+    alpha column (the long / short fusion weight, for ``mean_alpha``) is allocated only when the batches carry one."""
 
     def __init__(self, device):
         self.device, self.n, self.cap = device, 0, 0
-        self.pred = self.labels = self.users = None
+        self.pred = self.labels = self.users = self.alpha = None
 
-    def _grow(self, need):
+    @property
+    def has_alpha(self):
+        return self.alpha is not None
+
+    def _grow(self, need, with_alpha):
         cap = max(need, 2 * self.cap, 1 << 16)
-        new = (torch.empty(cap, dtype=torch.float32, device=self.device),
+        new = [torch.empty(cap, dtype=torch.float32, device=self.device),
                torch.empty(cap, dtype=torch.float32, device=self.device),
-               torch.empty(cap, dtype=torch.int32, device=self.device))
+               torch.empty(cap, dtype=torch.int32, device=self.device),
+               torch.empty(cap, dtype=torch.float32, device=self.device) if with_alpha else None]
         if self.n:
-            for dst, src in zip(new, (self.pred, self.labels, self.users)):
-                dst[: self.n].copy_(src[: self.n])
-        self.pred, self.labels, self.users = new
+            for dst, src in zip(new, (self.pred, self.labels, self.users, self.alpha)):
+                if dst is not None:
+                    dst[: self.n].copy_(src[: self.n])
+        self.pred, self.labels, self.users, self.alpha = new
         self.cap = cap
 
-    def append(self, pred, labels, users):
+    def append(self, pred, labels, users, alpha=None):
         b = pred.numel()
-        if self.n + b > self.cap:
-            self._grow(self.n + b)
+        if self.n and (alpha is not None) != self.has_alpha:
+            raise ValueError("either every appended batch carries an alpha column or none does")
+        if self.n + b > self.cap or (alpha is not None and self.alpha is None):
+            self._grow(self.n + b, alpha is not None)
         self.pred[self.n:self.n + b].copy_(pred.reshape(-1))
         self.labels[self.n:self.n + b].copy_(labels.reshape(-1))
         if users is not None:
             self.users[self.n:self.n + b].copy_(users.reshape(-1))
+        if alpha is not None:
+            self.alpha[self.n:self.n + b].copy_(alpha.reshape(-1))
         self.n += b
 
 
-def compute(scores, hp, group, weighted, raw=None):
-    """-> dict of metrics (the union of what cal_metric(metrics), cal_metric(pairwise_metrics) and, when
-    ``weighted``, cal_weighted_metric(weighted_metrics) return).  Synchronises once.  ``raw`` (a dict) receives the
-    unrounded values (tests: a mean that sits exactly on a 4-decimal rounding boundary may round either way)."""
+def compute(scores, hp, group, weighted, raw=None, n_users=None, mean_alpha=False):
+    """-> dict of metrics (the union of what cal_metric(metrics), cal_metric(pairwise_metrics), when ``weighted``
+    cal_weighted_metric(weighted_metrics) and, when ``mean_alpha``, cal_mean_alpha_metric return).  Synchronises once.
+    ``n_users``: None for any non-negative int32 id; otherwise a STRICT upper bound of every user id (the size of the
+    user vocabulary) -- a precondition: the sort then looks at the low ``ceil(log2(n_users))`` bits only, and an id at
+    or above the bound would silently be grouped with another user.  ``raw`` (a dict) receives the unrounded values (tests: a mean that sits exactly on a
+    4-decimal rounding boundary may round either way); for ``rmse`` -- the root of the ROUNDED mean squared error, as in
+    the reference -- it receives the unrounded root and the mean squared error itself as ``mse``."""
     N, dev = scores.n, scores.device
     if N == 0 or N % group:
         raise ValueError("%d scored lines do not divide into groups of %d" % (N, group))
+    if mean_alpha and not scores.has_alpha:
+        raise ValueError("mean_alpha needs scores appended with an alpha column")
     pred, labels = scores.pred[:N], scores.labels[:N]
-    outd = torch.zeros(32, dtype=torch.float64, device=dev)      # [0] logloss | [1..] group metrics | [30] wauc
-    outu = torch.zeros(3, dtype=torch.int64, device=dev)
+    outd = torch.zeros(24, dtype=torch.float64, device=dev)      # [0] logloss | [1..] group metrics | [20..22] point sums
+    outw = torch.zeros(18, dtype=torch.float64, device=dev)      # wauc, wmrr, 8 x wndcg@k, 8 x whit@k
+    outu = torch.zeros(8, dtype=torch.int64, device=dev)         # [0..2] auc pair counts | [4..7] acc, TP, FP, FN
     cnt = torch.zeros(1, dtype=torch.int32, device=dev)
-    err = torch.zeros(2, dtype=torch.int32, device=dev)
+    err = torch.zeros(3, dtype=torch.int32, device=dev)          # groups | one-class users | users without a positive
     metrics = list(hp.metrics or [])
     if "logloss" in metrics:
         ops.call("clsr_eval_logloss", pred, labels, N, outd)
@@ -86,6 +119,8 @@ def compute(scores, hp, group, weighted, raw=None):
         pos = torch.empty(N, dtype=torch.float32, device=dev)
         ops.call("clsr_eval_compact_pos", pred, labels, N, pos, cnt)
         ops.call("clsr_eval_auc_pairs", pred, labels, N, pos, cnt, outu)
+    if mean_alpha or any(m in ("rmse", "acc", "f1") for m in metrics):
+        ops.call("clsr_eval_point_stats", pred, labels, scores.alpha[:N] if mean_alpha else None, N, outd[20:], outu[4:])
     pair = list(hp.pairwise_metrics or [])
     ks = sorted({k for m in pair if m.startswith("ndcg") or m.startswith("hit") for k in _ks(m)})
     if pair:
@@ -93,17 +128,26 @@ def compute(scores, hp, group, weighted, raw=None):
         ops.call("clsr_eval_group_metrics", pred, labels, N // group, group, ctypes.addressof(karr), len(ks),
                  1 if "group_auc" in pair else 0, outd[1:], err)
     wm = list(getattr(hp, "weighted_metrics", None) or []) if weighted else []
+    wks = _weighted_ks(wm)
+    if wks is None or len(wks) > MAX_K:
+        raise ValueError("no device form for the weighted metrics %r (see supported())" % (wm,))
     if wm:
-        users = scores.users[:N]
-        bits = ops.query("clsr_sort_ids_bits", 1 << 18)
-        nb = 1 << bits
-        counts = torch.zeros(nb, dtype=torch.int32, device=dev)
+        # lines grouped by user: keys ascending, equal keys in line order; then the list of segment starts, whose length
+        # (the number of distinct users) stays on the device
+        bits = 31 if n_users is None else min(31, max(1, (int(n_users) - 1).bit_length()))
         keys = torch.empty(N, dtype=torch.int32, device=dev)
         perm = torch.empty(N, dtype=torch.int32, device=dev)
-        ops.sort_ids_multi([(users.data_ptr(), keys.data_ptr(), perm.data_ptr(), counts.data_ptr(), N, 1, 1, bits)])
-        ops.call("clsr_eval_user_auc", pred, labels, perm, counts, nb, N, outd[30:], err[1:])
-    d, u, c, e = outd.cpu().tolist(), outu.cpu().tolist(), int(cnt.cpu()), err.cpu().tolist()   # the one sync
-    res = {}
+        ws = torch.empty(ops.query("clsr_sort_ids_stable_workspace_bytes", N, 1), dtype=torch.uint8, device=dev)
+        ops.sort_ids_stable_multi([(scores.users[:N].data_ptr(), keys.data_ptr(), perm.data_ptr(), N, 1, 1, bits)], ws)
+        starts = torch.empty(N, dtype=torch.int32, device=dev)
+        nseg = torch.zeros(1, dtype=torch.int32, device=dev)
+        ops.call("clsr_eval_user_segments", keys, N, starts, nseg)
+        wkarr = (ctypes.c_int * max(len(wks), 1))(*wks)
+        ops.call("clsr_eval_user_metrics", pred, labels, perm, keys, starts, nseg, N, ctypes.addressof(wkarr), len(wks),
+                 1 if "wauc" in wm else 0, 1 if any(m != "wauc" for m in wm) else 0, outw, err[1:])
+    d, w, u, c, e = (outd.cpu().tolist(), outw.cpu().tolist(), outu.cpu().tolist(), int(cnt.cpu()),
+                     err.cpu().tolist())                          # the one sync
+    res, final = {}, {}
     for m in metrics:
         if m == "auc":
             if c == 0 or u[2] == 0:
@@ -111,6 +155,16 @@ def compute(scores, hp, group, weighted, raw=None):
             res["auc"] = (u[0] + 0.5 * u[1]) / (float(c) * float(u[2]))
         elif m == "logloss":
             res["logloss"] = d[0] / N
+        elif m == "rmse":
+            mse = d[20] / N
+            final["rmse"] = math.sqrt(round(mse, 4))
+            if raw is not None:
+                raw.update(rmse=math.sqrt(mse), mse=mse)
+        elif m == "acc":
+            res["acc"] = u[4] / float(N)
+        elif m == "f1":
+            den = 2.0 * u[5] + u[6] + u[7]
+            res["f1"] = u[5] * 2.0 / den if den > 0 else 0.0
     ng = N // group
     if pair and e[0]:
         raise ValueError("%d groups without a positive (or, for group_auc, without a negative) line" % e[0])
@@ -125,10 +179,23 @@ def compute(scores, hp, group, weighted, raw=None):
         elif m.startswith("hit"):
             for k in _ks(m):
                 res["hit@{0}".format(k)] = d[3 + len(ks) + ks.index(k)] / ng
-    if wm:
-        if e[1]:
-            raise ValueError("Only one class present in y_true. ROC AUC score is not defined in that case.")
-        res["wauc"] = d[30]
+    nan = float("nan") if e[2] else None       # a user without a positive line: the reference's mrr / ndcg are 0 / 0 there
+    for m in wm:
+        if m == "wauc":
+            if e[1]:
+                raise ValueError("Only one class present in y_true. ROC AUC score is not defined in that case.")
+            res["wauc"] = w[0]
+        elif m == "wmrr":
+            res["wmrr"] = w[1] if nan is None else nan
+        elif m.startswith("wndcg"):
+            for k in _ks(m):
+                res["wndcg@{0}".format(k)] = w[2 + wks.index(k)] if nan is None else nan
+        elif m.startswith("whit"):
+            for k in _ks(m):
+                res["whit@{0}".format(k)] = w[2 + MAX_K + wks.index(k)]
+    if mean_alpha:
+        res["mean_alpha"] = d[21] / d[22] if d[22] else float("nan")
     if raw is not None:
         raw.update(res)
-    return {k: round(v, 4) for k, v in res.items()}
+    final.update((k, round(v, 4)) for k, v in res.items())
+    return final

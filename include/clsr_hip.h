@@ -954,17 +954,38 @@ int clsr_table_tf_rows(int opt, float* table, float* grad_table, float* s1, floa
 
 /* ---- evaluation metrics on the device (csrc/metrics.hip): cal_metric / cal_weighted_metric of
  *      deeprec_utils.py:554-821 as SequentialBaseModel.run_eval / run_weighted_eval use them
- *      (sequential_base_model.py:204-292), by exact pair / rank COUNTING (no sort).  The double accumulators (out) must be
- *      ZERO on entry and hold the final sums on return: block partials are added as 64-bit fixed-point integers, so the
- *      result does not depend on the order in which blocks finish (bit-identical from run to run).  Rank ties inside a group: the later line ranks first (stable ascending sort read backwards). */
+ *      (sequential_base_model.py:204-292), by exact pair / rank COUNTING (no sort of the scores).  The double
+ *      accumulators (out) must be ZERO on entry and hold the final sums on return: block partials are added as 64-bit
+ *      fixed-point integers, so the result does not depend on the order in which blocks finish (bit-identical from run
+ *      to run).  Rank ties inside a group or a user: the later line ranks first (stable ascending sort read backwards). */
 int clsr_eval_logloss(const float* pred, const float* labels, long N, double* out, void* stream);
 int clsr_eval_compact_pos(const float* pred, const float* labels, long N, float* pos_out, int* count, void* stream);
 int clsr_eval_auc_pairs(const float* pred, const float* labels, long N, const float* pos, const int* count,
                         void* out_u64x3, void* stream);
 int clsr_eval_group_metrics(const float* pred, const float* labels, long n_groups, int G, const int* ks_host, int nk,
                             int want_auc, double* out, int* err, void* stream);
+/* wauc over the segments of a COUNTING sort (clsr_sort_ids_multi: ends = its bucket end offsets; exact only while every
+ * bucket holds one user, i.e. ids below 2^18); the Python layer groups with the stable sort below instead */
 int clsr_eval_user_auc(const float* pred, const float* labels, const int* perm, const int* ends, int nb, long N,
                        double* out, int* err, void* stream);
+/* user segments of the line list sorted by user id (keys / perm of clsr_sort_ids_stable_multi on the user column, any
+ * non-negative int32 id): starts[0 .. count[0]) = the entries e with e == 0 or keys[e] != keys[e - 1], in any order.
+ * count[0] ZERO on entry; starts holds N ints.  The number of users stays on the device.  N < 2^31 - 2048. */
+int clsr_eval_user_segments(const int* keys, long N, int* starts, int* count, void* stream);
+/* user-weighted metrics in one launch, one wave per segment, w = n_u / N: out[0] += w roc_auc(u) (want_auc); with
+ * want_rank out[1] += w mrr(u), out[2 + i] += w ndcg@ks[i](u), out[10 + i] += w hit@ks[i](u) (nk <= 8 distinct k > 0;
+ * out: 18 doubles).
+ * The rank of a positive line counts the user's lines with a greater score, or an equal score and a greater line index
+ * (perm).  err[0] += users whose lines are all one class (want_auc), err[1] += users without a positive line: they add
+ * nothing to out[1 ..], where the reference yields NaN for mrr / ndcg.  No wave waits for another; 3 KB of LDS. */
+int clsr_eval_user_metrics(const float* pred, const float* labels, const int* perm, const int* keys, const int* starts,
+                           const int* count, long N, const int* ks_host, int nk, int want_auc, int want_rank,
+                           double* out, int* err, void* stream);
+/* one reduction over all lines: out_d3 += {sum (label - pred)^2, sum alpha * label, sum label} (the last two only when
+ * alpha is given), out_u64x4 += {#((pred >= 0.5) == label), TP, FP, FN at 0.5} -- rmse, acc, f1, mean_alpha.  pred in
+ * [0, 1] (sigmoid outputs): the sums are kept in 2^-32 fixed point. */
+int clsr_eval_point_stats(const float* pred, const float* labels, const float* alpha, long N, double* out_d3,
+                          void* out_u64x4, void* stream);
 
 /* ---- host-side (no GPU) replay of CPython's random module for the input pipeline: continue the MT19937 stream of
  *      random.getstate() through random.shuffle / the in-batch negative sampling of io/sequential_iterator.py:249-261,
