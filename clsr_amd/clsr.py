@@ -164,15 +164,22 @@ class BaseModel(object):
 class SequentialBaseModel(BaseModel):
     def __init__(self, hparams, iterator_creator, graph=None, seed=None, device="cuda:0", use_graph=False,
                  dedup_histories=True, dist=None, sync_bn=True, group=None, precision="fp32", table_dtype="fp32",
-                 table_master=False):
+                 table_master=False, shard_eval=False):
         """Reference ``SequentialBaseModel.__init__`` (:19-48): requires ``train_num_ngs``.
 
         ``dist`` (an initialised ``torch.distributed`` module, one process per GPU) turns ``train`` / ``fit``
         into single-node data parallelism: every rank iterates the SAME global batches (same files, same
         ``random`` seed -- the in-batch negative sampling runs over the global batch like in the reference),
         trains on its contiguous share of the positives and exchanges gradients through
-        :class:`clsr_amd.dp.DataParallel`; ``hparams.batch_size`` is the GLOBAL batch.  Evaluation is
-        replicated (every rank scores the whole file and gets the same metrics)."""
+        :class:`clsr_amd.dp.DataParallel`; ``hparams.batch_size`` is the GLOBAL batch.
+
+        Evaluation is replicated by default (every rank scores the whole file and gets the same metrics).  With
+        ``shard_eval=True`` (and ``dist``) the ranks share it: every rank still iterates the whole file, but scores
+        only its own chunks of lines, the scores are exchanged so that every rank holds all lines in file order, and
+        each rank runs its share of every metric kernel; the integer accumulators are summed across the ranks, so
+        ``run_eval`` / ``run_weighted_eval`` / ``fit`` return on every rank exactly the dict a single process
+        returns.  The host-metric fallbacks stay replicated.  ``eval_rows_scored``: the lines THIS rank scored in
+        the last evaluation on the device."""
         self.hparams = hparams
         self.need_sample = hparams.need_sample
         self.train_num_ngs = hparams.train_num_ngs
@@ -185,6 +192,8 @@ class SequentialBaseModel(BaseModel):
         self._precision = precision
         self._table_dtype = table_dtype      # "bf16": embedding tables stored as bf16 (CLSRNet(table_dtype=...))
         self._table_master = bool(table_master)     # ... with an exact fp32 master kept as optimiser state (table_master=...)
+        self._shard_eval = bool(shard_eval) and dist is not None
+        self.eval_rows_scored = 0
         self.dp_dropped_positives = self.dp_skipped_batches = 0
         self._use_graph = use_graph and dist is None
         self._dedup = dedup_histories
@@ -487,8 +496,28 @@ class SequentialBaseModel(BaseModel):
             return None
         with self._stream_ctx():
             acc = DM.DeviceScores(self.net.device)
+            part = reduce = None
+            if self._shard_eval:
+                # chunk by chunk the ranks agree on an owner (they iterate the same file); the others keep zeros at the
+                # chunk's lines, and ONE integer sum over the ranks puts every line on every rank, in file order
+                dist, grp = self._dist, self._group
+                part = (dist.get_rank(grp), dist.get_world_size(grp))
+                loads = [0] * part[1]
+
+                def reduce(tensors):
+                    for t in tensors:
+                        dist.all_reduce(t, op=dist.ReduceOp.SUM, group=grp)
+            self.eval_rows_scored = 0
 
             def score(feeds):
+                n = sum(int(np.asarray(x["labels"]).shape[0]) for x in feeds)
+                if part is not None:
+                    owner = DM.chunk_owner(loads)
+                    loads[owner] += n
+                    if owner != part[0]:
+                        acc.append_zeros(n, mean_alpha)
+                        return
+                self.eval_rows_scored += n
                 feed = feeds[0] if len(feeds) == 1 else {
                     k: (v if k == "hist_group" else np.concatenate([np.asarray(x[k]) for x in feeds], axis=0))
                     for k, v in feeds[0].items()}
@@ -517,8 +546,10 @@ class SequentialBaseModel(BaseModel):
                     pend, rows = [], 0
             if pend:
                 score(pend)
+            if part is not None and acc.n:
+                acc.merge(reduce)
             return DM.compute(acc, self.hparams, num_ngs + 1, weighted, n_users=self.user_vocab_length,
-                              mean_alpha=mean_alpha)
+                              mean_alpha=mean_alpha, part=part, reduce=reduce)
 
     def run_eval(self, filename, num_ngs):
         """auc/logloss + pairwise metrics over groups of ``num_ngs + 1`` lines

@@ -36,6 +36,23 @@ __global__ void fx_finalize_kernel(double* out, int n, double inv_scale) {
 static void fx_finalize(double* out, int n, double scale, hipStream_t s) {
   hipLaunchKernelGGL(fx_finalize_kernel, dim3(1), dim3(64), 0, s, out, n, 1.0 / scale);
 }
+// ---- partial forms (evaluation sharded over data-parallel ranks): `*_part(part, nparts)` does one share of the work
+// over the same full arrays and leaves every accumulator -- fixed-point slots, pair counts, `err` counters (64-bit in
+// this form) -- as a raw integer; the shares of all parts, added as integers, are the bits the whole entry leaves
+// before its own conversion, and clsr_eval_finalize converts them once.  A kernel that rounds ONE sum per block (or per
+// wave) to fixed point keeps its grid: part p runs the blocks [blocks p / nparts, blocks (p + 1) / nparts) of the
+// whole launch (vb0 = the first of them, vgrid = blocks), so every block meets the elements it meets in the whole
+// launch and rounds the same partial sum.  A part without a block launches nothing.
+static inline void part_blocks(int blocks, int part, int nparts, int* vb0, int* nb) {
+  *vb0 = (int)((long)blocks * part / nparts);
+  *nb = (int)((long)blocks * (part + 1) / nparts) - *vb0;
+}
+#define CLSR_CHECK_PART() CLSR_CHECK_ARG(nparts > 0 && part >= 0 && part < nparts)
+// err counters: int32 in the whole entries (their ABI), 64-bit slots of the packed accumulator in the partial ones
+__device__ __forceinline__ void err_add(int* err, int i, int v, int wide) {
+  if (wide) atomicAdd(reinterpret_cast<u64*>(err) + i, (u64)v);
+  else atomicAdd(err + i, v);
+}
 #define FX_LOGLOSS 67108864.0              // 2^26: the sum is at most 27 N (N < 2^31 lines)
 #define FX_GROUP 1073741824.0              // 2^30: sums of per-group values in [0, 1]
 #define FX_WAUC 1152921504606846976.0      // 2^60: the weighted sum is at most 1
@@ -46,10 +63,10 @@ static void fx_finalize(double* out, int n, double scale, hipStream_t s) {
 // out[0] = sum over lines of -(y log p + (1 - y) log(1 - p)), p clipped to [1e-11, 1 - 1e-11] (cal_metric "logloss")
 __global__ void __launch_bounds__(256) eval_logloss_kernel(const float* __restrict__ pred,
                                                            const float* __restrict__ labels, long N,
-                                                           double* __restrict__ out) {
+                                                           double* __restrict__ out, int vb0, int vgrid) {
   __shared__ double red[4];
   double s = 0.0;
-  for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < N; e += (long)gridDim.x * 256) {
+  for (long e = (long)(vb0 + blockIdx.x) * 256 + threadIdx.x; e < N; e += (long)vgrid * 256) {
     const double p = clip_d((double)pred[e], 10e-12, 1.0 - 10e-12);
     const double y = (double)labels[e];
     s -= y * log(p) + (1.0 - y) * log(1.0 - p);
@@ -58,12 +75,27 @@ __global__ void __launch_bounds__(256) eval_logloss_kernel(const float* __restri
   if (threadIdx.x == 0) fx_add(out, s, FX_LOGLOSS);
 }
 
+static void logloss_launch(const float* pred, const float* labels, long N, int part, int nparts, double* out,
+                           hipStream_t s) {
+  int blocks = clsr_cdiv(N, 256 * 8), vb0, nb;
+  if (blocks > 2048) blocks = 2048;
+  part_blocks(blocks, part, nparts, &vb0, &nb);
+  if (nb > 0) hipLaunchKernelGGL(eval_logloss_kernel, dim3(nb), dim3(256), 0, s, pred, labels, N, out, vb0, blocks);
+}
+
 extern "C" int clsr_eval_logloss(const float* pred, const float* labels, long N, double* out, void* stream) {
   CLSR_CHECK_ARG(pred && labels && out && N > 0);
-  int blocks = clsr_cdiv(N, 256 * 8);
-  if (blocks > 2048) blocks = 2048;
-  hipLaunchKernelGGL(eval_logloss_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, pred, labels, N, out);
+  logloss_launch(pred, labels, N, 0, 1, out, (hipStream_t)stream);
   fx_finalize(out, 1, FX_LOGLOSS, (hipStream_t)stream);
+  CLSR_CHECK_LAUNCH();
+  return CLSR_OK;
+}
+
+extern "C" int clsr_eval_logloss_part(const float* pred, const float* labels, long N, int part, int nparts, void* acc,
+                                      void* stream) {
+  CLSR_CHECK_ARG(pred && labels && acc && N > 0);
+  CLSR_CHECK_PART();
+  logloss_launch(pred, labels, N, part, nparts, (double*)acc, (hipStream_t)stream);
   CLSR_CHECK_LAUNCH();
   return CLSR_OK;
 }
@@ -102,12 +134,13 @@ extern "C" int clsr_eval_compact_pos(const float* pred, const float* labels, lon
 __global__ void __launch_bounds__(256) eval_auc_pairs_kernel(const float* __restrict__ pred,
                                                              const float* __restrict__ labels, long N,
                                                              const float* __restrict__ pos,
-                                                             const int* __restrict__ count, u64* __restrict__ out) {
+                                                             const int* __restrict__ count, u64* __restrict__ out,
+                                                             int vb0, int vgrid) {
   __shared__ float ps[AUC_PT];
   __shared__ u64 red[3][4];
   const int P = count[0];
   u64 gt = 0, eq = 0, nneg = 0;
-  for (long e0 = (long)blockIdx.x * (256 * AUC_NPT); e0 < N; e0 += (long)gridDim.x * (256 * AUC_NPT)) {
+  for (long e0 = (long)(vb0 + blockIdx.x) * (256 * AUC_NPT); e0 < N; e0 += (long)vgrid * (256 * AUC_NPT)) {
     float s[AUC_NPT];
     bool neg[AUC_NPT];
 #pragma unroll
@@ -150,11 +183,20 @@ __global__ void __launch_bounds__(256) eval_auc_pairs_kernel(const float* __rest
 
 extern "C" int clsr_eval_auc_pairs(const float* pred, const float* labels, long N, const float* pos,
                                    const int* count, void* out_u64x3, void* stream) {
-  CLSR_CHECK_ARG(pred && labels && pos && count && out_u64x3 && N > 0);
-  int blocks = clsr_cdiv(N, 256 * AUC_NPT);
+  return clsr_eval_auc_pairs_part(pred, labels, N, pos, count, 0, 1, out_u64x3, stream);
+}
+
+// pos / count: ALL positives of the file (every part compacts them itself); the part counts the pairs of its own lines
+extern "C" int clsr_eval_auc_pairs_part(const float* pred, const float* labels, long N, const float* pos,
+                                        const int* count, int part, int nparts, void* acc_u64x3, void* stream) {
+  CLSR_CHECK_ARG(pred && labels && pos && count && acc_u64x3 && N > 0);
+  CLSR_CHECK_PART();
+  int blocks = clsr_cdiv(N, 256 * AUC_NPT), vb0, nb;
   if (blocks > 4096) blocks = 4096;
-  hipLaunchKernelGGL(eval_auc_pairs_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, pred, labels, N, pos,
-                     count, (u64*)out_u64x3);
+  part_blocks(blocks, part, nparts, &vb0, &nb);
+  if (nb > 0)
+    hipLaunchKernelGGL(eval_auc_pairs_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, pred, labels, N, pos, count,
+                       (u64*)acc_u64x3, vb0, blocks);
   CLSR_CHECK_LAUNCH();
   return CLSR_OK;
 }
@@ -166,6 +208,7 @@ extern "C" int clsr_eval_auc_pairs(const float* pred, const float* labels, long 
 struct GroupMetricArgs {
   const float* pred; const float* labels; long n_groups; int G; int nk; int ks[GM_MAXK]; int want_auc;
   double* out; int* err;
+  int vb0, vgrid, err_wide;     // this launch = the blocks [vb0, vb0 + gridDim.x) of a launch of vgrid blocks (part_blocks)
 };
 
 __global__ void __launch_bounds__(256) eval_group_metrics_kernel(GroupMetricArgs a) {
@@ -178,7 +221,7 @@ __global__ void __launch_bounds__(256) eval_group_metrics_kernel(GroupMetricArgs
 #pragma unroll
   for (int i = 0; i < 2 + 2 * GM_MAXK; ++i) acc[i] = 0.0;
   int bad = 0;
-  for (long grp = (long)blockIdx.x * 4 + wave; grp < a.n_groups; grp += (long)gridDim.x * 4) {
+  for (long grp = (long)(a.vb0 + blockIdx.x) * 4 + wave; grp < a.n_groups; grp += (long)a.vgrid * 4) {
     const float* p = a.pred + grp * G;
     const float* l = a.labels + grp * G;
     for (int i = lane; i < G; i += 64) { sc[i] = p[i]; lb[i] = l[i]; }
@@ -239,23 +282,45 @@ __global__ void __launch_bounds__(256) eval_group_metrics_kernel(GroupMetricArgs
   if (lane == 0) {
     for (int i = 0; i < 2 + 2 * a.nk; ++i)
       if (acc[i] != 0.0) fx_add(a.out + i, acc[i], FX_GROUP);
-    if (bad) atomicAdd(a.err, bad);
+    if (bad) err_add(a.err, 0, bad, a.err_wide);
   }
+}
+
+static int group_metrics_launch(const float* pred, const float* labels, long n_groups, int G, const int* ks_host, int nk,
+                                int want_auc, int part, int nparts, double* out, int* err, int err_wide, hipStream_t s) {
+  CLSR_CHECK_ARG(pred && labels && out && err && n_groups > 0 && G > 0 && nk >= 0 && (nk == 0 || ks_host));
+  CLSR_CHECK_SUPPORTED(nk <= GM_MAXK && G <= 4096);
+  CLSR_CHECK_PART();
+  GroupMetricArgs a;
+  a.pred = pred; a.labels = labels; a.n_groups = n_groups; a.G = G; a.nk = nk; a.want_auc = want_auc;
+  a.out = out; a.err = err; a.err_wide = err_wide;
+  for (int i = 0; i < GM_MAXK; ++i) a.ks[i] = i < nk ? ks_host[i] : 0;
+  int blocks = clsr_cdiv(n_groups, 4), nb;
+  if (blocks > 4096) blocks = 4096;
+  a.vgrid = blocks;
+  part_blocks(blocks, part, nparts, &a.vb0, &nb);
+  if (nb > 0)
+    hipLaunchKernelGGL(eval_group_metrics_kernel, dim3(nb), dim3(256), (size_t)8 * G * sizeof(float), s, a);
+  return CLSR_OK;
 }
 
 extern "C" int clsr_eval_group_metrics(const float* pred, const float* labels, long n_groups, int G, const int* ks_host,
                                        int nk, int want_auc, double* out, int* err, void* stream) {
-  CLSR_CHECK_ARG(pred && labels && out && err && n_groups > 0 && G > 0 && nk >= 0 && (nk == 0 || ks_host));
-  CLSR_CHECK_SUPPORTED(nk <= GM_MAXK && G <= 4096);
-  GroupMetricArgs a;
-  a.pred = pred; a.labels = labels; a.n_groups = n_groups; a.G = G; a.nk = nk; a.want_auc = want_auc;
-  a.out = out; a.err = err;
-  for (int i = 0; i < GM_MAXK; ++i) a.ks[i] = i < nk ? ks_host[i] : 0;
-  int blocks = clsr_cdiv(n_groups, 4);
-  if (blocks > 4096) blocks = 4096;
-  hipLaunchKernelGGL(eval_group_metrics_kernel, dim3(blocks), dim3(256), (size_t)8 * G * sizeof(float),
-                     (hipStream_t)stream, a);
+  const int rc = group_metrics_launch(pred, labels, n_groups, G, ks_host, nk, want_auc, 0, 1, out, err, 0,
+                                      (hipStream_t)stream);
+  if (rc != CLSR_OK) return rc;
   fx_finalize(out, 2 + 2 * nk, FX_GROUP, (hipStream_t)stream);
+  CLSR_CHECK_LAUNCH();
+  return CLSR_OK;
+}
+
+// whole groups only: a group is never split.  acc: 2 + 2 nk slots, err_i64: one 64-bit counter
+extern "C" int clsr_eval_group_metrics_part(const float* pred, const float* labels, long n_groups, int G,
+                                            const int* ks_host, int nk, int want_auc, int part, int nparts, void* acc,
+                                            void* err_i64, void* stream) {
+  const int rc = group_metrics_launch(pred, labels, n_groups, G, ks_host, nk, want_auc, part, nparts, (double*)acc,
+                                      (int*)err_i64, 1, (hipStream_t)stream);
+  if (rc != CLSR_OK) return rc;
   CLSR_CHECK_LAUNCH();
   return CLSR_OK;
 }
@@ -384,6 +449,7 @@ struct UserMetricArgs {
   const float* pred; const float* labels; const int* perm; const int* keys; const int* starts; const int* count;
   long N; int nk; int ks[GM_MAXK];
   double* out; int* err;
+  int part, nparts;     // PART: the users with id % nparts == part -- the same users on every rank, whatever the order of starts
 };
 __device__ __forceinline__ u64 fx_wauc(double v) { return (u64)__double2ll_rn(v * FX_WAUC); }
 // s > t or (s == t and line_s > line_t)  <=>  um_key(s, line_s) > um_key(t, line_t)   (finite scores, -0 == +0)
@@ -399,7 +465,9 @@ __device__ __forceinline__ void um_wave_sync() {
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-template <bool AUC, bool RANK>
+// PART: the partial form (share of the users, 64-bit err counters); the whole entry keeps instances without it, so its
+// code -- one wave walks the heavy user's lines alone: every instruction of that loop shows -- is what it was
+template <bool AUC, bool RANK, bool PART>
 __global__ void __launch_bounds__(256) eval_user_metrics_kernel(UserMetricArgs a) {
   __shared__ float tn[4][64];   // tile: score of a NEGATIVE line, +inf for a positive one (hand-over: a positive's score)
   __shared__ u64 tk[4][64];     // tile: rank key of a line (hand-over: a positive's line)
@@ -415,6 +483,7 @@ __global__ void __launch_bounds__(256) eval_user_metrics_kernel(UserMetricArgs a
   for (long b = (long)blockIdx.x * 4 + wave; b < nseg; b += (long)gridDim.x * 4) {
     const int lo = __builtin_amdgcn_readfirstlane(a.starts[b]);      // (the same in every lane: scalar loop bounds)
     const int key = a.keys[lo];
+    if (PART && (unsigned)key % (unsigned)a.nparts != (unsigned)a.part) continue;
     int hi = (int)a.N;        // the segment ends at the first later entry with another key
     for (long i0 = (long)lo + 1; i0 < a.N; i0 += 64) {
       const long i = i0 + lane;
@@ -524,31 +593,60 @@ __global__ void __launch_bounds__(256) eval_user_metrics_kernel(UserMetricArgs a
 #pragma unroll
     for (int i = 0; i < 2 + 2 * GM_MAXK; ++i)
       if (acc[i]) atomicAdd(reinterpret_cast<u64*>(a.out) + i, acc[i]);
-    if (bad) atomicAdd(a.err, bad);
-    if (nopos) atomicAdd(a.err + 1, nopos);
+    if (bad) err_add(a.err, 0, bad, PART);
+    if (nopos) err_add(a.err, 1, nopos, PART);
   }
 }
 
-extern "C" int clsr_eval_user_metrics(const float* pred, const float* labels, const int* perm, const int* keys,
-                                      const int* starts, const int* count, long N, const int* ks_host, int nk,
-                                      int want_auc, int want_rank, double* out, int* err, void* stream) {
+static int user_metrics_launch(const float* pred, const float* labels, const int* perm, const int* keys,
+                               const int* starts, const int* count, long N, const int* ks_host, int nk, int want_auc,
+                               int want_rank, int part, int nparts, double* out, int* err, bool partial, hipStream_t s) {
   CLSR_CHECK_ARG(pred && labels && perm && keys && starts && count && out && err && N > 0 && nk >= 0 &&
                  (nk == 0 || ks_host) && (want_auc || want_rank) && (want_rank || nk == 0));
   CLSR_CHECK_SUPPORTED(nk <= GM_MAXK && N < (1L << 31) - 2048);
+  CLSR_CHECK_PART();
   UserMetricArgs a;
   a.pred = pred; a.labels = labels; a.perm = perm; a.keys = keys; a.starts = starts; a.count = count;
-  a.N = N; a.nk = nk; a.out = out; a.err = err;
+  a.N = N; a.nk = nk; a.out = out; a.err = err; a.part = part; a.nparts = nparts;
   for (int i = 0; i < GM_MAXK; ++i) {
     CLSR_CHECK_ARG(i >= nk || ks_host[i] > 0);
     a.ks[i] = i < nk ? ks_host[i] : 0;
   }
   int blocks = clsr_cdiv(N, 4);      // at most one wave per line: the number of users stays on the device
   if (blocks > 4096) blocks = 4096;
-  hipStream_t s = (hipStream_t)stream;
-  if (want_auc && want_rank) hipLaunchKernelGGL((eval_user_metrics_kernel<true, true>), dim3(blocks), dim3(256), 0, s, a);
-  else if (want_auc) hipLaunchKernelGGL((eval_user_metrics_kernel<true, false>), dim3(blocks), dim3(256), 0, s, a);
-  else hipLaunchKernelGGL((eval_user_metrics_kernel<false, true>), dim3(blocks), dim3(256), 0, s, a);
-  fx_finalize(out, 2 + 2 * GM_MAXK, FX_WAUC, s);
+#define UM_LAUNCH(AUC, RANK)                                                                                      \
+  do {                                                                                                            \
+    if (partial) hipLaunchKernelGGL((eval_user_metrics_kernel<AUC, RANK, true>), dim3(blocks), dim3(256), 0, s, a); \
+    else hipLaunchKernelGGL((eval_user_metrics_kernel<AUC, RANK, false>), dim3(blocks), dim3(256), 0, s, a);       \
+  } while (0)
+  if (want_auc && want_rank) UM_LAUNCH(true, true);
+  else if (want_auc) UM_LAUNCH(true, false);
+  else UM_LAUNCH(false, true);
+#undef UM_LAUNCH
+  return CLSR_OK;
+}
+
+extern "C" int clsr_eval_user_metrics(const float* pred, const float* labels, const int* perm, const int* keys,
+                                      const int* starts, const int* count, long N, const int* ks_host, int nk,
+                                      int want_auc, int want_rank, double* out, int* err, void* stream) {
+  const int rc = user_metrics_launch(pred, labels, perm, keys, starts, count, N, ks_host, nk, want_auc, want_rank, 0, 1,
+                                     out, err, false, (hipStream_t)stream);
+  if (rc != CLSR_OK) return rc;
+  fx_finalize(out, 2 + 2 * GM_MAXK, FX_WAUC, (hipStream_t)stream);
+  CLSR_CHECK_LAUNCH();
+  return CLSR_OK;
+}
+
+// the users whose id is `part` modulo nparts (keys / perm / starts cover ALL lines: the stable sort makes keys and perm
+// the same on every rank, the ORDER of starts is not -- so the share is a property of the user, not of a list position).
+// acc: 18 slots, err_i64x2: two 64-bit counters
+extern "C" int clsr_eval_user_metrics_part(const float* pred, const float* labels, const int* perm, const int* keys,
+                                           const int* starts, const int* count, long N, const int* ks_host, int nk,
+                                           int want_auc, int want_rank, int part, int nparts, void* acc,
+                                           void* err_i64x2, void* stream) {
+  const int rc = user_metrics_launch(pred, labels, perm, keys, starts, count, N, ks_host, nk, want_auc, want_rank, part,
+                                     nparts, (double*)acc, (int*)err_i64x2, true, (hipStream_t)stream);
+  if (rc != CLSR_OK) return rc;
   CLSR_CHECK_LAUNCH();
   return CLSR_OK;
 }
@@ -559,12 +657,13 @@ extern "C" int clsr_eval_user_metrics(const float* pred, const float* labels, co
 __global__ void __launch_bounds__(256) eval_point_stats_kernel(const float* __restrict__ pred,
                                                                const float* __restrict__ labels,
                                                                const float* __restrict__ alpha, long N,
-                                                               double* __restrict__ outd, u64* __restrict__ outu) {
+                                                               double* __restrict__ outd, u64* __restrict__ outu,
+                                                               int vb0, int vgrid) {
   __shared__ double red[3][4];
   __shared__ u64 redu[4][4];
   double s[3] = {0.0, 0.0, 0.0};
   u64 c[4] = {0, 0, 0, 0};
-  for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < N; e += (long)gridDim.x * 256) {
+  for (long e = (long)(vb0 + blockIdx.x) * 256 + threadIdx.x; e < N; e += (long)vgrid * 256) {
     const float p = pred[e], y = labels[e];
     const double d = (double)y - (double)p;
     s[0] += d * d;
@@ -596,15 +695,44 @@ __global__ void __launch_bounds__(256) eval_point_stats_kernel(const float* __re
   }
 }
 
-extern "C" int clsr_eval_point_stats(const float* pred, const float* labels, const float* alpha, long N, double* out_d3,
-                                     void* out_u64x4, void* stream) {
+static int point_stats_launch(const float* pred, const float* labels, const float* alpha, long N, int part, int nparts,
+                              double* out_d3, u64* out_u64x4, hipStream_t s) {
   CLSR_CHECK_ARG(pred && labels && out_d3 && out_u64x4 && N > 0);
   CLSR_CHECK_SUPPORTED(N < (1L << 31));
-  int blocks = clsr_cdiv(N, 256 * 8);
+  CLSR_CHECK_PART();
+  int blocks = clsr_cdiv(N, 256 * 8), vb0, nb;
   if (blocks > 2048) blocks = 2048;
-  hipLaunchKernelGGL(eval_point_stats_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, pred, labels, alpha, N,
-                     out_d3, (u64*)out_u64x4);
+  part_blocks(blocks, part, nparts, &vb0, &nb);
+  if (nb > 0)
+    hipLaunchKernelGGL(eval_point_stats_kernel, dim3(nb), dim3(256), 0, s, pred, labels, alpha, N, out_d3, out_u64x4,
+                       vb0, blocks);
+  return CLSR_OK;
+}
+
+extern "C" int clsr_eval_point_stats(const float* pred, const float* labels, const float* alpha, long N, double* out_d3,
+                                     void* out_u64x4, void* stream) {
+  const int rc = point_stats_launch(pred, labels, alpha, N, 0, 1, out_d3, (u64*)out_u64x4, (hipStream_t)stream);
+  if (rc != CLSR_OK) return rc;
   fx_finalize(out_d3, 3, FX_POINT, (hipStream_t)stream);
+  CLSR_CHECK_LAUNCH();
+  return CLSR_OK;
+}
+
+extern "C" int clsr_eval_point_stats_part(const float* pred, const float* labels, const float* alpha, long N, int part,
+                                          int nparts, void* acc_d3, void* acc_u64x4, void* stream) {
+  const int rc = point_stats_launch(pred, labels, alpha, N, part, nparts, (double*)acc_d3, (u64*)acc_u64x4,
+                                    (hipStream_t)stream);
+  if (rc != CLSR_OK) return rc;
+  CLSR_CHECK_LAUNCH();
+  return CLSR_OK;
+}
+
+// the conversion every whole entry ends with, on its own: n <= 64 raw fixed-point slots of scale `scale`
+// (CLSR_EVAL_FX_*) become doubles in place, after the shares of all parts have been added as integers
+extern "C" int clsr_eval_finalize(void* acc, int n, int scale, void* stream) {
+  CLSR_CHECK_ARG(acc && n > 0 && n <= 64 && scale >= 0 && scale <= 3);
+  const double scales[4] = {FX_LOGLOSS, FX_GROUP, FX_WAUC, FX_POINT};
+  fx_finalize((double*)acc, n, scales[scale], (hipStream_t)stream);
   CLSR_CHECK_LAUNCH();
   return CLSR_OK;
 }

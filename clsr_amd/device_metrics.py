@@ -9,7 +9,12 @@ lines); ``mean_mrr``, ``ndcg@k``, ``hit@k``, ``group_auc`` (groups of 1 + num_ng
 ``whit@k``, ``wndcg@k`` (per user: any non-negative int32 id, any number of users -- the lines are grouped with the stable
 radix sort of csrc/segsum.hip); ``mean_alpha``.  Rank ties break towards the later line of the file, in groups and in
 users alike.  What stays on the host (:func:`supported` returns False, the caller keeps clsr_amd/deeprec_utils.py): more
-than 8 distinct k over the pairwise or over the weighted metrics, and groups of more than ``MAX_GROUP`` lines."""
+than 8 distinct k over the pairwise or over the weighted metrics, and groups of more than ``MAX_GROUP`` lines.
+
+Sharded over data-parallel ranks (``SequentialBaseModel(shard_eval=True)``): :func:`plan_chunks` spreads the scoring
+chunks over the ranks, :meth:`DeviceScores.merge` gives every rank all lines in file order, and
+``compute(part=(rank, world), reduce=...)`` has every rank run its share of each metric kernel (the ``clsr_eval_*_part``
+entries), sums the raw integer accumulators across the ranks and converts them once: the same bits as one process."""
 import ctypes
 import math
 
@@ -53,6 +58,24 @@ def supported(hp, n_users, group):
     return wks is not None and len(wks) <= MAX_K and all(k > 0 for k in wks)
 
 
+def chunk_owner(loads):
+    """The rank that scores the next chunk, given the lines every rank has been handed so far: the one with the
+    fewest, the lowest rank on a tie.  The ranks iterate the same file, so they agree without talking."""
+    return min(range(len(loads)), key=lambda r: (loads[r], r))
+
+
+def plan_chunks(sizes, world):
+    """[(offset, size, owner)] for scoring chunks of ``sizes`` lines in file order: offsets are the chunks' global line
+    offsets, every chunk has one owner (:func:`chunk_owner`, applied chunk by chunk as the evaluation loop does)."""
+    loads, off, plan = [0] * world, 0, []
+    for n in sizes:
+        r = chunk_owner(loads)
+        plan.append((off, n, r))
+        loads[r] += n
+        off += n
+    return plan
+
+
 class DeviceScores(object):
     """Growing device buffers of (pred, label, user[, alpha]) per scored line; appends are stream-ordered copies.  The
     alpha column (the long / short fusion weight, for ``mean_alpha``) is allocated only when the batches carry one."""
@@ -92,41 +115,82 @@ class DeviceScores(object):
             self.alpha[self.n:self.n + b].copy_(alpha.reshape(-1))
         self.n += b
 
+    def append_zeros(self, b, with_alpha=False):
+        """``b`` lines that another rank scores: all-zero bits in every column, filled in by :meth:`merge`."""
+        if self.n and with_alpha != self.has_alpha:
+            raise ValueError("either every appended batch carries an alpha column or none does")
+        if self.n + b > self.cap or (with_alpha and self.alpha is None):
+            self._grow(self.n + b, with_alpha)
+        for col in (self.pred, self.labels, self.users, self.alpha):
+            if col is not None:
+                col[self.n:self.n + b].zero_()
+        self.n += b
 
-def compute(scores, hp, group, weighted, raw=None, n_users=None, mean_alpha=False):
+    def merge(self, reduce):
+        """Every line was appended by ONE rank and as zeros (:meth:`append_zeros`) by the others: ``reduce`` (sums a list
+        of integer device tensors across the ranks, in place) leaves all lines on every rank.  The columns travel as
+        int32 bit patterns in one buffer: a pattern plus zeros is that pattern, whatever float it encodes."""
+        cols = [c[:self.n] for c in (self.pred, self.labels, self.users, self.alpha) if c is not None]
+        packed = torch.cat([c.view(torch.int32) for c in cols])
+        reduce([packed])
+        for i, c in enumerate(cols):
+            c.view(torch.int32).copy_(packed[i * self.n:(i + 1) * self.n])
+
+
+# the partial forms' accumulators in ONE int64 buffer (one small collective): the slots of outd | outw | outu | err below
+_ACC_D, _ACC_W, _ACC_U, _ACC_E, _ACC_SLOTS = 0, 24, 42, 50, 53
+_FX_LOGLOSS, _FX_GROUP, _FX_USER, _FX_POINT = 0, 1, 2, 3      # CLSR_EVAL_FX_* (include/clsr_hip.h)
+
+
+def compute(scores, hp, group, weighted, raw=None, n_users=None, mean_alpha=False, part=None, reduce=None):
     """-> dict of metrics (the union of what cal_metric(metrics), cal_metric(pairwise_metrics), when ``weighted``
     cal_weighted_metric(weighted_metrics) and, when ``mean_alpha``, cal_mean_alpha_metric return).  Synchronises once.
     ``n_users``: None for any non-negative int32 id; otherwise a STRICT upper bound of every user id (the size of the
     user vocabulary) -- a precondition: the sort then looks at the low ``ceil(log2(n_users))`` bits only, and an id at
     or above the bound would silently be grouped with another user.  ``raw`` (a dict) receives the unrounded values (tests: a mean that sits exactly on a
     4-decimal rounding boundary may round either way); for ``rmse`` -- the root of the ROUNDED mean squared error, as in
-    the reference -- it receives the unrounded root and the mean squared error itself as ``mse``."""
+    the reference -- it receives the unrounded root and the mean squared error itself as ``mse``.
+    ``part=(rank, world)``: ``scores`` holds ALL lines on every rank (:meth:`DeviceScores.merge`); this rank runs share
+    ``rank`` of ``world`` of every metric kernel into raw integer accumulators, ``reduce([acc])`` (a callable that sums
+    int64 device tensors across the ranks in place; may be None for a world of one) is called once, and the sums are
+    converted once -- the dict, ``raw`` included, is the one ``part=None`` gives, to the bit, on every rank."""
     N, dev = scores.n, scores.device
     if N == 0 or N % group:
         raise ValueError("%d scored lines do not divide into groups of %d" % (N, group))
     if mean_alpha and not scores.has_alpha:
         raise ValueError("mean_alpha needs scores appended with an alpha column")
     pred, labels = scores.pred[:N], scores.labels[:N]
-    outd = torch.zeros(24, dtype=torch.float64, device=dev)      # [0] logloss | [1..] group metrics | [20..22] point sums
-    outw = torch.zeros(18, dtype=torch.float64, device=dev)      # wauc, wmrr, 8 x wndcg@k, 8 x whit@k
-    outu = torch.zeros(8, dtype=torch.int64, device=dev)         # [0..2] auc pair counts | [4..7] acc, TP, FP, FN
-    cnt = torch.zeros(1, dtype=torch.int32, device=dev)
-    err = torch.zeros(3, dtype=torch.int32, device=dev)          # groups | one-class users | users without a positive
+    if part is None:
+        outd = torch.zeros(24, dtype=torch.float64, device=dev)  # [0] logloss | [1..] group metrics | [20..22] point sums
+        outw = torch.zeros(18, dtype=torch.float64, device=dev)  # wauc, wmrr, 8 x wndcg@k, 8 x whit@k
+        outu = torch.zeros(8, dtype=torch.int64, device=dev)     # [0..2] auc pair counts | [4..7] acc, TP, FP, FN
+        err = torch.zeros(3, dtype=torch.int32, device=dev)      # groups | one-class users | users without a positive
+        sfx, share = "", ()
+    else:
+        rank, world = part
+        if not 0 <= rank < world or (world > 1 and reduce is None):
+            raise ValueError("part=(rank, world) with 0 <= rank < world, and a reduce for more than one rank")
+        acc = torch.zeros(_ACC_SLOTS, dtype=torch.int64, device=dev)      # the same slots, raw (err: 64-bit counters)
+        outd, outw, outu, err = acc[_ACC_D:_ACC_W], acc[_ACC_W:_ACC_U], acc[_ACC_U:_ACC_E], acc[_ACC_E:]
+        sfx, share = "_part", (rank, world)
+    cnt = torch.zeros(1, dtype=torch.int32, device=dev)           # positives of the file (every part counts them all)
     metrics = list(hp.metrics or [])
+    point = mean_alpha or any(m in ("rmse", "acc", "f1") for m in metrics)
     if "logloss" in metrics:
-        ops.call("clsr_eval_logloss", pred, labels, N, outd)
+        ops.call("clsr_eval_logloss" + sfx, pred, labels, N, *share, outd)
     if "auc" in metrics:
         pos = torch.empty(N, dtype=torch.float32, device=dev)
         ops.call("clsr_eval_compact_pos", pred, labels, N, pos, cnt)
-        ops.call("clsr_eval_auc_pairs", pred, labels, N, pos, cnt, outu)
-    if mean_alpha or any(m in ("rmse", "acc", "f1") for m in metrics):
-        ops.call("clsr_eval_point_stats", pred, labels, scores.alpha[:N] if mean_alpha else None, N, outd[20:], outu[4:])
+        ops.call("clsr_eval_auc_pairs" + sfx, pred, labels, N, pos, cnt, *share, outu)
+    if point:
+        ops.call("clsr_eval_point_stats" + sfx, pred, labels, scores.alpha[:N] if mean_alpha else None, N, *share,
+                 outd[20:], outu[4:])
     pair = list(hp.pairwise_metrics or [])
     ks = sorted({k for m in pair if m.startswith("ndcg") or m.startswith("hit") for k in _ks(m)})
     if pair:
         karr = (ctypes.c_int * max(len(ks), 1))(*ks)
-        ops.call("clsr_eval_group_metrics", pred, labels, N // group, group, ctypes.addressof(karr), len(ks),
-                 1 if "group_auc" in pair else 0, outd[1:], err)
+        ops.call("clsr_eval_group_metrics" + sfx, pred, labels, N // group, group, ctypes.addressof(karr), len(ks),
+                 1 if "group_auc" in pair else 0, *share, outd[1:], err)
     wm = list(getattr(hp, "weighted_metrics", None) or []) if weighted else []
     wks = _weighted_ks(wm)
     if wks is None or len(wks) > MAX_K:
@@ -143,10 +207,25 @@ def compute(scores, hp, group, weighted, raw=None, n_users=None, mean_alpha=Fals
         nseg = torch.zeros(1, dtype=torch.int32, device=dev)
         ops.call("clsr_eval_user_segments", keys, N, starts, nseg)
         wkarr = (ctypes.c_int * max(len(wks), 1))(*wks)
-        ops.call("clsr_eval_user_metrics", pred, labels, perm, keys, starts, nseg, N, ctypes.addressof(wkarr), len(wks),
-                 1 if "wauc" in wm else 0, 1 if any(m != "wauc" for m in wm) else 0, outw, err[1:])
-    d, w, u, c, e = (outd.cpu().tolist(), outw.cpu().tolist(), outu.cpu().tolist(), int(cnt.cpu()),
-                     err.cpu().tolist())                          # the one sync
+        ops.call("clsr_eval_user_metrics" + sfx, pred, labels, perm, keys, starts, nseg, N, ctypes.addressof(wkarr),
+                 len(wks), 1 if "wauc" in wm else 0, 1 if any(m != "wauc" for m in wm) else 0, *share, outw, err[1:])
+    if part is None:
+        d, w, u, c, e = (outd.cpu().tolist(), outw.cpu().tolist(), outu.cpu().tolist(), int(cnt.cpu()),
+                         err.cpu().tolist())                      # the one sync
+    else:
+        if reduce is not None:
+            reduce([acc])                                         # integer sums: the whole kernels' bits on every rank
+        if "logloss" in metrics:
+            ops.call("clsr_eval_finalize", outd, 1, _FX_LOGLOSS)
+        if pair:
+            ops.call("clsr_eval_finalize", outd[1:], 2 + 2 * len(ks), _FX_GROUP)
+        if point:
+            ops.call("clsr_eval_finalize", outd[20:], 3, _FX_POINT)
+        if wm:
+            ops.call("clsr_eval_finalize", outw, 18, _FX_USER)
+        host, c = acc.cpu(), int(cnt.cpu())                       # the one sync
+        d, w = host[_ACC_D:_ACC_W].view(torch.float64).tolist(), host[_ACC_W:_ACC_U].view(torch.float64).tolist()
+        u, e = host[_ACC_U:_ACC_E].tolist(), host[_ACC_E:].tolist()
     res, final = {}, {}
     for m in metrics:
         if m == "auc":

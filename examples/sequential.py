@@ -62,6 +62,8 @@ def get_flags():
     p.add_argument("--show_step", type=int, default=500)
     p.add_argument("--sample_rate", type=float, default=1.0)
     p.add_argument("--synthetic", action="store_true", help="generate a 1k-item synthetic slice first")
+    p.add_argument("--shard_eval", type=str2bool, default=False,
+                   help="data parallel only: the ranks share validation / test (same metrics, to the bit)")
     return p.parse_args()
 
 
@@ -87,7 +89,7 @@ def get_model(flags_obj, model_path, summary_path, user_vocab, item_vocab, cate_
             pairwise_metrics=pairwise_metrics, weighted_metrics=weighted_metrics, time_unit=time_unit, **extra)
         if dist is not None and dist.get_rank() != 0:
             hparams.save_model = False
-        return cls(hparams, SequentialIterator, seed=None, device=device, dist=dist)
+        return cls(hparams, SequentialIterator, seed=None, device=device, dist=dist, shard_eval=flags_obj.shard_eval)
     if flags_obj.model != "CLSR":
         raise SystemExit("--model must be CLSR, SLIREC, GRU4REC, DIN, DIEN or A2SVD (the other quick-start models do not share "
                          "this path's kernels; SURVEY.md section 2)")
@@ -107,7 +109,8 @@ def get_model(flags_obj, model_path, summary_path, user_vocab, item_vocab, cate_
         sequential_model=flags_obj.sequential_model, time_unit=time_unit)
     # data parallel: save_model stays on for EVERY rank -- CLSRModel.save_model is collective (rank 0 writes the
     # file atomically, then all ranks pass a barrier), so nobody loads a checkpoint that is still being written
-    return CLSRModel(hparams, SASequentialIterator, seed=None, device=device, dist=dist)
+    return CLSRModel(hparams, SASequentialIterator, seed=None, device=device, dist=dist,
+                     shard_eval=flags_obj.shard_eval)
 
 
 def init_data_parallel(flags_obj):

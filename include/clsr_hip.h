@@ -986,6 +986,32 @@ int clsr_eval_user_metrics(const float* pred, const float* labels, const int* pe
  * [0, 1] (sigmoid outputs): the sums are kept in 2^-32 fixed point. */
 int clsr_eval_point_stats(const float* pred, const float* labels, const float* alpha, long N, double* out_d3,
                           void* out_u64x4, void* stream);
+/* ---- partial forms: evaluation sharded over data-parallel ranks.  `*_part(part, nparts)` does the share `part` of
+ *      `nparts` of the work of the entry of the same name, over the SAME full arrays, and leaves every accumulator as a
+ *      raw 64-bit integer (fixed-point slots, pair counts; the err counters are 64-bit here as well, so that all of
+ *      them fit one int64 buffer).  The accumulators of all parts, added as integers (in one process, or by an integer
+ *      all-reduce across ranks), are exactly the bits the whole entry holds before its final conversion;
+ *      clsr_eval_finalize then converts the fixed-point slots, and the result equals the whole entry's bit for bit.
+ *      Shares: logloss / point statistics / the global AUC take a range of the whole launch's BLOCKS (the lines those
+ *      blocks read; pos / count of the AUC hold all positives of the file), group metrics a range of its blocks = whole
+ *      groups, user metrics the users with id % nparts == part (never a position in `starts`, whose order is not
+ *      defined).  A part without work launches nothing.  Accumulators ZERO on entry (of the first part). */
+int clsr_eval_logloss_part(const float* pred, const float* labels, long N, int part, int nparts, void* acc, void* stream);
+int clsr_eval_auc_pairs_part(const float* pred, const float* labels, long N, const float* pos, const int* count, int part,
+                             int nparts, void* acc_u64x3, void* stream);
+int clsr_eval_group_metrics_part(const float* pred, const float* labels, long n_groups, int G, const int* ks_host, int nk,
+                                 int want_auc, int part, int nparts, void* acc, void* err_i64, void* stream);
+int clsr_eval_user_metrics_part(const float* pred, const float* labels, const int* perm, const int* keys,
+                                const int* starts, const int* count, long N, const int* ks_host, int nk, int want_auc,
+                                int want_rank, int part, int nparts, void* acc, void* err_i64x2, void* stream);
+int clsr_eval_point_stats_part(const float* pred, const float* labels, const float* alpha, long N, int part, int nparts,
+                               void* acc_d3, void* acc_u64x4, void* stream);
+/* n <= 64 fixed-point slots -> doubles, in place; scale: which entry filled them */
+#define CLSR_EVAL_FX_LOGLOSS 0     /* clsr_eval_logloss_part: 1 slot */
+#define CLSR_EVAL_FX_GROUP 1       /* clsr_eval_group_metrics_part: 2 + 2 nk slots */
+#define CLSR_EVAL_FX_USER 2        /* clsr_eval_user_metrics_part: 18 slots */
+#define CLSR_EVAL_FX_POINT 3       /* clsr_eval_point_stats_part: acc_d3 */
+int clsr_eval_finalize(void* acc, int n, int scale, void* stream);
 
 /* ---- host-side (no GPU) replay of CPython's random module for the input pipeline: continue the MT19937 stream of
  *      random.getstate() through random.shuffle / the in-batch negative sampling of io/sequential_iterator.py:249-261,

@@ -1,6 +1,10 @@
 #!/usr/bin/env python
 """Throughput of the scoring / evaluation path: CLSRModel.run_weighted_eval and predict on a synthetic test
 file with 1 + 99 lines per positive (the reference's test protocol).   python scripts/eval_throughput.py [n_pos]
+[--shard_eval]
+
+--shard_eval measures the sharded evaluation path at a world of one (``shard_eval=True`` over a one-rank host-staged
+process group: the partial kernels, one reduce, the finalize launches) -- its overhead against the default path.
 
 CLSR_EVAL_WEIGHTED=wauc adds ``wauc`` to the metrics of config/clsr.yaml (which requests no user-weighted metric);
 CLSR_EVAL_WEIGHTED=all requests all four (wauc, wmrr, whit@k, wndcg@k) on a user vocabulary above 2^18 (400 000 train
@@ -20,7 +24,9 @@ from clsr_amd.synthetic import make_tsv_dataset  # noqa: E402
 
 
 def main():
-    n_pos = int(sys.argv[1]) if len(sys.argv) > 1 else 2000
+    args = [a for a in sys.argv[1:] if a != "--shard_eval"]
+    shard = len(args) != len(sys.argv) - 1
+    n_pos = int(args[0]) if args else 2000
     mode = os.environ.get("CLSR_EVAL_WEIGHTED", "")
     if mode not in ("", "wauc", "all"):
         raise SystemExit("CLSR_EVAL_WEIGHTED: wauc or all")
@@ -37,7 +43,22 @@ def main():
                          time_unit="s", contrastive_loss="triplet", contrastive_length_threshold=5, is_clip_norm=1,
                          embed_l2=1e-6, layer_l2=1e-6, discrepancy_loss_weight=0.01, contrastive_loss_weight=0.1,
                          show_step=10 ** 9, save_model=False, MODEL_DIR=None, epochs=1, **extra)
-    model = CLSRModel(hp, SASequentialIterator, seed=0)
+    kw = {}
+    if shard:
+        import socket
+
+        import torch.distributed as dist
+
+        from clsr_amd.dp import HostStagedDist
+
+        s = socket.socket()
+        s.bind(("127.0.0.1", 0))
+        os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
+        os.environ.setdefault("MASTER_PORT", str(s.getsockname()[1]))
+        s.close()
+        dist.init_process_group("gloo", rank=0, world_size=1)
+        kw = dict(dist=HostStagedDist(dist), shard_eval=True)
+    model = CLSRModel(hp, SASequentialIterator, seed=0, **kw)
     print("user vocabulary: %d, weighted metrics: %s" % (model.user_vocab_length, hp.weighted_metrics))
     rows = n_pos * 100
     t = time.perf_counter()
@@ -50,8 +71,11 @@ def main():
         dts.append(time.perf_counter() - t)
         assert res2 == res
     dt = min(dts)
-    print("run_weighted_eval: %.3f s for %d rows = %.0f rows/s (best of %s)" % (
-        dt, rows, rows / dt, " ".join("%.3f" % x for x in dts)))
+    print("run_weighted_eval%s: %.3f s for %d rows = %.0f rows/s (best of %s)" % (
+        " (shard_eval, one rank)" if shard else "", dt, rows, rows / dt, " ".join("%.3f" % x for x in dts)))
+    if shard:
+        assert model.eval_rows_scored == rows
+        return
     t = time.perf_counter()
     n = sum(1 for f in model.iterator.load_data_from_file(paths["test_data"], batch_num_ngs=0) if f)
     print("  iterator alone: %.3f s (%d batches)" % (time.perf_counter() - t, n))
