@@ -185,6 +185,7 @@ class DataParallel(object):
         self.overlap = bool(overlap)
         self.coalesce = True        # dense gradients + dense gradient tables in one collective (False: one each)
         net.dp_world = self.world
+        net.dp_rank = self.rank     # dropout masks are drawn by GLOBAL row: the ranks together draw the single-process masks
         # recorded launch plans keep raw communicator pointers: a new stepper on the same net must never replay the plans
         # of an earlier one (a freed communicator's address can be handed out again)
         net.dp_generation = getattr(net, "dp_generation", 0) + 1
@@ -273,6 +274,7 @@ class DataParallel(object):
         if hasattr(net, "_unused_tables"):
             tensors += [net.P[n] for n in net._unused_tables() if n in net.P]
         tensors.append(net.bn_moving)
+        tensors.append(getattr(net, "drop_state", None))      # seed and draw counter of the dropout masks
         tensors = [t for t in tensors if t is not None]     # (optimisers with fewer than two slots allocate fewer)
         for t in tensors:
             dist.broadcast(t, src=0, group=self.group)

@@ -133,6 +133,7 @@ class CLSRNet(object):
             raise ValueError("table_master=True keeps an fp32 master for bf16 tables: it needs table_dtype='bf16'")
         self._tu = "_hm" if self.table_master else self._th     # ... of the Adam updates of the tables
         self._check_supported()
+        self._dropout_setup(seed)
         self.optimizer = resolve_optimizer(hp.optimizer)
         # non-Adam optimisers: kernel code + slots (TF_OPTIMIZERS); None for (lazy)Adam
         self.tf_opt = TF_OPTIMIZERS.get(self.optimizer)
@@ -289,8 +290,7 @@ class CLSRNet(object):
             bad.append("enable_BN must be True")
         if list(hp.activation) != ["relu"] * len(hp.activation):
             bad.append("activation must be relu")
-        if any(float(d) != 0.0 for d in hp.dropout) or float(hp.embedding_dropout) != 0.0 or hp.user_dropout:
-            bad.append("dropout must be 0")
+        self._check_dropout(hp, bad, mlp_only=False)
         if any(float(getattr(hp, k)) != 0.0 for k in ("cross_l1", "cross_l2")):
             bad.append("cross regularisers must be 0 (no model of this family has cross-layer parameters)")
         if hp.loss != "softmax" or hp.method != "classification":
@@ -314,6 +314,45 @@ class CLSRNet(object):
                            "%d to be multiples of 8 (use precision='fp32')" % (att, qs, int(hp.hidden_size)))
         if bad:
             raise NotImplementedError("CLSR HIP path does not support: " + "; ".join(bad))
+
+    @staticmethod
+    def dropout_in_effect(hp):
+        """The reference drops (base_model.py: _active_layer) only when ``user_dropout`` is set, and ``tf.nn.dropout`` at
+        keep 1 is the identity: dropout is in effect when ``user_dropout`` is true and some ``dropout[i] > 0``."""
+        return bool(hp.user_dropout) and any(float(d) > 0.0 for d in (hp.dropout or ()))
+
+    @classmethod
+    def _check_dropout(cls, hp, bad, mlp_only):
+        """``mlp_only``: the model's one ``_fcn_net`` is the logit MLP (A2SVD, GRU4Rec), which has a dropout path
+        (``_mlp_fwd_drop``); every other model also runs its attention / alpha MLP through ``_fcn_net``, inside the fused
+        attention and heads kernels, which have none."""
+        rates = [float(d) for d in (hp.dropout or ())]
+        if any(not 0.0 <= d < 1.0 for d in rates):
+            raise ValueError("dropout values must lie in [0, 1), got %r" % (list(hp.dropout),))
+        if float(hp.embedding_dropout) != 0.0:
+            bad.append("embedding_dropout must be 0 (dropout of the embedding lookups: no reference config sets it)")
+        if cls.dropout_in_effect(hp):
+            if not mlp_only:
+                bad.append("user_dropout with dropout %r: dropout inside the attention MLP / alpha MLP is not implemented "
+                           "(only A2SVD and GRU4Rec, whose one _fcn_net is the logit MLP, train with dropout)" % (rates,))
+            elif len(rates) < len(hp.layer_sizes):
+                bad.append("dropout must hold one value per layer of layer_sizes")
+
+    def _dropout_setup(self, seed):
+        """Per-layer constants of the mask rule (csrc/philox.h) and the device-resident {seed low, seed high, draw, 0}."""
+        hp = self.hp
+        self.drop_on = self.dropout_in_effect(hp)
+        keeps = [1.0 - float(d) for d in hp.dropout] if self.drop_on else []
+        self.drop_thr = tuple(int(round(k * (1 << 24))) for k in keeps)              # kept <=> (word >> 8) < thr
+        self.drop_inv = tuple(float(np.float32(1.0 / k)) for k in keeps)
+        s = int.from_bytes(os.urandom(8), "little") if seed is None else int(seed) & ((1 << 64) - 1)
+        self.drop_state = torch.from_numpy(
+            np.array([s & 0xffffffff, s >> 32, 0, 0], dtype=np.uint32).view(np.int32).copy()).to(self.device)
+        self.dp_rank = 0           # data-parallel rank: the masks are drawn by GLOBAL row (clsr_amd/dp.py sets it)
+
+    def _dropout_state_host(self):
+        """(seed low, seed high, draw) as an int64 tensor: the checkpoint payload ``__dropout__/state``."""
+        return torch.from_numpy(self.drop_state.cpu().numpy().view(np.uint32)[:3].astype(np.int64))
 
     @staticmethod
     def _shape_limits(hp, rnn):
@@ -346,7 +385,7 @@ class CLSRNet(object):
                  "lazy", "use_plans", "heads_fused", "early_user_update", "fold_hist_shares", "enc_x6", "rnn_products", "rnn_fused_proj",
                  "rnn_act_tiled", "att_bwd", "att_bwd_l0", "_l1x", "_l0x", "bf16_chain", "dw_wide", "dw_wide_entry", "split_query",
                  "split_query_min", "rowlist_min_elems", "att_hist_bwd_pieces", "proj_gate_pieces", "proj_bwd_pieces",
-                 "proj_wide_pieces")
+                 "proj_wide_pieces", "drop_on", "drop_thr", "drop_inv", "dp_rank")
 
     def _plan_key(self, what, f):
         hp = self.hp
@@ -577,6 +616,8 @@ class CLSRNet(object):
         for scope, bn in self.bn.items():
             sd[scope + "moving_mean"] = bn.moving_mean.cpu().clone()
             sd[scope + "moving_variance"] = bn.moving_var.cpu().clone()
+        if self.drop_on:
+            sd["__dropout__/state"] = self._dropout_state_host()
         if self.tf_opt is not None:
             # __opt__/<optimizer>/dense_<slot>, __opt__/<optimizer>/<table>_<slot> (TF slot names), __opt__/state
             pre = "__opt__/%s/" % self.optimizer
@@ -631,6 +672,14 @@ class CLSRNet(object):
                 bn.moving_var.copy_(torch.as_tensor(np.asarray(sd[scope + "moving_variance"]), dtype=F32))
             elif strict:
                 raise KeyError(scope + "moving_mean")
+        if self.drop_on:
+            # seed and draw counter of the dropout masks; a checkpoint without them: this net's seed, draw 0
+            st = self.drop_state.cpu().numpy().view(np.uint32).copy()
+            if "__dropout__/state" in sd:
+                st[:3] = np.asarray(sd["__dropout__/state"]).astype(np.int64)[:3].astype(np.uint32)
+            else:
+                st[2] = 0
+            self.drop_state.copy_(torch.from_numpy(st.view(np.int32)))
         pre = "__opt__/%s/" % self.optimizer
         names = self._slot_names()
         if self.tf_opt is None and "__adam__/dense_m" in sd:
@@ -1736,6 +1785,73 @@ class CLSRNet(object):
         if not (key == "lg" and self._step.defer_logit_out):   # (training step: the logits come out of clsr_mlp_tail_softmax)
             call("clsr_mlp_out_fwd", z1, bn1.scale, bn1.shift, P[nn + "w_nn_output"], P[nn + "b_nn_output"], B, C1, logit)
         return logit
+
+    def _drop_args(self, layer, B):
+        """state, layer, first GLOBAL row of this rank's shard, threshold, 1 / keep of hidden layer ``layer``."""
+        return (self.drop_state, layer, self.dp_rank * B if self.dp_world > 1 else 0, self.drop_thr[layer],
+                self.drop_inv[layer])
+
+    def _mlp_fwd_drop(self, key, nn, X, ldx, K0, sizes, B):
+        """``_mlp_fwd`` of a TRAINING step with dropout in effect (base_model.py _active_layer: relu(dropout(bn(z)))): the
+        dropped activations a0 / a1 are materialised by csrc/dropout.hip, the next product reads them as they are, and the
+        output layer is the row dot of clsr_mlp_out_fwd with a unit affine (a1 * 1 + 0 = a1 >= 0: exact)."""
+        P = self.P
+        C0, C1 = sizes
+        bn0, bn1 = self.bn[nn + "batch_normalization/"], self.bn[nn + "batch_normalization_1/"]
+        z0, z1 = self._buf(key + ".z0", B, C0), self._buf(key + ".z1", B, C1)
+        a0, a1 = self._buf(key + ".a0", B, C0), self._buf(key + ".a1", B, C1)
+        logit = self._buf(key + ".logit", B)
+        parts = query("clsr_pgemm_stats_parts", B)
+        st = self._stats_buf(parts, C0)
+        self._gemm(X, ldx, key + ".W0", B, K0, C0, z0, C0, bias=P[nn + "b_nn_layer0"], stats=st)
+        self._bn_fwd(bn0, st, parts, B, True)
+        call("clsr_bn_relu_dropout_fwd", z0, bn0.scale, bn0.shift, *self._drop_args(0, B), B, C0, a0)
+        st = self._stats_buf(parts, C1)
+        self._gemm(a0, C0, key + ".W1", B, C0, C1, z1, C1, bias=P[nn + "b_nn_layer1"], stats=st)
+        self._bn_fwd(bn1, st, parts, B, True)
+        call("clsr_bn_relu_dropout_fwd", z1, bn1.scale, bn1.shift, *self._drop_args(1, B), B, C1, a1)
+        one, zero = self._unit_affine(C1)
+        call("clsr_mlp_out_fwd", a1, one, zero, P[nn + "w_nn_output"], P[nn + "b_nn_output"], B, C1, logit)
+        return logit
+
+    def _unit_affine(self, C):
+        one = self._bufs.get(("drop.one", C))
+        if one is None:
+            one = self._bufs[("drop.one", C)] = torch.ones(C, dtype=F32, device=self.device)
+        return one, self._buf("drop.zero", C)
+
+    def _mlp_bwd_drop(self, key, nn, dlogit, X, ldx, K0, K0_real, sizes, B):
+        """Mirror of ``_mlp_fwd_drop``; returns dX [B, K0].  The masks are drawn again (never stored); the batch-norm
+        sums leave the dropout backward kernel in the layout ``_bn_bwd_from_partial`` reads."""
+        P, Gd = self.P, self.Gd
+        C0, C1 = sizes
+        bn0, bn1 = self.bn[nn + "batch_normalization/"], self.bn[nn + "batch_normalization_1/"]
+        z0, z1 = self._buf(key + ".z0", B, C0), self._buf(key + ".z1", B, C1)
+        a0, a1 = self._buf(key + ".a0", B, C0), self._buf(key + ".a1", B, C1)
+        dz1, dz0 = self._buf(key + ".dz1", B, C1), self._buf(key + ".dz0", B, C0)
+        # output layer: d a1 = dlogit * w_out where a1 > 0 (the mask and the ReLU gate of the dropout backward cover the
+        # same elements, so gating early changes nothing), d w_out / d b_out partial rows; its batch-norm sums are unused
+        parts = query("clsr_mlp_out_bwd_parts", B, C1)
+        one, zero = self._unit_affine(C1)
+        junk = self._buf("drop.bnp_unused", parts * 2 * C1, dtype=torch.float64)
+        wp = self._buf("mlp.wp." + key, 512 * (256 + 4))[: parts * (C1 + 4)] if C1 <= 256 else \
+            self._buf("mlp.wpw." + key, parts * (C1 + 4))
+        call("clsr_mlp_out_bwd", dlogit, a1, one, zero, zero, one, P[nn + "w_nn_output"], B, C1, dz1, junk, wp)
+        self._rp(wp, parts, C1 + 4, C1, Gd[nn + "w_nn_output"])
+        self._rp(wp[C1:], parts, C1 + 4, 1, Gd[nn + "b_nn_output"])
+        for layer, bn, C, z, dz in ((1, bn1, C1, z1, dz1), (0, bn0, C0, z0, dz0)):
+            if layer == 0:
+                self._dw(a0, C0, dz1, C1, B, C0, C1, Gd[nn + "w_nn_layer1"], C1, db=Gd[nn + "b_nn_layer1"])
+                self._gemm(dz1, C1, key + ".W1^T", B, C1, C0, dz0, C0)
+            parts = query("clsr_bn_relu_dropout_bwd_parts", B, C)
+            bnp = self._buf("drop.bnp%d" % layer, parts * 2 * C, dtype=torch.float64)
+            call("clsr_bn_relu_dropout_bwd", dz, z, bn.scale, bn.shift, bn.mean, bn.invstd, *self._drop_args(layer, B),
+                 B, C, dz, bnp)
+            self._bn_bwd_from_partial(bn, bnp, parts, dz, z, B)
+        self._dw(X, ldx, dz0, C0, B, K0_real, C0, Gd[nn + "w_nn_layer0"], C0, db=Gd[nn + "b_nn_layer0"])
+        dX = self._buf(key + ".dX", B, K0)
+        self._gemm(dz0, C0, key + ".W0^T", B, C0, K0, dX, K0)
+        return dX
 
     def _mlp_bwd(self, key, nn, dlogit, X, ldx, K0, K0_real, sizes, B, tail=None):
         """Returns dX [B, K0] (K0 = padded input width).  ``tail = (labels, groups, rows per group, loss scale)``: the

@@ -16,6 +16,9 @@ clip + Adam) and differ in ``_build_seq_graph``:
 launch, the attention block (forward and backward), the MLP heads, sorted segmented embedding gradients, regularisers,
 clip, Adam, the stream structure, data parallelism -- and only re-states the three graphs and their backward passes.
 New device code: the A2SVD attention and the length scaling of DIN's history sum (csrc/sibling.hip).
+
+A2SVD and GRU4Rec, whose one ``_fcn_net`` is the logit MLP, also train with the config's dropout (``user_dropout``,
+``dropout``: csrc/dropout.hip, ``CLSRNet._mlp_fwd_drop``); the other three refuse it by name.
 """
 import numpy as np
 import torch
@@ -46,8 +49,7 @@ class SeqNet(CLSRNet):
             bad.append("enable_BN must be True")
         if list(hp.activation) != ["relu"] * len(hp.activation):
             bad.append("activation must be relu")
-        if any(float(d) != 0.0 for d in hp.dropout) or float(hp.embedding_dropout) != 0.0 or hp.user_dropout:
-            bad.append("dropout must be 0")
+        self._check_dropout(hp, bad, mlp_only=self.kind in ("a2svd", "gru4rec"))
         if any(float(getattr(hp, k)) != 0.0 for k in ("embed_l1", "layer_l1", "cross_l1", "cross_l2")):
             bad.append("l1 / cross regularisers must be 0")
         if hp.loss != "softmax" or hp.method != "classification":
@@ -84,6 +86,11 @@ class SeqNet(CLSRNet):
 
     def _att_qh(self, key):
         return 0
+
+    def _det_merged(self, f):
+        """As in the CLSR graph, the target rows' ids follow the history lookup's ids in ONE sorted list per table: no
+        float atomics on the target site, two runs of a step give bit-identical gradient tables."""
+        return {"item": ("items", f["B"]), "cate": ("cates", f["B"])}
 
     # ------------------------------------------------------------------ encoders
     def _gru_list(self):
@@ -271,13 +278,18 @@ class SeqNet(CLSRNet):
             out.update(att_fea1=att1, att_fea2=att2, rnn_out=rnn_out, alpha=alpha, w_asvd=w1,
                        w_att=self._buf("st.wts", B, T))
         self._join()
-        out["logit"] = self._mlp_fwd("lg", LG, mo, W, W, (self.L0, self.L1), B, training)
+        if training and self.drop_on:
+            out["logit"] = self._mlp_fwd_drop("lg", LG, mo, W, W, (self.L0, self.L1), B)
+        else:       # (evaluation and predict never drop: keep_prob_test)
+            out["logit"] = self._mlp_fwd("lg", LG, mo, W, W, (self.L0, self.L1), B, training)
         return out
 
     # ------------------------------------------------------------------ training step
     def _train_step(self, f, apply):
         hp, P, Gd, kind, sc = self.hp, self.P, self.Gd, self.kind, self.sc
-        self._step = _StepState()      # (these graphs set none of its fields: the shared phases read an idle one)
+        self._step = _StepState(f)     # (these graphs set none of its other fields: the shared phases read idle ones)
+        if self.drop_on:
+            call("clsr_dropout_tick", self.drop_state)     # first launch of the step: this step's draw number
         B, T = f["B"], f["T"]
         G = self.G_train if self.dedup else 1
         Hn = B // G
@@ -307,7 +319,8 @@ class SeqNet(CLSRNet):
         Gl = hp.train_num_ngs + 1
         call("clsr_softmax_loss", out["logit"], f["labels"], B // Gl, Gl, 1.0 / ((B // Gl) * self.dp_world),
              self.losses[0:], dlogit)
-        dmo = self._mlp_bwd("lg", LG, dlogit, out["model_output"], W, W, W, (self.L0, self.L1), B)
+        mlp_bwd = self._mlp_bwd_drop if self.drop_on else self._mlp_bwd
+        dmo = mlp_bwd("lg", LG, dlogit, out["model_output"], W, W, W, (self.L0, self.L1), B)
         hist = out["hist_input"]
         if kind == "gru4rec":
             NX = self.NX
@@ -408,9 +421,13 @@ class SeqNet(CLSRNet):
         self._join()
         # ---- embedding gradients
         ss = self.sumsq_tab
-        self._hist_grad_sorted(dhist, dM, dR, Hn, T, seq_len, ls, ss)
-        call("clsr_scatter_add_rows", dtarget, D, 0, f["items"], 1, B, Di, self.tab_grad["item"], ss[2:])
-        call("clsr_scatter_add_rows", dtarget, D, Di, f["cates"], 1, B, Dc, self.tab_grad["cate"], ss[3:])
+        if self.det_grads and self._det_merged(f):
+            # the target rows ride in the sorted lists of the history lookups: every gradient row summed in a fixed order
+            self._hist_grad_sorted(dhist, dM, dR, Hn, T, seq_len, ls, ss, dtarget=dtarget)
+        else:
+            self._hist_grad_sorted(dhist, dM, dR, Hn, T, seq_len, ls, ss)
+            call("clsr_scatter_add_rows", dtarget, D, 0, f["items"], 1, B, Di, self.tab_grad["item"], ss[2:])
+            call("clsr_scatter_add_rows", dtarget, D, Di, f["cates"], 1, B, Dc, self.tab_grad["cate"], ss[3:])
         if apply:
             self._apply_updates()
         return out

@@ -8,6 +8,7 @@ user of the reference makes is the import root (clsr_amd instead of reco_utils..
 
     python examples/sequential.py --dataset taobao --data_path <dir with train_data/valid_data/test_data + vocab pkl>
     python examples/sequential.py --synthetic          # 1k-item synthetic slice (BASELINE config 1 shape)
+    python examples/sequential.py --model A2SVD --user_dropout true --dropout 0.3,0.3 ...   # the reference's asvd.yaml recipe
 """
 import argparse
 import os
@@ -62,6 +63,11 @@ def get_flags():
     p.add_argument("--show_step", type=int, default=500)
     p.add_argument("--sample_rate", type=float, default=1.0)
     p.add_argument("--synthetic", action="store_true", help="generate a 1k-item synthetic slice first")
+    p.add_argument("--user_dropout", type=str2bool, default=None,
+                   help="sibling models: apply --dropout in front of each activation of the logit MLP (A2SVD, GRU4REC; "
+                        "the reference's asvd.yaml trains with --user_dropout true --dropout 0.3,0.3)")
+    p.add_argument("--dropout", type=lambda v: [float(x) for x in v.split(",")], default=None,
+                   help="comma list, one rate per layer of layer_sizes")
     p.add_argument("--shard_eval", type=str2bool, default=False,
                    help="data parallel only: the ranks share validation / test (same metrics, to the bit)")
     return p.parse_args()
@@ -80,6 +86,10 @@ def get_model(flags_obj, model_path, summary_path, user_vocab, item_vocab, cate_
         yaml_name, cls = siblings[flags_obj.model]
         extra = dict(manual_alpha=flags_obj.manual_alpha, manual_alpha_value=flags_obj.manual_alpha_value) \
             if flags_obj.model == "SLIREC" else {}
+        if flags_obj.user_dropout is not None:      # (default: what the model's yaml says)
+            extra["user_dropout"] = flags_obj.user_dropout
+        if flags_obj.dropout is not None:
+            extra["dropout"] = flags_obj.dropout
         hparams = prepare_hparams(
             os.path.join(os.path.dirname(YAML), yaml_name), embed_l2=flags_obj.embed_l2, layer_l2=flags_obj.layer_l2,
             learning_rate=flags_obj.learning_rate, epochs=flags_obj.epochs, EARLY_STOP=flags_obj.early_stop,

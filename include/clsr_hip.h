@@ -752,6 +752,30 @@ int clsr_softmax_weights_bwd(const float* dw, const float* wts, const int* seq_l
 int clsr_mul_rows(const float* a, int lda, const float* b, int ldb, int G, long R, int C, float* out, int ldo,
                   void* stream);
 
+/* ---- dropout of _fcn_net's hidden layers (csrc/dropout.hip, csrc/philox.h): base_model.py _active_layer, user_dropout --
+ * a = relu(dropout(bn(z))), keep = 1 - dropout[layer].  The mask is a function of (seed, draw, layer, GLOBAL row, column):
+ * Philox4x32-10 with counter (row0 + r, c / 4, layer, draw) and key (seed low, seed high); its four words serve columns
+ * 4 (c / 4) ... + 3; kept <=> (word >> 8) < thr with thr = round(keep * 2^24) (0 ... 2^24, computed by the caller); kept
+ * elements are scaled by inv_keep = float(1 / keep).  Nothing stores the mask: the backward kernel draws it again.
+ * `state`: 4 unsigned 32-bit words on the DEVICE, {seed low, seed high, draw, 0}; clsr_dropout_tick adds 1 to draw (the
+ * first launch of a training step, so that replayed launch sequences and graphs see a new mask per step).
+ * fwd: a [B, C] = mask * relu(scale * z + shift) * inv_keep.
+ * bwd: dy [B, C] = da * mask * inv_keep * [scale * z + shift > 0] (dy may be da) and the batch-norm backward sums as
+ * bn_partial [clsr_bn_relu_dropout_bwd_parts(B, C)][2][C] doubles (sum dy | sum dy * xhat: clsr_mlp_out_bwd's layout, read
+ * by clsr_bn_bwd_coef* / clsr_bn_bwd_coef_apply); fixed summation order, no atomics, no LDS.  C: multiple of 4, 4 ... 1024.
+ * The two `_host` entry points run the same generator on the host (HOST pointers, no GPU, no stream): one Philox block,
+ * and mask [B, C] bytes (1 kept / 0) of rows row0 ... row0 + B - 1 for any C >= 1. */
+int clsr_dropout_tick(unsigned int* state, void* stream);
+int clsr_bn_relu_dropout_fwd(const float* z, const float* scale, const float* shift, const unsigned int* state,
+                             int layer, long row0, int thr, float inv_keep, long B, int C, float* a, void* stream);
+int clsr_bn_relu_dropout_bwd_parts(long B, int C);
+int clsr_bn_relu_dropout_bwd(const float* da, const float* z, const float* scale, const float* shift,
+                             const float* mean, const float* invstd, const unsigned int* state, int layer, long row0,
+                             int thr, float inv_keep, long B, int C, float* dy, double* bn_partial, void* stream);
+int clsr_philox4x32_10_host(const unsigned int* ctr, const unsigned int* key, unsigned int* out);
+int clsr_dropout_mask_host(unsigned long seed, unsigned int draw, int layer, long row0, long B, int C, int thr,
+                           unsigned char* mask);
+
 /* ---- regularisers, clip, Adam: base_model.py:118-159,249-297; clsr.py:73-82.  l2 / l1: embed_l2 / embed_l1 for the
  *      involved embedding rows, layer_l2 / layer_l1 for the dense variables (loss += l2/2 ||w||^2 + l1 |w|_1,
  *      grad += l2 w + l1 sign(w)) */
