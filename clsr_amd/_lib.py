@@ -1,7 +1,7 @@
 """ctypes loader for libclsr_hip.so (the C ABI declared in include/clsr_hip.h).
 
-The prototypes are parsed from the header itself so the Python bindings can never drift from
-the C declarations.  There is NO fallback: if the shared library is missing the product path
+The prototypes and the descriptor structs are parsed from the header itself so the Python bindings
+can never drift from the C declarations.  There is NO fallback: if the shared library is missing the product path
 raises (the CPU oracle under oracle/ is test infrastructure and is never used here).
 """
 import ctypes
@@ -41,6 +41,30 @@ def parse_header(path=HEADER):
                 kinds.append(None)
         protos[name] = (_CT[ret], argtypes, kinds)
     return protos
+
+
+def parse_structs(path=HEADER):
+    """Return {struct name: [(field, ctype)]}, fields in declaration order, for every
+    ``typedef struct clsr_X { ... } clsr_X;`` of the header.  Pointers of any kind are ``c_void_p``; a member of an
+    earlier struct type (``clsr_bn_ptrs bn[4]``) is a ctypes Structure built from that struct's own entry.  A base
+    type that is not known raises: a layout is never guessed."""
+    text = re.sub(r"/\*.*?\*/", " ", open(path).read(), flags=re.S)
+    types, structs = dict(_CT), {}
+    for m in re.finditer(r"typedef\s+struct\s+(clsr_\w+)\s*\{(.*?)\}\s*\1\s*;", text, flags=re.S):
+        fields = []
+        for decl in filter(None, (d.strip() for d in m.group(2).split(";"))):
+            base, fname, count = re.fullmatch(r"(.*?)(\w+)\s*(?:\[\s*(\d+)\s*\])?", decl, flags=re.S).groups()
+            base = " ".join(base.replace("const", " ").split())
+            if "*" in base:
+                ct = ctypes.c_void_p
+            elif base in types:
+                ct = types[base]
+            else:
+                raise ValueError("%s.%s: unknown type %r in %s" % (m.group(1), fname, base, path))
+            fields.append((fname, ct * int(count) if count else ct))
+        structs[m.group(1)] = fields
+        types[m.group(1)] = type(m.group(1), (ctypes.Structure,), {"_fields_": fields})
+    return structs
 
 
 class ClsrLibraryError(RuntimeError):

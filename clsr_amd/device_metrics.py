@@ -202,7 +202,8 @@ def compute(scores, hp, group, weighted, raw=None, n_users=None, mean_alpha=Fals
         keys = torch.empty(N, dtype=torch.int32, device=dev)
         perm = torch.empty(N, dtype=torch.int32, device=dev)
         ws = torch.empty(ops.query("clsr_sort_ids_stable_workspace_bytes", N, 1), dtype=torch.uint8, device=dev)
-        ops.sort_ids_stable_multi([(scores.users[:N].data_ptr(), keys.data_ptr(), perm.data_ptr(), N, 1, 1, bits)], ws)
+        ops.sort_ids_stable_multi([ops.SortIdsDesc.row(ids=scores.users[:N], keys_out=keys, perm_out=perm, nrows=N, row_stride=1,
+                                                       ncols=1, bits=bits)], ws)
         starts = torch.empty(N, dtype=torch.int32, device=dev)
         nseg = torch.zeros(1, dtype=torch.int32, device=dev)
         ops.call("clsr_eval_user_segments", keys, N, starts, nseg)

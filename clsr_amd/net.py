@@ -906,9 +906,8 @@ class CLSRNet(object):
         sc, sh = (aff.scale, aff.shift) if aff is not None else (None, None)
         if self._dw_batch is not None and not x_bf16 and not (dy_bf16 and not self.bf16):
             # inside _dw_batched(): the product joins the ONE multi-job launch issued when the block ends
-            ptr = lambda t: 0 if t is None else t.data_ptr()
-            self._dw_batch.append((ptr(X), ptr(Xmul), ptr(sc), ptr(sh), ptr(dY), ptr(ws), 0, ldx, T, G, ldmul, 1,
-                                   int(dy_bf16), ldy, M, K, N, 0))
+            self._dw_batch.append(ops.DwJob.row(X=X, Xmul=Xmul, in_scale=sc, in_shift=sh, dY=dY, workspace=ws, ldx=ldx, T=T,
+                                                G=G, ldmul=ldmul, in_relu=1, dy_bf16=int(dy_bf16), ldy=ldy, M=M, K=K, N=N))
         elif self.overlap and self._ws_tag == "":
             # nothing on the main chain needs a weight gradient before the flush: the partial-sum kernels of the
             # main stream go to a stream of their own (inputs are final at this point and stay untouched until the
@@ -918,8 +917,8 @@ class CLSRNet(object):
             self._dw_launch(X, x_bf16, ldx, T, G, Xmul, ldmul, sc, sh, dY, dy_bf16, ldy, M, K, N, ws, self._dw_stream())
         else:
             self._dw_launch(X, x_bf16, ldx, T, G, Xmul, ldmul, sc, sh, dY, dy_bf16, ldy, M, K, N, ws, None)
-        pend.append((ws.data_ptr(), dW.data_ptr(), db.data_ptr() if db is not None else 0, 1.0,
-                     query("clsr_hdw_parts" if self.bf16 else "clsr_pgemm_dw_parts", M), K, N, ldw, acc))
+        pend.append(ops.DwDesc.row(partial=ws, dW=dW, db=db, scale=1.0, K=K, N=N, ldw=ldw, accumulate=acc,
+                                   nparts=query("clsr_hdw_parts" if self.bf16 else "clsr_pgemm_dw_parts", M)))
         if not self.defer_dw:
             self._dw_flush()
 
@@ -992,7 +991,7 @@ class CLSRNet(object):
         """A weight gradient whose ``parts`` partial chunks were written by the back-propagating kernel itself
         (csrc/attbwdx3.hip) on the CURRENT stream: only the entry of the batched reduction is left."""
         self._dw_pending.setdefault(self._ws_tag, []).append(
-            (ws.data_ptr(), dW.data_ptr(), db.data_ptr() if db is not None else 0, 1.0, parts, K, N, ldw, acc))
+            ops.DwDesc.row(partial=ws, dW=dW, db=db, scale=1.0, nparts=parts, K=K, N=N, ldw=ldw, accumulate=acc))
         if not self.defer_dw:
             self._dw_flush()
 
@@ -1000,7 +999,7 @@ class CLSRNet(object):
         """out[0:n] = sum over ``parts`` per-block partial rows (deferred to ``_dw_flush`` like the dW reductions;
         the partial buffer must stay untouched until then)."""
         self._rp_pending.setdefault(self._ws_tag, []).append(
-            (partial.data_ptr(), out.data_ptr(), 1.0, parts, stride, n, 0, 0))
+            ops.RpDesc.row(partial=partial, out=out, scale=1.0, nparts=parts, stride=stride, n=n))
 
     def _dw_flush(self, tag=None):
         """Reduce the partial chunks of every ``_dw`` issued under workspace tag ``tag`` (default: the current
@@ -1748,7 +1747,8 @@ class CLSRNet(object):
         if self.defer_dw:
             pend = self._dw_pending[self._ws_tag]
             pa, pq = pend[-2], pend[-1]
-            pend.append((pa[0], dW0[2 * Q:3 * Q].data_ptr(), 0, 1.0, pa[4], Q, A0, A0, 0, pq[0], -1.0, pq[4]))
+            pend.append(ops.DwDesc.row(partial=pa.partial, dW=dW0[2 * Q:3 * Q], scale=1.0, nparts=pa.nparts, K=Q, N=A0, ldw=A0,
+                                       partial2=pq.partial, scale2=-1.0, nparts2=pq.nparts))
         else:
             call("clsr_axpby", dW0[2 * Q:3 * Q], dW0[0:Q], 1.0, dW0[Q:2 * Q], -1.0, Q * A0)
         fused = not da_has_u and self._hist_bwd_x3(Dk, Q, qh)
@@ -2002,7 +2002,7 @@ class CLSRNet(object):
         for i, (dW, ldw, db, K, N) in enumerate(prods):
             ws = self._buf("%s.ws%d" % (prefix, i), query("clsr_enc_bwd_fused%s_workspace_floats" % tag, M, i))
             wss.append(ws)
-            pend.append((ws.data_ptr(), dW.data_ptr(), db.data_ptr() if db is not None else 0, 1.0, parts, K, N, ldw, 0))
+            pend.append(ops.DwDesc.row(partial=ws, dW=dW, db=db, scale=1.0, nparts=parts, K=K, N=N, ldw=ldw))
         return wss
 
     def _enc_bwd_fused(self, f, hist, dPinAll, dhist, Hn, T, hs):
@@ -2111,10 +2111,10 @@ class CLSRNet(object):
         ulong, ushort = self._buf("u_long", Hn, Du), self._buf("u_short", Hn, Du)
         tb = self.tables
         ops.multi("clsr_gather_rows_multi" + self._th, ops.GatherDesc, [     # target = [item | cate], user_long, user_short
-            (tb["item"].data_ptr(), f["items"].data_ptr(), target.data_ptr(), 1, B, Di, D, 0),
-            (tb["cate"].data_ptr(), f["cates"].data_ptr(), target.data_ptr(), 1, B, Dc, D, Di),
-            (tb["user_long"].data_ptr(), f["users"].data_ptr(), ulong.data_ptr(), hs, Hn, Du, Du, 0),
-            (tb["user_short"].data_ptr(), f["users"].data_ptr(), ushort.data_ptr(), hs, Hn, Du, Du, 0)])
+            ops.GatherDesc.row(table=tb["item"], idx=f["items"], out=target, idx_stride=1, N=B, C=Di, ldo=D),
+            ops.GatherDesc.row(table=tb["cate"], idx=f["cates"], out=target, idx_stride=1, N=B, C=Dc, ldo=D, col0=Di),
+            ops.GatherDesc.row(table=tb["user_long"], idx=f["users"], out=ulong, idx_stride=hs, N=Hn, C=Du, ldo=Du),
+            ops.GatherDesc.row(table=tb["user_short"], idx=f["users"], out=ushort, idx_stride=hs, N=Hn, C=Du, ldo=Du)])
         # ---- sequence encoders: ONE fused input projection, then ONE fused launch for all recurrences
         st = CL + "short_term/"
         M = Hn * T
@@ -2412,29 +2412,31 @@ class CLSRNet(object):
         def zero_and_mark():
             # ONE zero-fill launch: squared norms (16) + loss terms (8), the gradient pool, the counters of the
             # history-id sort and the distinct-user counter of the discrepancy loss
-            zr = [(self.stats24.data_ptr(), 24 * 8), (zpool.data_ptr(), zpool.numel() * 4)]
+            zero = ops.ZeroDesc.row
+            zr = [zero(p=self.stats24, nbytes=24 * 8), zero(p=zpool, nbytes=zpool.numel() * 4)]
             counts = self._sort_counts()[0]
-            zr.append((counts.data_ptr(), counts.numel() * 4))
+            zr.append(zero(p=counts, nbytes=counts.numel() * 4))
             step.counts_zeroed = True
             if "user_long" in self.tables:
-                zr.append((self.ucount.data_ptr(), 4))
+                zr.append(zero(p=self.ucount, nbytes=4))
                 step.ucount_zeroed = True
             if heads_fused:
-                zr.append((self._heads_ws().data_ptr(), int(query("clsr_heads_fused_counter_bytes"))))
+                zr.append(zero(p=self._heads_ws(), nbytes=int(query("clsr_heads_fused_counter_bytes"))))
             if self._att_qh("st") and G > 1:
                 # split short-term query: the history-level columns of d(query) only receive the V path (an
                 # accumulating product): cleared here with the other accumulators
                 dq_st = self._buf("st.dq", B, Du + D)
-                zr.append((dq_st.data_ptr(), dq_st.numel() * 4))
+                zr.append(zero(p=dq_st, nbytes=dq_st.numel() * 4))
             ops.multi("clsr_zero_multi", ops.ZeroDesc, zr)
             # involved-row flags (tf.unique id sets)
+            mark = ops.MarkDesc.row
             ops.multi("clsr_mark_rows_multi", ops.MarkDesc, [
-                (f["item_history"].data_ptr(), fl["item"].data_ptr(), Hn, hs * T, T, 0),
-                (f["items"].data_ptr(), fl["item"].data_ptr(), B, 1, 1, 0),
-                (f["item_cate_history"].data_ptr(), fl["cate"].data_ptr(), Hn, hs * T, T, 0),
-                (f["cates"].data_ptr(), fl["cate"].data_ptr(), B, 1, 1, 0),
-                (f["users"].data_ptr(), fl["user_long"].data_ptr(), Hn, hs, 1, 0),
-                (f["users"].data_ptr(), fl["user_short"].data_ptr(), Hn, hs, 1, 0)])
+                mark(idx=f["item_history"], flags=fl["item"], nrows=Hn, row_stride=hs * T, ncols=T),
+                mark(idx=f["items"], flags=fl["item"], nrows=B, row_stride=1, ncols=1),
+                mark(idx=f["item_cate_history"], flags=fl["cate"], nrows=Hn, row_stride=hs * T, ncols=T),
+                mark(idx=f["cates"], flags=fl["cate"], nrows=B, row_stride=1, ncols=1),
+                mark(idx=f["users"], flags=fl["user_long"], nrows=Hn, row_stride=hs, ncols=1),
+                mark(idx=f["users"], flags=fl["user_short"], nrows=Hn, row_stride=hs, ncols=1)])
             self._dp_hook("flags_ready")      # involved-row byte maps are final: their exchange hides under the forward
             if (apply and not self.capture_grads and self.dp_hooks is None
                     and "user_long" in self.tables):
@@ -2626,7 +2628,8 @@ class CLSRNet(object):
         for (name, fkey, V, _, _, _), b in zip(tabs, bits):
             keys = self._buf("sort.keys." + name, n, dtype=torch.int32)
             perm = self._buf("sort.perm." + name, n, dtype=torch.int32)
-            rows.append((f[fkey].data_ptr(), keys.data_ptr(), perm.data_ptr(), counts[o:].data_ptr(), Hn, hs * T, T, b))
+            rows.append(ops.SortIdsDesc.row(ids=f[fkey], keys_out=keys, perm_out=perm, counts=counts[o:], nrows=Hn,
+                                            row_stride=hs * T, ncols=T, bits=b))
             o += 1 << b
         ops.sort_ids_multi(rows)
 
@@ -2658,15 +2661,15 @@ class CLSRNet(object):
             ne = n + (extra[1] if extra else 0)
             keys = self._buf("sort.keys." + name, ne, dtype=torch.int32)
             perm = self._buf("sort.perm." + name, ne, dtype=torch.int32)
-            row = (f[fkey].data_ptr(), keys.data_ptr(), perm.data_ptr(), Hn, hs * T, T, max(1, (V - 1).bit_length()))
-            if extra:
-                row += (f[extra[0]].data_ptr(), extra[1], 1)
-            rows.append(row)
+            second = dict(ids2=f[extra[0]], nrows2=extra[1], row_stride2=1) if extra else {}
+            rows.append(ops.SortIdsDesc.row(ids=f[fkey], keys_out=keys, perm_out=perm, nrows=Hn, row_stride=hs * T, ncols=T,
+                                            bits=max(1, (V - 1).bit_length()), **second))
             total += ne
         for name, fkey, V, nr, stride in self._det_sites(f):
             keys = self._buf("sort.keys." + name, nr, dtype=torch.int32)
             perm = self._buf("sort.perm." + name, nr, dtype=torch.int32)
-            rows.append((f[fkey].data_ptr(), keys.data_ptr(), perm.data_ptr(), nr, stride, 1, max(1, (V - 1).bit_length())))
+            rows.append(ops.SortIdsDesc.row(ids=f[fkey], keys_out=keys, perm_out=perm, nrows=nr, row_stride=stride, ncols=1,
+                                            bits=max(1, (V - 1).bit_length())))
             total += nr
         ws = self._buf("sort.ws", query("clsr_sort_ids_stable_workspace_bytes", total, len(rows)), dtype=torch.uint8)
         ops.sort_ids_stable_multi(rows, ws)
@@ -2680,13 +2683,13 @@ class CLSRNet(object):
         other lookup site, its gradient rows are zero: the totals are stored"""
         keys = self._buf("sort.keys." + name, n, dtype=torch.int32)
         perm = self._buf("sort.perm." + name, n, dtype=torch.int32)
-        return (src.data_ptr(), 0, 0, 0, keys.data_ptr(), perm.data_ptr(), 0, grad.data_ptr(), sumsq.data_ptr(), n, 0, 0, 1,
-                ld, col0, C, 1, grad.shape[1], 0, 1)
+        return ops.SegsumDesc.row(src=src, keys=keys, perm=perm, grad=grad, sumsq=sumsq, n=n, T=1, D=ld, col0=col0, C=C,
+                                  recent_k=1, ldg=grad.shape[1], assign=1)
 
     def _scatter_user_item_rows(self, f, dul, dushort, dtarget, Hn, B, hs):
         """User rows (long / short table) and the target items' rows: ONE launch, blockIdx.y = lookup site (``None``:
         that site is not part of this launch)."""
-        tg, ss, dp_ = self.tab_grad, self.sumsq_tab, lambda t: t.data_ptr()
+        tg, ss = self.tab_grad, self.sumsq_tab
         D, Du, Di = self.D, self.Du, self.Di
         if self.det_grads and self._det_sites(f):
             rows = []
@@ -2702,13 +2705,13 @@ class CLSRNet(object):
             if dushort is not None:
                 self._dp_hook("table_ready", "user_short")
             return
-        sites = []
+        sites, site = [], ops.ScatterDesc.row
         if dul is not None:
-            sites.append((dp_(dul), dp_(f["users"]), dp_(tg["user_long"]), dp_(ss[6:]), hs, Du, 0, Hn, Du))
+            sites.append(site(src=dul, idx=f["users"], tbl_grad=tg["user_long"], sumsq=ss[6:], idx_stride=hs, ld_src=Du, N=Hn, C=Du))
         if dushort is not None:
-            sites.append((dp_(dushort), dp_(f["users"]), dp_(tg["user_short"]), dp_(ss[7:]), hs, Du, 0, Hn, Du))
+            sites.append(site(src=dushort, idx=f["users"], tbl_grad=tg["user_short"], sumsq=ss[7:], idx_stride=hs, ld_src=Du, N=Hn, C=Du))
         if dtarget is not None:
-            sites.append((dp_(dtarget), dp_(f["items"]), dp_(tg["item"]), dp_(ss[2:]), 1, D, 0, B, Di))
+            sites.append(site(src=dtarget, idx=f["items"], tbl_grad=tg["item"], sumsq=ss[2:], idx_stride=1, ld_src=D, N=B, C=Di))
         ops.multi("clsr_scatter_add_rows_multi", ops.ScatterDesc, sites)
         if dul is not None:
             self._dp_hook("table_ready", "user_long")
@@ -2751,17 +2754,13 @@ class CLSRNet(object):
                 ne = n + (merged[name][1] if name in merged else 0)
                 keys = self._buf("sort.keys." + name, ne, dtype=torch.int32)
                 perm = self._buf("sort.perm." + name, ne, dtype=torch.int32)
-                ptr = lambda t: 0 if t is None else t.data_ptr()
-                row = (dhist.data_ptr(), ptr(dhist2), ptr(dM), ptr(dR), keys.data_ptr(), perm.data_ptr(),
-                       seq_len.data_ptr(), self.tab_grad[name].data_ptr(), ss[slot:].data_ptr(), ne,
-                       int(dhist.dtype == torch.bfloat16), ls, T, self.D, col0, C, k, C, 0)
-                if name in merged:
-                    # second source = the target rows' gradients [B, D] (same column slice), their squared norms in the
-                    # target site's slot (2 item, 3 category); every row is written once: stored
-                    row += (1, dtarget.data_ptr(), ss[slot + 2:].data_ptr(), n, self.D, col0)
-                else:
-                    row += (0, 0, 0, 0, 0, 0)
-                rows.append(row + (0, 0))
+                # second source = the target rows' gradients [B, D] (same column slice), their squared norms in the
+                # target site's slot (2 item, 3 category); every row is written once: stored
+                second = dict(assign=1, src_b=dtarget, sumsq_b=ss[slot + 2:], n1=n, ldb=self.D, colb=col0) if name in merged else {}
+                rows.append(ops.SegsumDesc.row(
+                    src=dhist, src2=dhist2, dmean=dM, drecent=dR, keys=keys, perm=perm, seq_len=seq_len, grad=self.tab_grad[name],
+                    sumsq=ss[slot:], n=ne, src_bf16=int(dhist.dtype == torch.bfloat16), len_stride=ls, T=T, D=self.D, col0=col0,
+                    C=C, recent_k=k, ldg=C, **second))
             self._segsum("hist." + (only or "all"), rows)
             return
         for name, _, V, col0, C, slot in self._sort_tables():
@@ -2808,9 +2807,9 @@ class CLSRNet(object):
         tb, ss = self.tables, self.sumsq_tab
         V, C = tb[key].shape
         pt = tb[partner] if partner else None
-        return (tb[key].data_ptr(), ops._ptr(pt), self.tab_grad[key].data_ptr(), ops._ptr(self.tab_m.get(key)),
-                ops._ptr(self.tab_v.get(key)), self.tab_flags[key].data_ptr(), ss[slot:].data_ptr(), ops._ptr(dloss),
-                ss[base:].data_ptr(), V, C, nsum, 2, dscale, dloss_scale, 0)
+        return ops.TableDesc.row(table=tb[key], partner=pt, grad=self.tab_grad[key], m=self.tab_m.get(key), v=self.tab_v.get(key),
+                                 flags=self.tab_flags[key], sumsq_reg=ss[slot:], disc_loss=dloss, sumsq_adam=ss[base:], V=V, C=C,
+                                 nsum=nsum, sumsq_stride=2, disc_scale=dscale, disc_loss_scale=dloss_scale)
 
     def _tab_halves(self, key):
         """Leading arguments of a single-table Adam entry: the table -- with ``table_master`` its bf16 and residual halves."""
@@ -2821,9 +2820,9 @@ class CLSRNet(object):
         if self.tf_opt is not None:     # touched rows only (IndexedSlices), flags cleared by the launch
             ops.multi("clsr_tables_tf_multi", ops.TableDesc, rows, self.tf_opt[0], clip, self.adam_state,
                       float(self.hp.learning_rate))
-        elif self.table_master:         # (rows[i][0]: the bf16 half of the table; its residual half rides beside the descriptors)
+        elif self.table_master:         # (row.table: the bf16 half of the table; its residual half rides beside the descriptors)
             ops.multi("clsr_tables_adam_multi_hm", ops.TableDesc, rows, clip, self.adam_state, 0.9, 0.999, 1e-8, self.lazy,
-                      lo=[self._lo_of[r[0]] for r in rows])
+                      lo=[self._lo_of[r.table] for r in rows])
         else:
             ops.multi("clsr_tables_adam_multi" + self._th, ops.TableDesc, rows, clip, self.adam_state, 0.9, 0.999, 1e-8,
                       self.lazy)
@@ -2931,7 +2930,7 @@ class CLSRNet(object):
             else:
                 rest.append(key)
         if rest:
-            self._tables_update_multi([r for r in sweep if r[0] in {tb[k].data_ptr() for k in rest}], clip)
+            self._tables_update_multi([r for r in sweep if r.table in {tb[k].data_ptr() for k in rest}], clip)
         if tick_early:
             self._join()          # the dense path (@aux): the next step reads the updated variables on this stream
 

@@ -170,8 +170,8 @@ class SeqNet(CLSRNet):
         target = self._buf("target", B, D)
         tb = self.tables
         ops.multi("clsr_gather_rows_multi", ops.GatherDesc, [
-            (tb["item"].data_ptr(), f["items"].data_ptr(), target.data_ptr(), 1, B, Di, D, 0),
-            (tb["cate"].data_ptr(), f["cates"].data_ptr(), target.data_ptr(), 1, B, Dc, D, Di)])
+            ops.GatherDesc.row(table=tb["item"], idx=f["items"], out=target, idx_stride=1, N=B, C=Di, ldo=D),
+            ops.GatherDesc.row(table=tb["cate"], idx=f["cates"], out=target, idx_stride=1, N=B, C=Dc, ldo=D, col0=Di)])
         M = Hn * T
         W = self.out_dim
         mo = self._buf("model_output", B, W)
@@ -304,11 +304,12 @@ class SeqNet(CLSRNet):
             call("clsr_zero_doubles", self.losses, 8)
             call("clsr_zero_doubles", self.sumsq_tab, 16)
             call("clsr_zero_floats", zpool, zpool.numel())
+            mark = ops.MarkDesc.row
             ops.multi("clsr_mark_rows_multi", ops.MarkDesc, [
-                (f["item_history"].data_ptr(), fl["item"].data_ptr(), Hn, hs * T, T, 0),
-                (f["items"].data_ptr(), fl["item"].data_ptr(), B, 1, 1, 0),
-                (f["item_cate_history"].data_ptr(), fl["cate"].data_ptr(), Hn, hs * T, T, 0),
-                (f["cates"].data_ptr(), fl["cate"].data_ptr(), B, 1, 1, 0)])
+                mark(idx=f["item_history"], flags=fl["item"], nrows=Hn, row_stride=hs * T, ncols=T),
+                mark(idx=f["items"], flags=fl["item"], nrows=B, row_stride=1, ncols=1),
+                mark(idx=f["item_cate_history"], flags=fl["cate"], nrows=Hn, row_stride=hs * T, ncols=T),
+                mark(idx=f["cates"], flags=fl["cate"], nrows=B, row_stride=1, ncols=1)])
         take = self._carver(zpool)
         dhist, drnn = take(Hn, T, D), take(Hn, T, H)
         dtarget, dS, datt = take(B, D), take(B, D), take(B, D)
