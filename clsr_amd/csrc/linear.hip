@@ -504,6 +504,14 @@ static int pgemm_grid_x(int M) {
 
 extern "C" int clsr_pgemm_stats_parts(int M) { return pgemm_grid_x(M); }
 
+static int pgemm_exact_stats_rows() {
+  static const int rows = [] {
+    const char* e = getenv("CLSR_PGEMM_EXACT_STATS_ROWS");
+    return e ? atoi(e) : 256;
+  }();
+  return rows;
+}
+
 template <typename KernelT>
 static int launch_kernel(KernelT kernel, const PGemmArgs& a, dim3 grid, size_t shmem, hipStream_t stream) {
   if (shmem > 64 * 1024)
@@ -534,7 +542,13 @@ static int launch_pgemm(const PGemmArgs& a, hipStream_t stream) {
   // few positions, wide K: latency bound (see the kernel); also the skinny d(hist) = dPin . W^T product (K = 480 -> 40
   // columns: 30 k-tiles per wave-tile, 100 -> 132 VGPRs with the ring)
   const bool ring = !a.no_ring && KTn > 5 && (a.M <= 65536 || (OT == 3 && KTn >= 16));
-#define CLSR_FAST(P, E, S)                                                                          \
+  // Batch-norm statistics of FEW rows: the generic kernel, whose column sums and sums of squares are accumulated in double
+  // from the first value on.  The fast kernels keep fp32 partials (up to 512 values) before they widen; var = E[z^2] - mean^2
+  // then carries a relative error of 2^-24 * (1 + (mean / std)^2), and in a small batch a column's spread can be a
+  // hundredth of its mean (DIN, four rows, masked history sums of 250 steps: |mean| / std = 104, invstd off by 3e-4, logits
+  // by 5.5e-5 where the float32 reference is within 4e-6).  CLSR_PGEMM_EXACT_STATS_ROWS: the row count up to which (A/B).
+  if (st && a.M <= pgemm_exact_stats_rows()) return launch_kernel(pgemm_generic_kernel<OT, true>, a, grid, shmem, stream);
+#define CLSR_FAST(P, E, S)                                                                         \
   if (uv_ok && pro == (P) && epi == (E) && st == (S)) {                                             \
     /* (the X * Xmul variant holds twice the operands: with everything in flight it drops to one wave per SIMD and loses) */ \
     if (upfront && (P) != PRO_MUL && KTn == 5) return launch_kernel(pgemm_fast_kernel<OT, P, E, S, 5>, a, grid, shmem, stream); \

@@ -35,8 +35,13 @@ def chunks_to_matrix(ws, parts, K, N):
     return full[:K, :N].cpu(), w[25 * 256: 25 * 256 + N].cpu(), full
 
 
+# histories past one 64-step chunk, up to max_seq_length = 256 (the rows of tests/test_kernels_gpu.py LONG_L0)
+LONG_L0 = [(3, 5, 65, 80, 80), (2, 8, 256, 80, 80), (4, 1, 250, 40, 80)]
+
+
 @pytest.mark.parametrize("Hn,G,T,Q,A0", [(37, 5, 50, 40, 80), (64, 1, 50, 40, 80), (9, 8, 7, 44, 40), (6, 3, 17, 24, 40),
-                                         (1, 5, 1, 80, 80), (130, 2, 33, 48, 80), (2100, 2, 5, 40, 80), (5, 5, 50, 8, 16)])
+                                         (1, 5, 1, 80, 80), (130, 2, 33, 48, 80), (2100, 2, 5, 40, 80), (5, 5, 50, 8, 16)]
+                         + LONG_L0)
 @pytest.mark.parametrize("entry,tol,tols", [("clsr_att_l0_bwd_x3", 1e-4, 3e-5), ("clsr_att_l0_bwd_x6", 3e-6, 3e-6)])
 def test_layer0_backward_x3_with_weight_gradient(Hn, G, T, Q, A0, entry, tol, tols):
     """x3: two bf16 pieces per operand (2^-16 per product term); x6: three pieces -- every tensor at fp32 accuracy"""
@@ -171,7 +176,8 @@ def test_layer1_backward_x3_two_passes_with_weight_gradient(M, C1, C0, entry, to
 @pytest.mark.parametrize("Hn,G,T,Q,A0", [(37, 5, 50, 80, 80), (64, 1, 50, 40, 80), (9, 8, 7, 44, 36), (6, 3, 17, 24, 40),
                                          (1, 5, 1, 80, 80), (2100, 2, 33, 48, 80), (11, 8, 18, 80, 80), (5, 4, 20, 40, 80),
                                          (7, 5, 16, 80, 40), (3, 2, 8, 16, 16),   # packed / unpacked ragged tiles
-                                         (37, 5, 50, 128, 80), (9, 3, 17, 96, 40)])   # K up to 128: the wide layers of configs[4]
+                                         (37, 5, 50, 128, 80), (9, 3, 17, 96, 40)]    # K up to 128: the wide layers of configs[4]
+                         + LONG_L0)
 @pytest.mark.parametrize("entry,tol", [("clsr_att_l0_fwd_x6", 2e-6)])
 def test_layer0_forward_x3(Hn, G, T, Q, A0, entry, tol):
     """clsr_att_l0_fwd_x6: z0 = U[h,t] + V[r] + (a[h,t] * q[r]) . Wp with the product over three bf16 pieces: 2^-23 relative

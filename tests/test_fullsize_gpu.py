@@ -1,6 +1,7 @@
 """GPU tests at BASELINE.json's full sizes (configs[1] Taobao-shaped: 4096 positives x 5 rows, T=50;
-configs[2] Kuaishou-shaped: T=250) through size-independent properties -- the oracle is far too slow
-there -- plus an oracle check at T=250 on a small batch."""
+configs[2] Kuaishou-shaped: T=250) through size-independent properties -- the float64 oracle is far too
+slow at those batch sizes -- plus oracle checks on small batches: the whole step at T=250 on 8 positives here
+(about a second of oracle), and the 63 .. 256-step cases of tests/test_long_histories_gpu.py."""
 import os
 
 import numpy as np
@@ -106,6 +107,7 @@ def test_kuaishou_shape_runs_and_matches_oracle_on_a_slice():
     sd = dict(params)
     sd.update(O.init_bn_state(params))
     net.load_state_dict(sd)
+    net.capture_grads = True
     p64 = type(params)((k, v.double()) for k, v in params.items())
     _, _, _, ls, _, _, out = O.train_step(p64, O.init_bn_state(p64), O.init_adam(p64), 1,
                                            O.to_torch_feed(feed, dtype=torch.float64), hp)
@@ -114,6 +116,18 @@ def test_kuaishou_shape_runs_and_matches_oracle_on_a_slice():
     assert float((got["logit"].cpu().double() - out["logit"].detach().reshape(-1)).abs().max()) < 1e-3
     gl = net.read_losses()
     assert abs(gl["loss"] - float(ls["loss"])) < 1e-4 * abs(float(ls["loss"]))
+    # the five loss terms, every dense gradient and every gradient table (pre-clip, as captured), at the bars of
+    # test_catalogue_dims_match_oracle_on_a_slice
+    for k in ("loss", "data_loss", "contrastive_loss", "regular_loss", "discrepancy_loss"):
+        assert abs(gl[k] - float(ls[k])) <= 1e-4 * max(1e-3, abs(float(ls[k]))), (k, gl[k], float(ls[k]))
+    raw = out["raw_grads"]
+    gs = max(float(raw[n].abs().max()) for n in net.captured["dense"])
+    tables = {net._table_map()[k]: g for k, g in net.captured["tables"].items()}
+    assert set(tables) == set(net._table_map().values())
+    for name, g in list(net.captured["dense"].items()) + list(tables.items()):
+        exp = raw[name].reshape(g.shape)
+        d = float((g.cpu().double() - exp).abs().max())
+        assert bool(torch.isfinite(g).all()) and d <= 2e-3 * float(exp.abs().max()) + 3e-6 * gs, (name, d)
 
 
 def test_kuaishou_full_size_step_is_finite():

@@ -1,5 +1,6 @@
 """Random small shapes of the training / scoring step against the oracles (scripts/fuzz_step.py): widths that are
-not the golden 40, lengths 1..50, 1..64 positives, 2..10 rows per positive, all encoders and sibling models.  The
+not the golden 40, lengths 1..50 (63..256: tests/test_long_histories_gpu.py), 1..64 positives, 2..10 rows per positive,
+all encoders and sibling models.  The
 seeds below include the cases that exposed real limits (groups of more than 8 rows in the attention backward, bpr on
 wide embeddings, DIN with D > T).
 

@@ -35,8 +35,30 @@ def rnd(gen, *shape, scale=1.0):
     return (torch.randn(*shape, generator=gen, dtype=torch.float64) * scale)
 
 
+def chunk_edge_lens(lens, T):
+    """Rows with T > 64 (the attention tail works in 64-step chunks; the recurrences run up to max_seq_length = 256 steps):
+    whatever was drawn, the lengths at the edges are there -- T, 1, 63, 64, 65 and T - 1 (rows of fewer than
+    six histories keep their draw)."""
+    if T >= 64 and len(lens) >= 6:
+        edges = [v for v in (T, 1, 63, 64, 65, T - 1) if v <= T]
+        lens[:len(edges)] = torch.tensor(edges)
+    return lens
+
+
+def float32_reference_within_half(ref32, ref64, bars):
+    """Conditioning of a long recurrence row, an assertion on the REFERENCE alone: the float32 run of the oracle stays within
+    half of every fp32-form bar of its float64 run (inputs that miss this are ill-conditioned in float32 whatever computes
+    them; the remedy is a smaller weight scale for that row, never a wider bar)."""
+    for name, (rtol, atol) in bars.items():
+        if ref64.get(name) is None:
+            continue
+        a, b = ref32[name].detach().double(), ref64[name].detach().double()
+        worst = float(((a - b).abs() / (atol + rtol * b.abs())).max())
+        assert worst <= 0.5, "float32 oracle, %s: %.3f of the bar" % (name, worst)
+
+
 # ------------------------------------------------------------------------------- embedding
-@pytest.mark.parametrize("Hn,T,Di,Dc,G", [(37, 10, 32, 8, 5), (64, 50, 32, 8, 1), (9, 7, 96, 32, 3)])
+@pytest.mark.parametrize("Hn,T,Di,Dc,G", [(37, 10, 32, 8, 5), (64, 50, 32, 8, 1), (9, 7, 96, 32, 3), (6, 256, 32, 8, 3)])
 def test_gather_hist_fwd(Hn, T, Di, Dc, G):
     g = torch.Generator().manual_seed(1)
     Vi, Vc, k = 301, 23, 3
@@ -45,6 +67,7 @@ def test_gather_hist_fwd(Hn, T, Di, Dc, G):
     lens_h = torch.randint(1, T + 1, (Hn,), generator=g)
     lens_h[0] = 1
     lens_h[-1] = T
+    chunk_edge_lens(lens_h, T)
     lens = lens_h.repeat_interleave(G)
     valid = torch.arange(T)[None, :] < lens[:, None]
     ii = torch.where(valid, torch.randint(1, Vi, (B, T), generator=g), torch.zeros(B, T, dtype=torch.long))
@@ -96,13 +119,14 @@ def test_gather_scatter_rows_and_flags():
     assert float(cnt) == float(exp_f.sum())
 
 
-@pytest.mark.parametrize("Hn,T,Di,Dc,G,V", [(64, 50, 32, 8, 5, 40), (33, 10, 32, 8, 1, 5000), (16, 7, 96, 32, 2, 300)])
+@pytest.mark.parametrize("Hn,T,Di,Dc,G,V", [(64, 50, 32, 8, 5, 40), (33, 10, 32, 8, 1, 5000), (16, 7, 96, 32, 2, 300),
+                                           (6, 250, 32, 8, 2, 300)])
 def test_sorted_segmented_history_gradient(Hn, T, Di, Dc, G, V):
     """sort (id, position) pairs + run-length sums == index_add of every slice (heavy duplicates: V small)."""
     g = torch.Generator().manual_seed(Hn)
     D, k = Di + Dc, 3
     B = Hn * G
-    lens = torch.randint(1, T + 1, (Hn,), generator=g).repeat_interleave(G)
+    lens = chunk_edge_lens(torch.randint(1, T + 1, (Hn,), generator=g), T).repeat_interleave(G)
     idx = torch.randint(0, V, (Hn, T), generator=g).repeat_interleave(G, 0).contiguous()
     dh, dm, dr = rnd(g, Hn, T, D), rnd(g, Hn, D), rnd(g, Hn, D)
     n = Hn * T
@@ -193,6 +217,28 @@ def test_pgemm_plain_bias_stats(M, K, N):
     close(tot[1], (exp ** 2).sum(0), rtol=1e-5, atol=10 * tol * max(1.0, K / 100.0), name="colsumsq")
     Y2, _ = _pgemm(X, W, None, Y=Y.clone(), accumulate=1)
     close(Y2, 2 * exp - b, rtol=1e-5, atol=2 * tol, name="accumulate")
+
+
+@pytest.mark.parametrize("M,K,N", [(4, 48, 36), (25, 40, 80), (256, 80, 40)])
+def test_pgemm_stats_of_a_small_batch_whose_columns_sit_far_from_zero(M, K, N):
+    """Batch-norm statistics of few rows (the MLP heads of a small batch): every column of z has a spread of a hundredth of
+    its mean (DIN's masked history sums over 250 steps did that to a batch of four rows).  var = E[z^2] - mean^2 from the
+    kernel's column sums against the two-pass variance of the stored values, both in float64: sums accumulated in double
+    from the first value on lose about 2^-53 * (mean / std)^2 per addition, 1e-10 of the variance over 256 rows at
+    |mean| / std of a few hundred -- held to 1e-8; fp32 partial sums lose 2^-24 * (mean / std)^2 >= 6e-4."""
+    g = torch.Generator().manual_seed(M)
+    W = rnd(g, K, N, scale=0.3)
+    X = rnd(g, 1, K) + 0.01 * rnd(g, M, K)              # rows: a common vector + 1 % of spread
+    z0 = X.float().double() @ W.float().double()
+    b = 100.0 * z0.std(0) * torch.sign(z0.mean(0))      # every column's mean at least 100 standard deviations out
+    Y, st = _pgemm(X, W, b, stats=True)
+    z = Y.double().cpu()
+    tot = st.sum(0).cpu()
+    mean = tot[0] / M
+    var = tot[1] / M - mean * mean
+    assert float((z.mean(0).abs() / z.std(0, unbiased=False)).min()) > 30
+    close(mean, z.mean(0), rtol=1e-12, atol=0, name="mean")
+    close(var, z.var(0, unbiased=False), rtol=1e-8, atol=0, name="variance")
 
 
 @pytest.mark.parametrize("M,K,N", [(32768, 1536, 128), (40000, 512, 96), (33000, 260, 40), (32768 + 77, 1000, 128)])
@@ -363,7 +409,8 @@ def test_bn_forward_backward(M, C):
 # ------------------------------------------------------------------------------- attention tail
 @pytest.mark.parametrize("Hn,G,T,C1,Dk", [(19, 5, 10, 40, 40), (7, 1, 50, 40, 40), (3, 2, 130, 40, 40),
                                              (5, 10, 10, 40, 40), (2, 21, 7, 12, 24), (3, 3, 256, 256, 40),
-                                             (9, 1, 256, 256, 128)])
+                                             (9, 1, 256, 256, 128), (6, 3, 64, 40, 40), (6, 3, 65, 40, 40),
+                                             (6, 2, 192, 40, 40), (6, 2, 193, 40, 40)])
 def test_att_out_fwd_bwd(Hn, G, T, C1, Dk):
     g = torch.Generator().manual_seed(T)
     R = Hn * G
@@ -375,6 +422,7 @@ def test_att_out_fwd_bwd(Hn, G, T, C1, Dk):
     b_out = rnd(g, 1).requires_grad_(True)
     lens = torch.randint(1, T + 1, (Hn,), generator=g)
     lens[0] = T
+    chunk_edge_lens(lens, T)
     lens_rows = lens.repeat_interleave(G)
     h1 = torch.relu(z1 * sc + sh)
     score = (h1 @ w_out + b_out).view(R, T)
@@ -426,7 +474,7 @@ def _oracle():
 
 
 @pytest.mark.parametrize("Hn,G,T,Q,col0,ld", [(19, 5, 10, 80, 0, 80), (7, 1, 50, 40, 0, 40), (11, 5, 13, 40, 40, 80),
-                                               (5, 9, 6, 128, 128, 256)])
+                                               (5, 9, 6, 128, 128, 256), (3, 5, 65, 80, 0, 80), (2, 3, 256, 40, 40, 80)])
 def test_att_prod_bwd_on_column_blocks(Hn, G, T, Q, col0, ld):
     """Backward of the product feature a[h,t] * q[r]: da[h,t] = sum_g daq[r,t] * q[r], dq[r] = sum_t daq[r,t] * a[h,t]
     (clsr.py:368-370) -- the plain entry point and the leading-dimension one on a column block [col0, col0+Q) of
@@ -460,7 +508,27 @@ def test_att_prod_bwd_on_column_blocks(Hn, G, T, Q, col0, ld):
 # The recurrences come in two forms (clsr_gru_desc.products, csrc/rnn.hip): "fp32" = fp32-input MFMAs, bit-exact fp32
 # products -- the tolerances below; "x3" = split-bf16 products (16 significand bits per operand, errors compound over the
 # steps; relative to the float64 oracle on weights of scale 0.3) -- twenty times those tolerances.  The plain entry points (clsr_gru_fwd ...) always run the fp32 form.
+# The rows with T > 64 (up to the 256 steps a history may have) keep both factors; their inputs are first shown to be
+# well-conditioned in float32 on the reference alone (float32_reference_within_half, weight_scale).
 FORMS = [("fp32", 1.0), ("x3", 20.0)]
+
+
+# (rtol, atol) of the fp32 form per checked tensor; the long rows (T > 64) also hold the float32 ORACLE to half of them
+GRU_BARS = dict(hT=(1e-4, 2e-5), out_seq=(1e-4, 2e-5), dx=(2e-4, 2e-5), dWg_x=(2e-4, 1e-4), dbg=(2e-4, 1e-4),
+                dbc=(2e-4, 1e-4), dWg_h=(2e-4, 1e-4), dWc_h=(2e-4, 1e-4), dh0=(2e-4, 2e-5))
+T4_BARS = dict(rnn_out=(1e-4, 2e-5), dx=(2e-4, 2e-5),
+               **{k: (2e-4, 1e-4) for k in ("dkernel_x", "dkernel_m", "dbias", "d_time_kernel_w1", "d_time_kernel_w2",
+                                            "d_o_kernel_t1", "d_time_kernel_t2", "d_time_input_w1", "d_time_input_w2",
+                                            "d_time_input_bias1", "d_time_input_bias2")})
+AUGRU_BARS = {"final state": (1e-4, 2e-5), "d att": (2e-4, 2e-5), "dx": (2e-4, 2e-5), "dWg_x": (2e-4, 1e-4),
+              "dbc": (2e-4, 1e-4), "dWg_h": (2e-4, 1e-4), "dWc_h": (2e-4, 1e-4)}
+
+
+def weight_scale(T, fan_in):
+    """0.3, the scale the x3 factor is stated for; the long rows (T > 64) keep the spectral radius of the 80-row matrices
+    at that scale when the matrix is taller: at 0.3 the 128-wide recurrences are chaotic over 129 steps, the float32
+    oracle ends 60 bars from the float64 one (float32_reference_within_half)."""
+    return 0.3 * min(1.0, math.sqrt(80.0 / fan_in)) if T > 64 else 0.3
 
 
 def _scaled_close(tf, exact=()):
@@ -474,47 +542,56 @@ def _scaled_close(tf, exact=()):
 @pytest.mark.parametrize("form,tf", FORMS)
 @pytest.mark.parametrize("Hn,T,n,use_h0,seq_out", [(37, 10, 40, True, False), (16, 50, 40, False, True),
                                                    (5, 7, 40, True, True), (21, 9, 128, True, True),
-                                                   (4, 5, 64, False, False)])
+                                                   (4, 5, 64, False, False), (9, 65, 40, True, True),
+                                                   (6, 250, 40, False, True), (6, 256, 40, True, True),
+                                                   (6, 129, 128, True, True)])
 def test_gru_fwd_bwd(Hn, T, n, use_h0, seq_out, form, tf):
     O = _oracle()
     close = _scaled_close(tf)
     g = torch.Generator().manual_seed(T + Hn)
     D = 40
-    x = rnd(g, Hn, T, D).float().double().requires_grad_(True)
-    Wg = (rnd(g, D + n, 2 * n) * 0.3).requires_grad_(True)
-    bg = (rnd(g, 2 * n) * 0.1 + 1).requires_grad_(True)
-    Wc = (rnd(g, D + n, n) * 0.3).requires_grad_(True)
-    bc = (rnd(g, n) * 0.1).requires_grad_(True)
-    h0 = (rnd(g, Hn, n) * 0.5).requires_grad_(True) if use_h0 else None
+    ws = weight_scale(T, D + n)
+    x = rnd(g, Hn, T, D).float().double()
+    Wg, bg = rnd(g, D + n, 2 * n) * ws, rnd(g, 2 * n) * 0.1 + 1
+    Wc, bc = rnd(g, D + n, n) * ws, rnd(g, n) * 0.1
+    h0 = rnd(g, Hn, n) * 0.5 if use_h0 else None
     lens = torch.randint(1, T + 1, (Hn,), generator=g)
     lens[0] = T
-    params = {"gates/kernel": Wg, "gates/bias": bg, "candidate/kernel": Wc, "candidate/bias": bc}
-    h_init = h0 if use_h0 else torch.zeros(Hn, n, dtype=torch.float64)
-    outs, hT = O.dynamic_gru(x, lens, h_init, "", params)
+    chunk_edge_lens(lens, T)
     up_T, up_seq = rnd(g, Hn, n), rnd(g, Hn, T, n)
-    loss = (hT * up_T).sum() + ((outs * up_seq).sum() if seq_out else 0)
-    loss.backward()
+
+    def reference(dt):
+        x_, Wg_, bg_, Wc_, bc_, h0_ = (None if v is None else v.to(dt).clone().requires_grad_(True)
+                                       for v in (x, Wg, bg, Wc, bc, h0))
+        params = {"gates/kernel": Wg_, "gates/bias": bg_, "candidate/kernel": Wc_, "candidate/bias": bc_}
+        outs, hT = O.dynamic_gru(x_, lens, h0_ if use_h0 else torch.zeros(Hn, n, dtype=dt), "", params)
+        ((hT * up_T.to(dt)).sum() + ((outs * up_seq.to(dt)).sum() if seq_out else 0)).backward()
+        return dict(hT=hT, out_seq=outs if seq_out else None, dx=x_.grad.reshape(-1, D), dWg_x=Wg_.grad[:D],
+                    dbg=bg_.grad, dbc=bc_.grad, dWg_h=Wg_.grad[D:], dWc_h=Wc_.grad[D:], dh0=h0_.grad if use_h0 else None)
+    exp = reference(torch.float64)
+    if T > 64:
+        float32_reference_within_half(reference(torch.float32), exp, GRU_BARS)
     # kernel: Pin = x . [Wg_x | Wc_x] + [bg | bc]
-    Win = torch.cat([Wg[:D], Wc[:D]], 1).detach()
-    Pin = (x.detach().reshape(-1, D) @ Win + torch.cat([bg, bc]).detach()).float()
-    dPin_exp = None
+    Win = torch.cat([Wg[:D], Wc[:D]], 1)
+    Pin = (x.reshape(-1, D) @ Win + torch.cat([bg, bc])).float()
     f32 = torch.float32
-    d_Wg, d_Wc = dev(Wg.detach(), f32), dev(Wc.detach(), f32)
+    d_Wg, d_Wc = dev(Wg, f32), dev(Wc, f32)
     d_len = dev(lens, torch.int32)
     hT_k = torch.empty(Hn, n, device="cuda")
     out_k = torch.full((Hn, T, n), 7.0, device="cuda") if seq_out else None
     hprev = torch.zeros(Hn, T, n, device="cuda")
     gates = torch.zeros(Hn, T, 3 * n, device="cuda")
-    h0d = None if h0 is None else dev(h0.detach(), f32)
+    h0d = None if h0 is None else dev(h0, f32)
     if form == "fp32" and Hn % 2:      # (the plain entry point: always the fp32 form)
         call("clsr_gru_fwd", dev(Pin), 3 * n, d_Wg[D:], 2 * n, d_Wc[D:], n, h0d, n, d_len, 1, Hn, T, n, hT_k, out_k, hprev, gates)
     else:
         ops.rnn_multi("clsr_rnn_fwd_multi", [ops.gru_desc(n, Pin=dev(Pin), ldp=3 * n, Wgh=d_Wg[D:], ldg=2 * n, Wch=d_Wc[D:],
                                                           ldc=n, h0=h0d, h0_stride=n, hT=hT_k, out_seq=out_k, hprev=hprev,
                                                           gates=gates, products=form)], None, d_len, 1, Hn, T)
-    close(hT_k, hT, rtol=1e-4, atol=2e-5, name="hT")
+    chk = lambda got, name: close(got, exp[name], *GRU_BARS[name], name=name)
+    chk(hT_k, "hT")
     if seq_out:
-        close(out_k, outs, rtol=1e-4, atol=2e-5, name="out_seq")
+        chk(out_k, "out_seq")
     dPin = torch.full((Hn, T, 3 * n), 5.0, device="cuda")
     dh0 = torch.empty(Hn, n, device="cuda")
     if form == "fp32" and Hn % 2:
@@ -527,48 +604,64 @@ def test_gru_fwd_bwd(Hn, T, n, use_h0, seq_out, form, tf):
                                                           lddp=3 * n, dh0=dh0, products=form)], None, d_len, 1, Hn, T)
     # check through the implied parameter / input gradients
     dP = dPin.double().cpu().reshape(-1, 3 * n)
-    close(dP @ Win.T, x.grad.reshape(-1, D), rtol=2e-4, atol=2e-5, name="dx")
-    xf = x.detach().reshape(-1, D)
-    close(xf.T @ dP[:, :2 * n], Wg.grad[:D], rtol=2e-4, atol=1e-4, name="dWg_x")
-    close(dP[:, :2 * n].sum(0), bg.grad, rtol=2e-4, atol=1e-4, name="dbg")
-    close(dP[:, 2 * n:].sum(0), bc.grad, rtol=2e-4, atol=1e-4, name="dbc")
+    chk(dP @ Win.T, "dx")
+    xf = x.reshape(-1, D)
+    chk(xf.T @ dP[:, :2 * n], "dWg_x")
+    chk(dP[:, :2 * n].sum(0), "dbg")
+    chk(dP[:, 2 * n:].sum(0), "dbc")
     hp = hprev.double().cpu().reshape(-1, n)
     rh = (gates[..., :n] * hprev).double().cpu().reshape(-1, n)
-    close(hp.T @ dP[:, :2 * n], Wg.grad[D:], rtol=2e-4, atol=1e-4, name="dWg_h")
-    close(rh.T @ dP[:, 2 * n:], Wc.grad[D:], rtol=2e-4, atol=1e-4, name="dWc_h")
+    chk(hp.T @ dP[:, :2 * n], "dWg_h")
+    chk(rh.T @ dP[:, 2 * n:], "dWc_h")
     if use_h0:
-        close(dh0, h0.grad, rtol=2e-4, atol=2e-5, name="dh0")
+        chk(dh0, "dh0")
 
 
 @pytest.mark.parametrize("form,tf", FORMS)
-@pytest.mark.parametrize("Hn,T,n", [(37, 10, 40), (16, 50, 40), (19, 8, 128)])
+@pytest.mark.parametrize("Hn,T,n", [(37, 10, 40), (16, 50, 40), (19, 8, 128), (9, 65, 40), (6, 256, 40), (6, 130, 128)])
 def test_t4lstm_fwd_bwd(Hn, T, n, form, tf):
     O = _oracle()
     close = _scaled_close(tf, exact=("TT",))
     g = torch.Generator().manual_seed(T)
     D = 40
-    x = rnd(g, Hn, T, D).float().double().requires_grad_(True)
+    x = rnd(g, Hn, T, D).float().double()
     names = {"_time_input_w1": (n,), "_time_input_bias1": (n,), "_time_input_w2": (n,), "_time_input_bias2": (n,),
              "_time_kernel_w1": (D, n), "_time_kernel_t1": (n, n), "_time_bias1": (n,),
              "_time_kernel_w2": (D, n), "_time_kernel_t2": (n, n), "_time_bias2": (n,),
              "_o_kernel_t1": (n, n), "_o_kernel_t2": (n, n), "kernel": (D + n, 4 * n), "bias": (4 * n,)}
-    P = {k: (rnd(g, *s) * 0.3).requires_grad_(True) for k, s in names.items()}
+    ws = weight_scale(T, D + n)
+    Pd = {k: rnd(g, *s) * ws for k, s in names.items()}
     lens = torch.randint(1, T + 1, (Hn,), generator=g)
     lens[0] = T
+    chunk_edge_lens(lens, T)
     tfirst, tnow = rnd(g, Hn, T).float().double(), rnd(g, Hn, T).float().double()
-    out = O.time4lstm(x, tfirst, tnow, lens, "", P, n)
     up = rnd(g, Hn, T, n)
-    (out * up).sum().backward()
+
+    def reference(dt):
+        x_ = x.to(dt).clone().requires_grad_(True)
+        P_ = {k: v.to(dt).clone().requires_grad_(True) for k, v in Pd.items()}
+        out = O.time4lstm(x_, tfirst.to(dt), tnow.to(dt), lens, "", P_, n)
+        (out * up.to(dt)).sum().backward()
+        gr = {k: v.grad for k, v in P_.items()}
+        return dict(rnn_out=out, dx=x_.grad.reshape(-1, D), dkernel_x=gr["kernel"][:D], dkernel_m=gr["kernel"][D:],
+                    dbias=gr["bias"], d_time_kernel_w1=gr["_time_kernel_w1"], d_time_kernel_w2=gr["_time_kernel_w2"],
+                    d_o_kernel_t1=gr["_o_kernel_t1"], d_time_kernel_t2=gr["_time_kernel_t2"],
+                    d_time_input_w1=gr["_time_input_w1"], d_time_input_w2=gr["_time_input_w2"],
+                    d_time_input_bias1=gr["_time_input_bias1"], d_time_input_bias2=gr["_time_input_bias2"])
+    exp = reference(torch.float64)
+    if T > 64:
+        float32_reference_within_half(reference(torch.float32), exp, T4_BARS)
+    chk = lambda got, name: close(got, exp[name], *T4_BARS[name], name=name)
+    P = Pd
     f32 = torch.float32
-    d = {k: dev(v.detach(), f32) for k, v in P.items()}
+    d = {k: dev(v, f32) for k, v in P.items()}
     TT = torch.empty(Hn * T, 2 * n, device="cuda")
     call("clsr_t4_time_inputs_fwd", dev(tnow, f32), dev(tfirst, f32), T, d["_time_input_w1"], d["_time_input_bias1"],
          d["_time_input_w2"], d["_time_input_bias2"], Hn, T, n, TT)
     tn = torch.tanh(tnow[..., None] * P["_time_input_w1"] + P["_time_input_bias1"]).detach()
     tl = torch.tanh(tfirst[..., None] * P["_time_input_w2"] + P["_time_input_bias2"]).detach()
     close(TT, torch.cat([tn, tl], -1).reshape(-1, 2 * n), rtol=1e-5, atol=1e-6, name="TT")
-    xd = x.detach()
-    Pd = {k: v.detach() for k, v in P.items()}
+    xd = x
     z = xd @ Pd["kernel"][:D] + Pd["bias"]
     z[..., 3 * n:] += tn @ Pd["_o_kernel_t1"] + tl @ Pd["_o_kernel_t2"]
     tns = xd @ Pd["_time_kernel_w1"] + tn @ Pd["_time_kernel_t1"] + Pd["_time_bias1"]
@@ -588,7 +681,7 @@ def test_t4lstm_fwd_bwd(Hn, T, n, form, tf):
         ops.rnn_multi("clsr_rnn_fwd_multi", [], ops.t4_desc(n, Pin=dev(Pin), ldp=6 * n, Wm=d["kernel"][D:], ldm=4 * n,
                                                             out_seq=out_k, act=act, cst=cst, mprev=mprev, products=form,
                                                             act_tiled=tiled), d_len, 1, Hn, T)
-    close(out_k, out, rtol=1e-4, atol=2e-5, name="rnn_out")
+    chk(out_k, "rnn_out")
     dPin = torch.full((Hn, T, 6 * n), 9.0, device="cuda")
     if form == "fp32" and Hn % 2:
         call("clsr_t4lstm_bwd", act, cst, d["kernel"][D:], 4 * n, d_len, 1, Hn, T, n, dev(up, f32), dPin)
@@ -598,18 +691,17 @@ def test_t4lstm_fwd_bwd(Hn, T, n, form, tf):
                                                             act_tiled=tiled), d_len, 1, Hn, T)
     dP = dPin.double().cpu().reshape(-1, 6 * n)
     xf = xd.reshape(-1, D)
-    close(xf.T @ dP[:, :4 * n], P["kernel"].grad[:D], rtol=2e-4, atol=1e-4, name="dkernel_x")
-    close(mprev.double().cpu().reshape(-1, n).T @ dP[:, :4 * n], P["kernel"].grad[D:], rtol=2e-4, atol=1e-4,
-          name="dkernel_m")
-    close(dP[:, :4 * n].sum(0), P["bias"].grad, rtol=2e-4, atol=1e-4, name="dbias")
-    close(xf.T @ dP[:, 4 * n:5 * n], P["_time_kernel_w1"].grad, rtol=2e-4, atol=1e-4, name="d_time_kernel_w1")
-    close(xf.T @ dP[:, 5 * n:], P["_time_kernel_w2"].grad, rtol=2e-4, atol=1e-4, name="d_time_kernel_w2")
+    chk(xf.T @ dP[:, :4 * n], "dkernel_x")
+    chk(mprev.double().cpu().reshape(-1, n).T @ dP[:, :4 * n], "dkernel_m")
+    chk(dP[:, :4 * n].sum(0), "dbias")
+    chk(xf.T @ dP[:, 4 * n:5 * n], "d_time_kernel_w1")
+    chk(xf.T @ dP[:, 5 * n:], "d_time_kernel_w2")
     tnf, tlf = tn.reshape(-1, n), tl.reshape(-1, n)
-    close(tnf.T @ dP[:, 3 * n:4 * n], P["_o_kernel_t1"].grad, rtol=2e-4, atol=1e-4, name="d_o_kernel_t1")
-    close(tlf.T @ dP[:, 5 * n:], P["_time_kernel_t2"].grad, rtol=2e-4, atol=1e-4, name="d_time_kernel_t2")
+    chk(tnf.T @ dP[:, 3 * n:4 * n], "d_o_kernel_t1")
+    chk(tlf.T @ dP[:, 5 * n:], "d_time_kernel_t2")
     dx = dP[:, :4 * n] @ Pd["kernel"][:D].T + dP[:, 4 * n:5 * n] @ Pd["_time_kernel_w1"].T \
         + dP[:, 5 * n:] @ Pd["_time_kernel_w2"].T
-    close(dx, x.grad.reshape(-1, D), rtol=2e-4, atol=2e-5, name="dx")
+    chk(dx, "dx")
     # time-input parameter gradients
     dTT = torch.cat([dP[:, 3 * n:4 * n] @ Pd["_o_kernel_t1"].T + dP[:, 4 * n:5 * n] @ Pd["_time_kernel_t1"].T,
                      dP[:, 3 * n:4 * n] @ Pd["_o_kernel_t2"].T + dP[:, 5 * n:] @ Pd["_time_kernel_t2"].T], 1)
@@ -617,10 +709,10 @@ def test_t4lstm_fwd_bwd(Hn, T, n, form, tf):
     part = torch.zeros(nparts, 2, 2 * n, device="cuda")
     call("clsr_t4_time_inputs_bwd", dev(dTT, f32), TT, dev(tnow, f32), dev(tfirst, f32), T, Hn, T, n, part)
     tot = part.sum(0).double().cpu()
-    close(tot[0, :n], P["_time_input_w1"].grad, rtol=2e-4, atol=1e-4, name="d_time_input_w1")
-    close(tot[0, n:], P["_time_input_w2"].grad, rtol=2e-4, atol=1e-4, name="d_time_input_w2")
-    close(tot[1, :n], P["_time_input_bias1"].grad, rtol=2e-4, atol=1e-4, name="d_time_input_bias1")
-    close(tot[1, n:], P["_time_input_bias2"].grad, rtol=2e-4, atol=1e-4, name="d_time_input_bias2")
+    chk(tot[0, :n], "d_time_input_w1")
+    chk(tot[0, n:], "d_time_input_w2")
+    chk(tot[1, :n], "d_time_input_bias1")
+    chk(tot[1, n:], "d_time_input_bias2")
 
 
 # ------------------------------------------------------------------------------- heads
@@ -873,7 +965,8 @@ def test_touched_row_compaction_pack_unpack(V, C, frac):
 
 # ------------------------------------------------------------------------------- sibling-model kernels
 @pytest.mark.parametrize("form,tf", FORMS)
-@pytest.mark.parametrize("Hn,G,T,n", [(7, 5, 10, 40), (5, 1, 50, 40), (3, 4, 9, 128)])
+@pytest.mark.parametrize("Hn,G,T,n", [(7, 5, 10, 40), (5, 1, 50, 40), (3, 4, 9, 128), (6, 2, 65, 40), (6, 3, 256, 40),
+                                      (6, 2, 129, 128)])
 def test_attentional_gru_fwd_bwd(Hn, G, T, n, form, tf):
     """clsr_rnn_*_multi with clsr_gru_desc.att (DIEN's VecAttGRUCell): one sequence per candidate row reading the
     input projections / length of its history (in_div = G), update gate scaled by 1 - att; backward incl. d att."""
@@ -882,47 +975,55 @@ def test_attentional_gru_fwd_bwd(Hn, G, T, n, form, tf):
 
     g = torch.Generator().manual_seed(T + Hn + n)
     B, Hin = Hn * G, 24
-    x = rnd(g, Hn, T, Hin).requires_grad_(True)
-    Wg = (rnd(g, Hin + n, 2 * n) * 0.3).requires_grad_(True)
-    bg = (rnd(g, 2 * n) * 0.1 + 1).requires_grad_(True)
-    Wc = (rnd(g, Hin + n, n) * 0.3).requires_grad_(True)
-    bc = (rnd(g, n) * 0.1).requires_grad_(True)
-    att = torch.rand(B, T, generator=g, dtype=torch.float64).requires_grad_(True)
+    ws = weight_scale(T, Hin + n)
+    x = rnd(g, Hn, T, Hin)
+    Wg, bg = rnd(g, Hin + n, 2 * n) * ws, rnd(g, 2 * n) * 0.1 + 1
+    Wc, bc = rnd(g, Hin + n, n) * ws, rnd(g, n) * 0.1
+    att = torch.rand(B, T, generator=g, dtype=torch.float64)
     lens = torch.randint(1, T + 1, (Hn,), generator=g)
     lens[0] = T
-    params = {"gates/kernel": Wg, "gates/bias": bg, "candidate/kernel": Wc, "candidate/bias": bc}
-    xr = x.repeat_interleave(G, 0)
-    hT = S.dynamic_augru(xr, att, lens.repeat_interleave(G), "", params, n)
+    chunk_edge_lens(lens, T)
     up = rnd(g, B, n)
-    (hT * up).sum().backward()
+
+    def reference(dt):
+        x_, Wg_, bg_, Wc_, bc_, att_ = (v.to(dt).clone().requires_grad_(True) for v in (x, Wg, bg, Wc, bc, att))
+        params = {"gates/kernel": Wg_, "gates/bias": bg_, "candidate/kernel": Wc_, "candidate/bias": bc_}
+        hT = S.dynamic_augru(x_.repeat_interleave(G, 0), att_, lens.repeat_interleave(G), "", params, n)
+        (hT * up.to(dt)).sum().backward()
+        return {"final state": hT, "d att": att_.grad, "dx": x_.grad.reshape(-1, Hin), "dWg_x": Wg_.grad[:Hin],
+                "dbc": bc_.grad, "dWg_h": Wg_.grad[Hin:], "dWc_h": Wc_.grad[Hin:]}
+    exp = reference(torch.float64)
+    if T > 64:
+        float32_reference_within_half(reference(torch.float32), exp, AUGRU_BARS)
+    chk = lambda got, name: close(got, exp[name], *AUGRU_BARS[name], name=name)
     f32 = torch.float32
-    Win = torch.cat([Wg[:Hin], Wc[:Hin]], 1).detach()
-    Pin = dev((x.detach().reshape(-1, Hin) @ Win + torch.cat([bg, bc]).detach()).float())     # history level
-    d_Wg, d_Wc, d_len, d_att = dev(Wg.detach(), f32), dev(Wc.detach(), f32), dev(lens, torch.int32), dev(att.detach(), f32)
+    Win = torch.cat([Wg[:Hin], Wc[:Hin]], 1)
+    Pin = dev((x.reshape(-1, Hin) @ Win + torch.cat([bg, bc])).float())     # history level
+    d_Wg, d_Wc, d_len, d_att = dev(Wg, f32), dev(Wc, f32), dev(lens, torch.int32), dev(att, f32)
     hT_k = torch.empty(B, n, device="cuda")
     hprev, gates = torch.zeros(B, T, n, device="cuda"), torch.zeros(B, T, 3 * n, device="cuda")
     d = ops.gru_desc(n, Pin=Pin, ldp=3 * n, Wgh=d_Wg[Hin:], ldg=2 * n, Wch=d_Wc[Hin:], ldc=n, hT=hT_k, hprev=hprev,
                      gates=gates, att=d_att, in_div=G, products=form)
     ops.rnn_multi("clsr_rnn_fwd_multi", [d], None, d_len, 1, B, T)
-    close(hT_k, hT, rtol=1e-4, atol=2e-5, name="final state")
+    chk(hT_k, "final state")
     dPin = torch.full((B, T, 3 * n), 5.0, device="cuda")
     datt = torch.zeros(B, T, device="cuda")
     db = ops.gru_desc(n, Wgh=d_Wg[Hin:], ldg=2 * n, Wch=d_Wc[Hin:], ldc=n, hprev=hprev, gates=gates, dhT=dev(up, f32),
                       dPin=dPin, lddp=3 * n, att=d_att, datt=datt, in_div=G, products=form)
     ops.rnn_multi("clsr_rnn_bwd_multi", [db], None, d_len, 1, B, T)
-    close(datt, att.grad, rtol=2e-4, atol=2e-5, name="d att")
+    chk(datt, "d att")
     dP = dPin.double().cpu().reshape(Hn, G, T, 3 * n).sum(1).reshape(-1, 3 * n)      # rows of a group share the inputs
-    close(dP @ Win.T, x.grad.reshape(-1, Hin), rtol=2e-4, atol=2e-5, name="dx")
-    close(x.detach().reshape(-1, Hin).T @ dP[:, :2 * n], Wg.grad[:Hin], rtol=2e-4, atol=1e-4, name="dWg_x")
-    close(dP[:, 2 * n:].sum(0), bc.grad, rtol=2e-4, atol=1e-4, name="dbc")
+    chk(dP @ Win.T, "dx")
+    chk(x.reshape(-1, Hin).T @ dP[:, :2 * n], "dWg_x")
+    chk(dP[:, 2 * n:].sum(0), "dbc")
     dPr = dPin.double().cpu().reshape(-1, 3 * n)
     hp = hprev.double().cpu().reshape(-1, n)
     rh = (gates[..., :n] * hprev).double().cpu().reshape(-1, n)
-    close(hp.T @ dPr[:, :2 * n], Wg.grad[Hin:], rtol=2e-4, atol=1e-4, name="dWg_h")
-    close(rh.T @ dPr[:, 2 * n:], Wc.grad[Hin:], rtol=2e-4, atol=1e-4, name="dWc_h")
+    chk(hp.T @ dPr[:, :2 * n], "dWg_h")
+    chk(rh.T @ dPr[:, 2 * n:], "dWc_h")
 
 
-@pytest.mark.parametrize("Hn,T,D", [(9, 10, 40), (4, 130, 40), (3, 7, 128)])
+@pytest.mark.parametrize("Hn,T,D", [(9, 10, 40), (4, 130, 40), (3, 7, 128), (3, 64, 40), (3, 65, 40), (2, 256, 128)])
 def test_asvd_attention_fwd_bwd(Hn, T, D):
     """A2SVD attention (base_model.py:595-625): unmasked softmax over T of (x.A).query, output sum_t w x."""
     g = torch.Generator().manual_seed(Hn * T)
@@ -984,8 +1085,12 @@ def test_weights_softmax_bwd_row_scaling_and_products():
     assert float((wide[:, :D] - 9.0).abs().max()) == 0 and float((wide[:, 2 * D:] - 9.0).abs().max()) == 0
 
 
+# histories past one 64-step chunk of the attention tail, up to max_seq_length = 256 (also tests/test_att_bwd_x3_gpu.py, test_x3_gpu.py)
+LONG_L0 = [(3, 5, 65, 80, 80), (2, 8, 256, 80, 80), (4, 1, 250, 40, 80)]
+
+
 @pytest.mark.parametrize("Hn,G,T,Q,A0", [(37, 5, 50, 80, 80), (64, 1, 50, 40, 80), (9, 8, 7, 44, 36), (6, 3, 17, 24, 40),
-                                         (1, 5, 1, 80, 80), (130, 2, 33, 48, 80)])
+                                         (1, 5, 1, 80, 80), (130, 2, 33, 48, 80)] + LONG_L0)
 def test_fused_layer0_backward_reductions_fp32(Hn, G, T, Q, A0):
     """clsr_att_l0_bwd: da, dq, dU, dV of the re-associated first attention layer from one pass over dz0 on the fp32
     matrix pipe (daq = dz0 . Wp^T never stored) == float64, and == the three kernels it replaces."""
@@ -1029,7 +1134,7 @@ def test_fused_layer0_backward_reductions_fp32(Hn, G, T, Q, A0):
 
 @pytest.mark.parametrize("Hn,G,T,Q,A0", [(37, 5, 50, 80, 80), (64, 1, 50, 40, 80), (9, 8, 7, 44, 36), (6, 3, 17, 24, 40),
                                          (1, 5, 1, 80, 80), (2100, 2, 33, 48, 80), (11, 8, 18, 80, 80), (5, 4, 20, 40, 80),
-                                         (7, 5, 16, 80, 40), (3, 2, 8, 16, 16)])   # packed / unpacked ragged tiles
+                                         (7, 5, 16, 80, 40), (3, 2, 8, 16, 16)] + LONG_L0)   # packed / unpacked ragged tiles
 def test_attention_layer0_forward_one_wave_per_history(Hn, G, T, Q, A0):
     """clsr_att_l0_fwd: z0 = U[h,t] + V[r] + (a[h,t] * q[r]) . Wp with the batch-norm column sums == float64, and ==
     clsr_pgemm with the Xmul prologue / addU + addV epilogue (the kernel it replaces)."""
