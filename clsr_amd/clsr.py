@@ -665,6 +665,11 @@ class DIENModel(_SiblingModel):
     kind = "dien"
 
 
+class CaserModel(_SiblingModel):
+    """Reference ``CaserModel`` (models/sequential/caser.py): hparams ``L``, ``n_v``, ``n_h`` (``T`` is read and unused)."""
+    kind = "caser"
+
+
 class SLI_RECModel(_SiblingModel):
     """Reference ``SLI_RECModel`` (models/sequential/sli_rec.py)."""
     kind = "sli_rec"

@@ -130,6 +130,9 @@ def init_tensor(kind, shape, hp, gen):
         fan_out = shape[1] if len(shape) > 1 else shape[0]
         lim = math.sqrt(6.0 / (fan_in + fan_out))
         return (torch.rand(shape, generator=gen) * 2 - 1) * lim
+    if kind == "glorot_conv":       # tf glorot_uniform on a conv kernel [width, in, out]: fans scaled by the width
+        lim = math.sqrt(6.0 / (shape[0] * (shape[1] + shape[2])))
+        return (torch.rand(shape, generator=gen) * 2 - 1) * lim
     if kind == "one":
         return torch.ones(shape)
     return torch.zeros(shape)
@@ -140,7 +143,7 @@ def init_tensor(kind, shape, hp, gen):
 # (examples/00_quick_start/sequential.py:94-205): they share the embedding layer and the logit MLP of
 # SequentialBaseModel (sequential_base_model.py:55-74,354-452) and differ in _build_seq_graph.
 SIB_TABLES = OrderedDict([("item", EMB + "item_embedding"), ("cate", EMB + "cate_embedding")])
-SIBLINGS = ("gru4rec", "din", "sli_rec", "a2svd", "dien")
+SIBLINGS = ("gru4rec", "din", "sli_rec", "a2svd", "dien", "caser")
 
 
 def sibling_kind(model_type):
@@ -164,11 +167,26 @@ def sibling_scopes(kind):
                     gru2="sequential/gru2/vec_att_gru_cell/")
     if kind == "a2svd":        # asvd.py:31-38
         return dict(asvd="sequential/a2svd/Attention_layer/")
+    if kind == "caser":        # caser.py:43,60-65: variable_scope("caser") / "item" | "cate" / "vertical" | "horizonal" (sic)
+        return dict(item="sequential/caser/item/", cate="sequential/caser/cate/")
     raise ValueError("unknown sibling model %r" % (kind,))
 
 
+def caser_specs(scope, Dx, hp):
+    """Variables of ``_add_cnn`` for one table (caser.py:49-74,94-106), in creation order: tf.layers.conv1d kernels are
+    [width, in channels, filters].  The vertical path convolves the TRANSPOSED history [B, Dx, T] with width Dx: kernel
+    [Dx, T, n_v].  The scope sets no initializer: conv1d's default glorot_uniform, zero biases."""
+    T, L, n_v, n_h = int(hp.max_seq_length), int(hp.L), int(hp.n_v), int(hp.n_h)
+    v = scope + "vertical/conv_%d/" % Dx
+    specs = [(v + "kernel", (Dx, T, n_v), "glorot_conv"), (v + "bias", (n_v,), "zero")]
+    for h in range(1, L + 1):
+        c = scope + "horizonal/conv_%d/" % h
+        specs += [(c + "kernel", (h, Dx, n_h), "glorot_conv"), (c + "bias", (n_h,), "zero")]
+    return specs
+
+
 def sibling_specs(dims, hp, kind):
-    """Ordered (name, shape, init kind) of every variable of GRU4Rec / DIN / SLi-Rec."""
+    """Ordered (name, shape, init kind) of every variable of GRU4Rec / DIN / SLi-Rec / A2SVD / DIEN / Caser."""
     Vu, Vi, Vc = dims["Vu"], dims["Vi"], dims["Vc"]
     Di, Dc, Du, H = hp.item_embedding_dim, hp.cate_embedding_dim, hp.user_embedding_dim, hp.hidden_size
     D = Di + Dc
@@ -180,6 +198,9 @@ def sibling_specs(dims, hp, kind):
     elif kind == "a2svd":
         specs += [(sc["asvd"] + "attention_mat", (D, D), "w"), (sc["asvd"] + "query", (hp.attention_size,), "w")]
         out_dim = 2 * D
+    elif kind == "caser":
+        specs += caser_specs(sc["item"], Di, hp) + caser_specs(sc["cate"], Dc, hp)
+        out_dim = 2 * (int(hp.n_v) + int(hp.L) * int(hp.n_h)) + D
     elif kind == "dien":
         att = list(hp.att_fcn_layer_sizes)
         specs += gru_specs(sc["gru1"], D, H)

@@ -1,4 +1,4 @@
-"""GRU4Rec, DIN, DIEN, SLi-Rec and A2SVD on the kernels of the CLSR step.
+"""GRU4Rec, DIN, DIEN, SLi-Rec, A2SVD and Caser on the kernels of the CLSR step.
 
 The reference's quick-start trains these from the same script as CLSR (examples/00_quick_start/sequential.py:94-205);
 they sit on the same ``SequentialBaseModel`` trunk (embeddings + involved-row regulariser + logit MLP + softmax loss +
@@ -11,15 +11,22 @@ clip + Adam) and differ in ``_build_seq_graph``:
                                                          per candidate row) final state, ++ target, history sum, product
   SLI_RECModel   models/sequential/sli_rec.py:25-147     A2SVD attention (unmasked), Time4LSTM over the item embedding,
                                                          _attention_fcn(target, rnn_outputs), alpha fusion
+  CaserModel     models/sequential/caser.py:37-106       per table: one dense contraction of the flattened history
+                                                         ("vertical") ++ width-1..L convolutions, ReLU, max over time
+                                                         ("horizonal"), ++ target -- no mask anywhere
 
 ``SeqNet`` re-uses CLSRNet wholesale -- parameter store, packed weights, the position-tiled GEMMs, the fused recurrence
 launch, the attention block (forward and backward), the MLP heads, sorted segmented embedding gradients, regularisers,
 clip, Adam, the stream structure, data parallelism -- and only re-states the three graphs and their backward passes.
-New device code: the A2SVD attention and the length scaling of DIN's history sum (csrc/sibling.hip).
+New device code: the A2SVD attention and the length scaling of DIN's history sum (csrc/sibling.hip); Caser's
+convolutions, forward and backward (csrc/caser.hip).
 
 A2SVD and GRU4Rec, whose one ``_fcn_net`` is the logit MLP, also train with the config's dropout (``user_dropout``,
-``dropout``: csrc/dropout.hip, ``CLSRNet._mlp_fwd_drop``); the other three refuse it by name.
+``dropout``: csrc/dropout.hip, ``CLSRNet._mlp_fwd_drop``); the others refuse it by name
+(Caser for now: its tail is the same one).
 """
+import copy
+
 import numpy as np
 import torch
 
@@ -35,9 +42,15 @@ class SeqNet(CLSRNet):
     def __init__(self, hp, dims, kind=None, **kw):
         self.kind = sibling_kind(kind if kind is not None else hp.model_type)
         if self.kind is None:
-            raise ValueError("SeqNet builds gru4rec / din / dien / sli_rec / a2svd, got %r" % (kind or hp.model_type,))
+            raise ValueError("SeqNet builds gru4rec / din / dien / sli_rec / a2svd / caser, got %r"
+                             % (kind or hp.model_type,))
         self.sc = sibling_scopes(self.kind)
+        if self.kind == "caser" and hp.hidden_size is None:
+            hp = copy.copy(hp)
+            hp.hidden_size = 0         # (caser.yaml has no recurrent encoder: nothing reads the width)
         super(SeqNet, self).__init__(hp, dims, **kw)
+        if self.kind == "caser":
+            self._caser_setup()
         if self.kind == "sli_rec":
             self.enc_in = self.Di          # Time4LSTM reads the item embedding only (sli_rec.py:43-57)
         self.split_query = False
@@ -49,7 +62,11 @@ class SeqNet(CLSRNet):
             bad.append("enable_BN must be True")
         if list(hp.activation) != ["relu"] * len(hp.activation):
             bad.append("activation must be relu")
-        self._check_dropout(hp, bad, mlp_only=self.kind in ("a2svd", "gru4rec"))
+        self._check_dropout(hp, bad, mlp_only=self.kind in ("a2svd", "gru4rec", "caser"))
+        if self.kind == "caser" and self.dropout_in_effect(hp):
+            # (its one _fcn_net is the logit MLP too: the tail of A2SVD / GRU4Rec would serve; not wired up or tested yet)
+            bad.append("user_dropout with dropout %r: dropout in Caser's logit MLP is not implemented yet"
+                       % ([float(d) for d in hp.dropout],))
         if any(float(getattr(hp, k)) != 0.0 for k in ("embed_l1", "layer_l1", "cross_l1", "cross_l2")):
             bad.append("l1 / cross regularisers must be 0")
         if hp.loss != "softmax" or hp.method != "classification":
@@ -67,10 +84,51 @@ class SeqNet(CLSRNet):
             if hp.attention_size != D:
                 bad.append("attention_size must equal item+cate dims (tensordot with query, base_model.py:622)")
         bad += self._shape_limits(hp, rnn=self.kind in ("gru4rec", "sli_rec", "dien"))
+        if self.kind == "caser":
+            bad += self._caser_limits(hp, bool(bad))
         if self.kind in ("a2svd", "sli_rec") and int(hp.attention_size) % 4:
             bad.append("attention_size must be a multiple of 4")
         if bad:
             raise NotImplementedError("%s HIP path does not support: %s" % (self.kind, "; ".join(bad)))
+
+    @staticmethod
+    def _caser_limits(hp, trunk_bad):
+        """Caser's own keys, by name; the kernels' say on the whole shape (csrc/caser.hip) once each key is in range."""
+        bad = []
+        if any(getattr(hp, k, None) is None for k in ("L", "n_v", "n_h")):
+            return ["L, n_v and n_h must be set (caser.yaml: L 3, n_v 128, n_h 128)"]
+        L, n_v, n_h, T = int(hp.L), int(hp.n_v), int(hp.n_h), int(hp.max_seq_length)
+        fmax = query("clsr_caser_max_filters")
+        if not 1 <= L <= T:
+            bad.append("L must lie in 1..max_seq_length (%d), got %d" % (T, L))
+        for k, v in (("n_v", n_v), ("n_h", n_h)):
+            if v <= 0 or v % 4 or v > fmax:
+                bad.append("%s must be a positive multiple of 4, at most %d, got %d" % (k, fmax, v))
+        if not bad and not trunk_bad and not query("clsr_caser_supported", T, int(hp.item_embedding_dim),
+                                                   int(hp.cate_embedding_dim), L, n_v, n_h):
+            bad.append("L = %d with embedding dims %d / %d and n_v, n_h = %d, %d: a chunk of 8 positions plus L - 1 rows of "
+                       "the wider table must fit 64 KB of LDS, and n_v + 3 L n_h must be at most 16 384"
+                       % (L, int(hp.item_embedding_dim), int(hp.cate_embedding_dim), n_v, n_h))
+        return bad
+
+    def _caser_setup(self):
+        """Caser's shape constants and the two parameter blocks the kernels address by offset: the variables of a table are
+        consecutive in the dense buffer, in the layout csrc/caser.hip states (checked here, once)."""
+        hp = self.hp
+        self.cz_L, self.cz_nv, self.cz_nh = int(hp.L), int(hp.n_v), int(hp.n_h)
+        self.cz_T = int(hp.max_seq_length)
+        self.cz_pw = self.cz_nv + self.cz_L * self.cz_nh          # pooled columns of one table
+        self.cz_W, self.cz_dW = {}, {}
+        for key, Dx in (("item", self.Di), ("cate", self.Dc)):
+            names = [n for n, _, _ in self.specs if n.startswith(self.sc[key])]
+            first, o = self.P[names[0]], 0
+            for n in names:
+                if self.P[n].data_ptr() != first.data_ptr() + 4 * o:
+                    raise AssertionError("Caser parameter block of %s is not contiguous at %s" % (key, n))
+                o += self.P[n].numel()
+            if o != query("clsr_caser_param_floats", self.cz_T, Dx, self.cz_L, self.cz_nv, self.cz_nh):
+                raise AssertionError("Caser parameter block of %s: %d floats" % (key, o))
+            self.cz_W[key], self.cz_dW[key] = first, self.Gd[names[0]]
 
     def _param_specs(self):
         return sibling_specs(self.dims, self.hp, self.kind)
@@ -115,6 +173,8 @@ class SeqNet(CLSRNet):
     @property
     def out_dim(self):
         """Width of ``model_output`` (the logit MLP's input)."""
+        if self.kind == "caser":
+            return 2 * (int(self.hp.n_v) + int(self.hp.L) * int(self.hp.n_h)) + self.D
         return {"gru4rec": self.H + self.D, "din": 3 * self.D, "sli_rec": 2 * self.D, "a2svd": 2 * self.D,
                 "dien": 3 * self.D + self.H}[self.kind]
 
@@ -240,6 +300,22 @@ class SeqNet(CLSRNet):
             call("clsr_copy_cols", hsum, D, 0, G, B, D, mo, W, D, 0)
             call("clsr_copy_cols", att, D, 0, 1, B, D, mo, W, 2 * D, 0)
             out.update(hist_sum=hsum, att_fea=att, w_att=self._buf("st.wts", B, T))
+        elif kind == "caser":
+            if T != self.cz_T:
+                raise ValueError("Caser's vertical kernels are [Dx, max_seq_length, n_v]: the feed must hold "
+                                 "max_seq_length = %d steps, got %d" % (self.cz_T, T))
+            aux()
+            PW2 = 2 * self.cz_pw
+            pooled = self._buf("cz.pooled", Hn, PW2)
+            am = [self._buf("cz.argmax." + k, Hn, self.cz_L, self.cz_nh, dtype=torch.int32) for k in ("item", "cate")]
+            # per pool: number of positions tied with the maximum | their bit mask (the backward splits evenly, as TF does)
+            ti = [self._buf("cz.ties." + k, Hn, self.cz_L, self.cz_nh, 1 + (T + 31) // 32, dtype=torch.int32)
+                  for k in ("item", "cate")]
+            call("clsr_caser_hconv_fwd", hist, D, Hn, T, Di, Dc, self.cz_W["item"], self.cz_W["cate"], self.cz_L,
+                 self.cz_nv, self.cz_nh, pooled, PW2, am[0], am[1], ti[0], ti[1])
+            call("clsr_copy_cols", pooled, PW2, 0, G, B, PW2, mo, W, 0, 0)
+            call("clsr_copy_cols", target, D, 0, 1, B, D, mo, W, PW2, 0)
+            out.update(pooled=pooled, argmax_item=am[0], argmax_cate=am[1], ties_item=ti[0], ties_cate=ti[1])
         else:
             NX = self.NX
             t = sc["t4"]
@@ -392,6 +468,18 @@ class SeqNet(CLSRNet):
             call("clsr_copy_cols", dq, D, 0, 1, B, D, dtarget, D, 0, 1)
             # d(masked sum) reaches every valid step: hand it to the embedding backward as len * d(mean)
             call("clsr_scale_rows_by_len", dsum, seq_len, ls, Hn, D, dM, 0)
+            self._dw_flush()
+        elif kind == "caser":
+            PW2 = 2 * self.cz_pw
+            dpool = self._buf("cz.dpool", Hn, PW2)
+            call("clsr_group_sum_cols", dmo, W, 0, G, Hn, PW2, dpool, PW2, 0, 0)
+            call("clsr_copy_cols", dmo, W, PW2, 1, B, D, dtarget, D, 0, 1)
+            shape = (Hn, T, Di, Dc, self.cz_L, self.cz_nv, self.cz_nh)
+            ws = self._buf("cz.ws", query("clsr_caser_hconv_bwd_workspace_floats", *shape))
+            # d hist of both paths (padded steps included: their rows reach table row 0) and every kernel / bias gradient
+            call("clsr_caser_hconv_bwd", dpool, PW2, out["pooled"], PW2, out["argmax_item"], out["argmax_cate"],
+                 out["ties_item"], out["ties_cate"], hist, D, Hn, T, Di, Dc, self.cz_W["item"], self.cz_W["cate"],
+                 self.cz_L, self.cz_nv, self.cz_nh, dhist, self.cz_dW["item"], self.cz_dW["cate"], ws)
             self._dw_flush()
         else:
             NX = self.NX

@@ -751,6 +751,35 @@ int clsr_softmax_weights_bwd(const float* dw, const float* wts, const int* seq_l
                              int T, float* ds, float* b_partial, void* stream);
 int clsr_mul_rows(const float* a, int lda, const float* b, int ldb, int G, long R, int C, float* out, int ldo,
                   void* stream);
+/* Caser (models/sequential/caser.py, csrc/caser.hip): per table (item | cate) over the history lookup X [Hn, T, Dx] --
+ * columns 0 .. Di (item) and Di .. Di + Dc (cate) of hist [Hn, T, ldh] -- with NO mask (padded steps hold embedding row 0):
+ *   out_v[b, f]    = relu(bv[f] + sum_{t, d} X[b, t, d] Wv[d, t, f])                                        f < n_v
+ *   out_h[b, h, f] = relu(max_{t <= T - h} (bh_h[f] + sum_{j < h, d} X[b, t + j, d] Wh_h[j, d, f]))   h = 1 .. L, f < n_h
+ * Wi / Wc: the table's parameter block  Wv [Dx][T][n_v] | bv | Wh_1 [1][Dx][n_h] | bh_1 | ... | Wh_L | bh_L
+ * (clsr_caser_param_floats floats, no padding: n_v, n_h multiples of 4); dWi / dWc: the gradient block, same layout.
+ * pooled [Hn, ldp]: [item out_v | item out_h(1..L) | cate out_v | cate out_h(1..L)], written by the forward with the
+ * FIRST position of every pool's maximum in argmax_i / argmax_c [Hn, L, n_h] and, in ties_i / ties_c
+ * [Hn, L, n_h, 1 + ceil(T / 32)], the number of positions whose value EQUALS the maximum | their bit mask (bit t of word
+ * 1 + t / 32; bits below the first maximum are stale); c_h never goes to memory.
+ * Backward, from dpool (same columns as pooled) gated by pooled > 0, a pool's gradient split evenly among its tied
+ * positions as tf.reduce_max does: d hist (accumulated, one owner thread per element), weight and bias gradients
+ * (written; per-slice partial sums in workspace reduced in ascending order).  No atomics: two runs give bit-identical
+ * results.  fp32 FMA chains in a fixed order per output element.
+ * clsr_caser_supported: 1 if the kernels take the shape (T <= 256, 1 <= L <= T, n_v / n_h positive multiples of 4 up
+ * to clsr_caser_max_filters(), an LDS chunk of >= 8 positions + L - 1 rows of the wider table within 64 KB, and
+ * n_v + 3 L n_h <= 16 384 words of LDS in the backward pass). */
+int clsr_caser_supported(int T, int Di, int Dc, int L, int n_v, int n_h);
+int clsr_caser_max_filters(void);
+long clsr_caser_param_floats(int T, int Dx, int L, int n_v, int n_h);
+int clsr_caser_hconv_fwd(const float* hist, int ldh, long Hn, int T, int Di, int Dc, const float* Wi, const float* Wc,
+                         int L, int n_v, int n_h, float* pooled, int ldp, int* argmax_i, int* argmax_c, int* ties_i,
+                         int* ties_c, void* stream);
+int clsr_caser_hconv_bwd_parts(long Hn, int T, int Di, int Dc, int L, int n_v, int n_h);
+long clsr_caser_hconv_bwd_workspace_floats(long Hn, int T, int Di, int Dc, int L, int n_v, int n_h);
+int clsr_caser_hconv_bwd(const float* dpool, int ldd, const float* pooled, int ldp, const int* argmax_i,
+                         const int* argmax_c, const int* ties_i, const int* ties_c, const float* hist, int ldh,
+                         long Hn, int T, int Di, int Dc, const float* Wi, const float* Wc, int L, int n_v, int n_h,
+                         float* dhist, float* dWi, float* dWc, float* workspace, void* stream);
 
 /* ---- dropout of _fcn_net's hidden layers (csrc/dropout.hip, csrc/philox.h): base_model.py _active_layer, user_dropout --
  * a = relu(dropout(bn(z))), keep = 1 - dropout[layer].  The mask is a function of (seed, draw, layer, GLOBAL row, column):

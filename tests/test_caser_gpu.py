@@ -1,0 +1,257 @@
+"""GPU parity of Caser (clsr_amd/seqnet.py kind "caser", csrc/caser.hip) against its torch-CPU oracle
+(tests/caser_oracle.py, float64, autograd): the checks and tolerances of tests/test_siblings_gpu.py -- forward values,
+loss terms, every dense and table gradient with the reference's clip norms, the Adam step, the BN moving statistics --
+plus the pooling's selection: the device's first-maximum positions and ReLU gates are compared with the oracle's, a
+difference must be a near-tie within the fp32 summation bound, and at most 4 pools per case may need the device's
+selection handed to the oracle (the committed fixture needs none: tests/test_caser_cpu.py)."""
+import copy
+import os
+import pickle
+
+import numpy as np
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+
+import caser_oracle as O  # noqa: E402
+from clsr_amd.params import SIB_TABLES  # noqa: E402
+from clsr_amd.seqnet import SeqNet  # noqa: E402
+
+EPS = 2.0 ** -23
+
+
+def _dims(hp):
+    return dict(Vu=len(pickle.load(open(hp.user_vocab, "rb"))), Vi=len(pickle.load(open(hp.item_vocab, "rb"))),
+                Vc=len(pickle.load(open(hp.cate_vocab, "rb"))))
+
+
+def _feed(golden_dir, name, b=0):
+    g = np.load(os.path.join(golden_dir, name))
+    pre = "b%d_" % b
+    return {k[len(pre):]: g[k] for k in g.files if k.startswith(pre)}
+
+
+def _close(got, exp, rtol, atol, name):
+    got = torch.as_tensor(got).detach().double().cpu().reshape(-1)
+    exp = torch.as_tensor(exp).detach().double().cpu().reshape(-1)
+    assert got.shape == exp.shape, (name, got.shape, exp.shape)
+    err = (got - exp).abs()
+    excess = float((err - (atol + rtol * exp.abs())).max())
+    assert excess <= 0, "%s: max abs err %.3e, max |exp| %.3e" % (name, float(err.max()), float(exp.abs().max()))
+
+
+def _setup(hp, dims, dedup):
+    params32 = O.init_params(dims, hp, **O.FIXTURE)
+    net = SeqNet(hp, dims, kind="caser", device="cuda:0", seed=0, dedup_histories=dedup)
+    sd = dict(params32)
+    sd.update(O.init_bn_state(params32))
+    net.load_state_dict(sd, strict=True)
+    params64 = type(params32)((k, v.double()) for k, v in params32.items())
+    return net, params64
+
+
+def _device_selection(got, hp, G):
+    """The step's first-maximum positions and ReLU gates, one row per feed row: per table gate_v / pos / gate."""
+    L, n_v, n_h = int(hp.L), int(hp.n_v), int(hp.n_h)
+    PW = n_v + L * n_h
+    pooled = got["pooled"].cpu()
+    sel = {}
+    for i, key in enumerate(("item", "cate")):
+        blk = pooled[:, i * PW:(i + 1) * PW]
+        sel[key] = dict(gate_v=(blk[:, :n_v] > 0).repeat_interleave(G, 0),
+                        gate=(blk[:, n_v:].reshape(-1, L, n_h) > 0).repeat_interleave(G, 0),
+                        pos=got["argmax_" + key].cpu().long().repeat_interleave(G, 0))
+    return sel
+
+
+def _overrides(dev, out, params, hp):
+    """Pools / gates where the device and the oracle select differently: each must be a near-tie within the fp32 summation
+    bound K * 2^-23 * sum |x . w| of the window.  -> (select argument of the oracle, number of overridden pools)"""
+    own = O.selection(out, hp)
+    select, n = {}, 0
+    for key in ("item", "cate"):
+        d, o, inf = dev[key], own[key], out["info"][key]
+        a_v, K_v, a_h, K_h = O.abs_terms(out["hist"][key], params, hp, key)
+        mask_v = d["gate_v"] != o["gate_v"]
+        for r, f in mask_v.nonzero().tolist():
+            assert abs(float(inf["pre_v"][r, f])) < K_v * EPS * float(a_v[r, f]), \
+                "%s vertical gate row %d filter %d: value %.3e is no near-tie" % (key, r, f, float(inf["pre_v"][r, f]))
+        mask = (d["pos"] != o["pos"]) | (d["gate"] != o["gate"])
+        for r, h0, f in mask.nonzero().tolist():
+            c, a = inf["c"][h0][r, :, f], a_h[h0][r, :, f]
+            pd, po = int(d["pos"][r, h0, f]), int(o["pos"][r, h0, f])
+            bound = K_h[h0] * EPS * float(min(a[pd], a[po]))
+            assert abs(float(c[pd] - c[po])) < bound, \
+                "%s row %d width %d filter %d: device window %d, oracle window %d, values %.9e / %.9e" % (
+                    key, r, h0 + 1, f, pd, po, float(c[pd]), float(c[po]))
+            if bool(d["gate"][r, h0, f]) != bool(o["gate"][r, h0, f]):
+                assert abs(float(c[po])) < bound, "%s row %d width %d filter %d: gate differs at value %.3e" % (
+                    key, r, h0 + 1, f, float(c[po]))
+        n += int(mask_v.sum()) + int(mask.sum())
+        select[key] = dict(mask_v=mask_v, gate_v=d["gate_v"], mask=mask, pos=d["pos"], gate=d["gate"])
+    return select, n
+
+
+def _step_matches_oracle(hp, dims, feed, dedup):
+    net, params = _setup(hp, dims, dedup)
+    tf = O.to_torch_feed(feed, dtype=torch.float64)
+    bn, adam = O.init_bn_state(params), O.init_adam(params)
+    new_p, new_bn, _, ls, grads, norms, out = O.train_step(params, bn, adam, 1, tf, hp)
+    net.capture_grads = True
+    got = net.train_step(net.upload(feed, True))
+    torch.cuda.synchronize()
+    B, T, G, Hn = net.last_shape
+    assert Hn * G == B and (G > 1) == dedup
+    select, n_over = _overrides(_device_selection(got, hp, G), out, params, hp)
+    print("pools handed the device's selection: %d" % n_over)
+    assert n_over <= 4, "%d pools / gates differ between the device and the oracle" % n_over
+    if n_over:
+        new_p, new_bn, _, ls, grads, norms, out = O.train_step(params, bn, adam, 1, tf, hp, select)
+    _close(got["logit"], out["logit"], 1e-4, 1e-4, "logit")
+    _close(got["model_output"], out["model_output"], 1e-4, 1e-5, "model_output")
+    gl = net.read_losses()
+    for k in ("loss", "data_loss", "regular_loss"):
+        _close([gl[k]], [float(ls[k])], 1e-5, 1e-7, k)
+    cap, raw = net.captured, out["raw_grads"]
+    # absolute floor: exactly-zero gradients (biases feeding a batch-norm, the softmax-invariant output bias) come
+    # back as fp32 accumulation noise ~1e-6 of the largest gradient
+    floor = 4e-6 * max(float(raw[n].abs().max()) for n in net.dense_names)
+    assert set(net.dense_names) | set(SIB_TABLES.values()) == set(raw)
+    for i, name in enumerate(net.dense_names):
+        scale = float(raw[name].abs().max()) + 1e-12
+        _close(cap["dense"][name], raw[name], 2e-3, 2e-4 * scale + floor, "grad " + name)
+        _close([float(cap["dense_sumsq"][i]) ** 0.5], [norms[name]], 1e-3, 20 * floor, "norm " + name)
+    ss = cap["table_sumsq"].cpu().numpy()
+    tab_norm = dict(item=(ss[0] + ss[2] + ss[4]) ** 0.5, cate=(ss[1] + ss[3] + ss[5]) ** 0.5)
+    for key, name in SIB_TABLES.items():
+        scale = float(raw[name].abs().max()) + 1e-12
+        _close(cap["tables"][key], raw[name], 2e-3, 2e-4 * scale + floor, "grad " + name)
+        if not dedup:
+            _close([tab_norm[key]], [norms[name]], 1e-3, 1e-7, "clip norm " + name)
+    # the padded steps' gradient reaches table row 0 (no mask enters Caser's graph)
+    assert float(raw[SIB_TABLES["item"]][0].abs().max()) > 0 and float(cap["tables"]["item"][0].abs().max()) > 0
+    sd = net.state_dict()
+    lr = hp.learning_rate
+    for name in list(net.dense_names) + list(SIB_TABLES.values()):
+        g_ = grads[name].double().reshape(-1)
+        sel = g_.abs() > 100 * floor
+        upd_got = (sd[name].double().reshape(-1) - params[name].reshape(-1))[sel]
+        upd_exp = (new_p[name].reshape(-1) - params[name].reshape(-1))[sel]
+        if upd_exp.numel():
+            _close(upd_got, upd_exp, 5e-3, 0.02 * lr, "adam update " + name)
+    for k, v in new_bn.items():
+        _close(sd[k], v, 1e-4, 1e-6, k)
+    # the user table exists (checkpoint compatibility) but is never trained
+    assert torch.equal(sd["sequential/embedding/user_embedding"].double(), params["sequential/embedding/user_embedding"])
+
+
+@pytest.mark.parametrize("dedup", [True, False])
+@pytest.mark.parametrize("L", [1, 3, 10])
+def test_train_step_matches_oracle(golden_dir, golden_hparams, L, dedup):
+    hp = O.hparams(golden_hparams, L=L)
+    _step_matches_oracle(hp, _dims(hp), _feed(golden_dir, "iterator_train_sa.npz", b=1), dedup)
+
+
+def test_pooled_values_at_config_width(golden_dir, golden_hparams):
+    """caser.yaml's widths (n_v = n_h = 128, L = 3): model_output is 1064 wide -- the wide first logit layer and the
+    full filter count, forward only."""
+    hp = O.hparams(golden_hparams, n_v=128, n_h=128)
+    net, params = _setup(hp, _dims(hp), True)
+    assert net.out_dim == 1064
+    feed = _feed(golden_dir, "iterator_eval_sa.npz", b=0)
+    exp = O.predict(params, O.init_bn_state(params), O.to_torch_feed(feed, dtype=torch.float64), hp)
+    got = net.forward(net.upload(feed, False), False)
+    torch.cuda.synchronize()
+    _close(got["model_output"], exp["model_output"], 1e-4, 1e-5, "model_output")
+    _close(torch.sigmoid(got["logit"]), exp["pred"], 2e-3, 2e-4, "pred")
+
+
+def _edge_feed(T, G, Vi, Vc):
+    """Three histories -- one real step, a full one, one that ends mid-way -- each repeated for its 1 + 4 candidate rows;
+    left-aligned, padded with id 0."""
+    rng = np.random.RandomState(11)
+    lens = [1, T, 33]
+    Hn, B = len(lens), len(lens) * G
+    ih, ch, mask = (np.zeros((Hn, T), np.int32) for _ in range(3))
+    for r, n in enumerate(lens):
+        ih[r, :n], ch[r, :n], mask[r, :n] = rng.randint(1, Vi, n), rng.randint(1, Vc, n), 1
+    t = np.cumsum(rng.rand(Hn, T).astype(np.float32), 1) * mask
+    rep = lambda a: np.repeat(a, G, axis=0)
+    labels = np.zeros((B, 1), np.float32)
+    labels[::G] = 1
+    return dict(users=rep(np.arange(1, Hn + 1, dtype=np.int32)), items=rng.randint(1, Vi, B).astype(np.int32),
+                cates=rng.randint(1, Vc, B).astype(np.int32), item_history=rep(ih), item_cate_history=rep(ch),
+                mask=rep(mask), time_from_first_action=rep(t), time_to_now=rep(t[:, ::-1].copy()), labels=labels,
+                time=np.zeros(B, np.float32), time_diff=rep(t))
+
+
+@pytest.mark.parametrize("dedup", [True, False])
+def test_shapes_at_the_edges(golden_hparams, dedup):
+    """T = 65 (no multiple of a tile, one position past a 64-position chunk), Di = 12, Dc = 4, n_h = 4, L = 5: a partial
+    last tile in every dimension and windows that straddle the valid / padded boundary."""
+    hp = O.hparams(golden_hparams, max_seq_length=65, item_embedding_dim=12, cate_embedding_dim=4, n_v=4, n_h=4, L=5)
+    dims = dict(Vu=8, Vi=30, Vc=7)
+    _step_matches_oracle(hp, dims, _edge_feed(65, hp.train_num_ngs + 1, dims["Vi"], dims["Vc"]), dedup)
+
+
+def test_two_runs_are_bit_identical(golden_dir, golden_hparams):
+    hp = O.hparams(golden_hparams)
+    feed = _feed(golden_dir, "iterator_train_sa.npz", b=1)
+    runs = []
+    for _ in range(2):
+        net, _ = _setup(hp, _dims(hp), True)
+        net.capture_grads = True
+        net.train_step(net.upload(feed, True))
+        torch.cuda.synchronize()
+        runs.append((net.state_dict(), net.captured))
+    (sd_a, cap_a), (sd_b, cap_b) = runs
+    assert set(sd_a) == set(sd_b) and any(k.startswith("__adam__/") for k in sd_a)
+    for k in sd_a:       # tables, dense parameters, BN statistics, Adam moments
+        assert torch.equal(sd_a[k], sd_b[k]), k
+    assert torch.equal(cap_a["dense_sumsq"], cap_b["dense_sumsq"])
+    # squared norms of the un-summed slices of the four lookup sites (history and target rows of both tables); slots 4, 5
+    # are the shared trunk's regulariser norms, which tests/test_det_grads_gpu.py leaves out for every model
+    assert torch.equal(cap_a["table_sumsq"][:4], cap_b["table_sumsq"][:4])
+    for k in cap_a["dense"]:
+        assert torch.equal(cap_a["dense"][k], cap_b["dense"][k]), k
+    for k in cap_a["tables"]:
+        assert torch.equal(cap_a["tables"][k], cap_b["tables"][k]), k
+
+
+def test_eval_scores_match_oracle(golden_dir, golden_hparams):
+    hp = O.hparams(golden_hparams)
+    net, params = _setup(hp, _dims(hp), True)
+    bn = O.init_bn_state(params)
+    feed_t = _feed(golden_dir, "iterator_train_sa.npz", b=0)
+    new_p, new_bn, _, _, _, _, _ = O.train_step(params, bn, O.init_adam(params), 1,
+                                               O.to_torch_feed(feed_t, dtype=torch.float64), hp)
+    net.train_step(net.upload(feed_t, True))
+    feed = _feed(golden_dir, "iterator_eval_sa.npz", b=0)
+    exp = O.predict(new_p, new_bn, O.to_torch_feed(feed, dtype=torch.float64), hp)
+    got = net.forward(net.upload(feed, False), False)
+    torch.cuda.synchronize()
+    _close(torch.sigmoid(got["logit"]), exp["pred"], 2e-3, 2e-4, "pred")
+
+
+def test_model_api_roundtrip(golden_dir, golden_hparams, tmp_path):
+    """CaserModel through the shared API: fit one epoch, run_eval, checkpoint into a fresh model, identical predictions."""
+    from clsr_amd.clsr import CaserModel
+    from clsr_amd.sequential_iterator import SequentialIterator
+
+    d = os.path.join(golden_dir, "data")
+    hp = O.hparams(golden_hparams, epochs=1, MODEL_DIR=str(tmp_path / "model") + "/")
+    model = CaserModel(hp, SequentialIterator, seed=7)
+    assert model.fit(os.path.join(d, "train_data"), os.path.join(d, "valid_data"), valid_num_ngs=4,
+                     eval_metric="auc") is model
+    res = model.run_eval(os.path.join(d, "test_data"), 9)
+    assert res and all(np.isfinite(float(v)) for v in res.values()), res
+    ckpt = str(tmp_path / "ckpt" / "caser")
+    os.makedirs(os.path.dirname(ckpt))
+    model.save_model(ckpt)
+    fresh = CaserModel(copy.deepcopy(hp), SequentialIterator, seed=123)
+    fresh.load_model(ckpt)
+    a, b = tmp_path / "pred_a.txt", tmp_path / "pred_b.txt"
+    model.predict(os.path.join(d, "test_data"), str(a))
+    fresh.predict(os.path.join(d, "test_data"), str(b))
+    assert a.read_text() == b.read_text() and len(a.read_text().split()) == sum(1 for _ in open(os.path.join(d, "test_data")))
