@@ -12,6 +12,10 @@ oracle/clsr_oracle.py (``fcn_net``, ``_unique``, ``_clip_factor``, ``adam_apply`
 No mask: padded steps (table row 0) take part.  The pooling is ``torch.amax``, which like TensorFlow splits the gradient
 evenly among tied positions.  ``select`` overrides single pools / gates with a given selection (the device's, at a near-tie
 between fp32 and float64): the pooled value is gathered at the given position and the ReLU gate is taken as given.
+
+At the end: the kernel-level reference of tests/test_caser_kernels_gpu.py -- one table's variables as a block
+(``pack_block`` / ``unpack_block``: the flat layout of csrc/caser.hip), its forward with the tie masks, the backward written
+out (``explicit_backward``, no autograd) and the comparator of the running-sum bound (``bar_excess``).
 """
 import math
 from collections import OrderedDict
@@ -232,3 +236,101 @@ def train_step(params, bn_state, adam, step, feed, hp, select=None):
 @torch.no_grad()
 def predict(params, bn_state, feed, hp):
     return forward(params, bn_state, feed, hp, False)
+
+
+# ------------------------------------------------------------------------------------------ kernel-level reference
+# One table's variables as a "block": dict(Wv [Dx, T, n_v], bv [n_v], Wh = [[h, Dx, n_h] for h = 1..L], bh = [[n_h]] * L);
+# flat, it is the layout csrc/caser.hip states:  Wv | bv | Wh_1 | bh_1 | ... | Wh_L | bh_L,  each tensor contiguous.
+EPS32 = 2.0 ** -23
+
+
+def pack_block(blk):
+    parts = [blk["Wv"].reshape(-1), blk["bv"].reshape(-1)]
+    for W, b in zip(blk["Wh"], blk["bh"]):
+        parts += [W.reshape(-1), b.reshape(-1)]
+    return torch.cat(parts)
+
+
+def unpack_block(flat, T, Dx, L, n_v, n_h):
+    flat = flat.reshape(-1)
+    o = [0]
+
+    def take(*shape):
+        n = int(math.prod(shape))
+        t = flat[o[0]:o[0] + n].reshape(shape)
+        o[0] += n
+        return t
+
+    blk = dict(Wv=take(Dx, T, n_v), bv=take(n_v), Wh=[], bh=[])
+    for h in range(1, L + 1):
+        blk["Wh"].append(take(h, Dx, n_h))
+        blk["bh"].append(take(n_h))
+    assert o[0] == flat.numel(), (o[0], flat.numel())
+    return blk
+
+
+def map_block(blk, fn):
+    return dict(Wv=fn(blk["Wv"]), bv=fn(blk["bv"]), Wh=[fn(w) for w in blk["Wh"]], bh=[fn(b) for b in blk["bh"]])
+
+
+def block_forward(X, blk):
+    """-> (pooled [B, n_v + L n_h], masks): the pre-activations of one table in X's dtype and what the backward needs of
+    them: gate_v [B, n_v] (pre_v > 0), per width M [B, T - h + 1, n_h] (c_h == max_t c_h), n [B, n_h] (tied positions),
+    gate [B, n_h] (max > 0), first [B, n_h] (first maximum)."""
+    pre_v = vertical_pre(X, blk["Wv"], blk["bv"])
+    outs = [torch.relu(pre_v)]
+    masks = dict(gate_v=pre_v > 0, M=[], n=[], gate=[], first=[])
+    for W, b in zip(blk["Wh"], blk["bh"]):
+        c = horizontal_pre(X, W, b)
+        top = c.amax(1)
+        M = c == top.unsqueeze(1)
+        outs.append(torch.relu(top))
+        masks["M"].append(M)
+        masks["n"].append(M.sum(1))
+        masks["gate"].append(top > 0)
+        masks["first"].append(first_max(c))
+    return torch.cat(outs, 1), masks
+
+
+def explicit_backward(X, blk, dpool, masks):
+    """The backward of one table written out, NOT autograd: with g = dpool where the gate is open (0 elsewhere) and
+    A_h[b, s, f] = g_h[b, f] / n_h[b, f] where M_h[b, s, f] (0 elsewhere),
+        d X[b, t, d]     = sum_f g_v[b, f] Wv[d, t, f] + sum_h sum_j sum_f A_h[b, t - j, f] Wh_h[j, d, f]
+        d Wv[d, t, f]    = sum_b g_v[b, f] X[b, t, d]              d bv[f]   = sum_b g_v[b, f]
+        d Wh_h[j, d, f]  = sum_b sum_s A_h[b, s, f] X[b, s + j, d]  d bh_h[f] = sum_b g_h[b, f]
+    Every output is a sum of products that is linear in (g, W) and in (g, X) and the masks are GIVEN, so the same call on
+    |X|, |W|, |dpool| returns S, the sum of the absolute addends of every output element.  -> (d X, gradient block)"""
+    n_v = blk["Wv"].shape[2]
+    g_v = dpool[:, :n_v] * masks["gate_v"].to(dpool.dtype)
+    dX = torch.einsum("bf,dtf->btd", g_v, blk["Wv"]).contiguous()
+    dblk = dict(Wv=torch.einsum("bf,btd->dtf", g_v, X), bv=g_v.sum(0), Wh=[], bh=[])
+    off = n_v
+    for h0, W in enumerate(blk["Wh"]):
+        h, n_h = h0 + 1, W.shape[2]
+        P = X.shape[1] - h + 1
+        g = dpool[:, off:off + n_h] * masks["gate"][h0].to(dpool.dtype)
+        off += n_h
+        A = (g / masks["n"][h0].to(dpool.dtype)).unsqueeze(1) * masks["M"][h0].to(dpool.dtype)
+        dblk["Wh"].append(torch.stack([torch.einsum("bsf,bsd->df", A, X[:, j:j + P]) for j in range(h)]))
+        dblk["bh"].append(g.sum(0))
+        for j in range(h):
+            dX[:, j:j + P] += A @ W[j].t()
+    return dX, dblk
+
+
+def bar_excess(got, ref, S, N):
+    """Worst of |got - ref| - N * 2^-23 * S over the elements (<= 0: within the running-sum bound of N addends whose
+    absolute values sum to S) and where it sits."""
+    ex = ((got.double() - ref.double()).abs() - N * EPS32 * S.double()).reshape(-1)
+    if ex.numel() == 0:
+        return 0.0, -1
+    i = int(ex.argmax())
+    return float(ex[i]), i
+
+
+def chain_lengths(Hn, T, L, n_v, n_h, parts):
+    """Addends of the longest chain behind an element: d hist (n_v vertical filters, up to h tied windows of every filter of
+    every width, the prior content, the rounding of g / n), per variable of the gradient block (the histories' windows,
+    the slices' partial sums, the rounding of g / n) -- the N of ``bar_excess``."""
+    return dict(dhist=n_v + n_h * L * (L + 1) // 2 + 2, Wv=Hn + parts + 2, bv=Hn + parts,
+                Wh=[Hn * (T - h + 1) + parts + 2 for h in range(1, L + 1)], bh=[Hn + parts] * L)

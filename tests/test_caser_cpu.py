@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 import torch
 
+import caser_cases as K
 import caser_oracle as O
 from clsr_amd.params import sibling_kind, sibling_specs
 
@@ -124,6 +125,157 @@ def test_fixture_sits_clear_of_near_ties(golden_dir, golden_hparams, L):
         pools += a["pos"].numel()
         assert 0 < int(a["gate"].sum()) < a["gate"].numel() or L == 10    # both states of the gate are exercised
     assert pools == 2 * feed["items"].shape[0] * L * 16
+
+
+def test_config_step_feed_sits_clear_of_near_ties(golden_hparams):
+    """The generated feed of the training step at caser.yaml's widths and length (tests/test_caser_gpu.py): with the committed
+    seed the float32 and the float64 oracle select alike, as for the golden batch above."""
+    cs = K.CONFIG_STEP
+    hp = O.hparams(golden_hparams, max_seq_length=cs["T"], n_v=128, n_h=128)
+    feed = K.edge_feed(cs["T"], hp.train_num_ngs + 1, cs["dims"]["Vi"], cs["dims"]["Vc"], cs["lens"], cs["seed"])
+    assert sorted({int(n) for n in feed["mask"].sum(1)}) == sorted(set(cs["lens"])) and 1 in cs["lens"] and 50 in cs["lens"]
+    p32 = O.init_params(cs["dims"], hp, dtype=torch.float32, **O.FIXTURE)
+    p64 = type(p32)((k, v.double()) for k, v in p32.items())
+    sel, hist = {}, {}
+    for tag, params, dt in (("f32", p32, torch.float32), ("f64", p64, torch.float64)):
+        with torch.no_grad():
+            out = O.forward(params, O.init_bn_state(params), O.to_torch_feed(feed, dtype=dt), hp, True, {})
+        sel[tag], hist[tag] = O.selection(out, hp), out["hist"]
+    for key in ("item", "cate"):
+        a, b = sel["f32"][key], sel["f64"][key]
+        assert torch.equal(a["gate_v"], b["gate_v"]), key + ": vertical ReLU gates differ between float32 and float64"
+        assert torch.equal(a["gate"], b["gate"]), key + ": pool ReLU gates differ between float32 and float64"
+        X = hist["f32"][key]
+        for r, h0, f in (a["pos"] != b["pos"]).nonzero().tolist():
+            h, pa, pb = h0 + 1, int(a["pos"][r, h0, f]), int(b["pos"][r, h0, f])
+            assert torch.equal(X[r, pa:pa + h], X[r, pb:pb + h]), \
+                "%s row %d width %d filter %d: float32 picks window %d, float64 window %d" % (key, r, h, f, pa, pb)
+        assert 0 < int(a["gate"].sum()) < a["gate"].numel()
+
+
+# ------------------------------------------------------------- the kernel-level reference (tests/test_caser_kernels_gpu.py)
+def _as_params(blk, hp, key):
+    p = {O.vname(hp, key) + "kernel": blk["Wv"], O.vname(hp, key) + "bias": blk["bv"]}
+    for h0, (W, b) in enumerate(zip(blk["Wh"], blk["bh"])):
+        p[O.hname(key, h0 + 1) + "kernel"], p[O.hname(key, h0 + 1) + "bias"] = W, b
+    return p
+
+
+def test_block_layout_roundtrip():
+    """pack_block / unpack_block: the flat layout csrc/caser.hip states -- Wv [Dx][T][n_v] | bv | Wh_1 | bh_1 | ... ."""
+    T, Dx, L, n_v, n_h = 5, 4, 3, 8, 4
+    n = Dx * T * n_v + n_v + sum(h * Dx * n_h + n_h for h in range(1, L + 1))
+    flat = torch.arange(n, dtype=torch.float64)
+    blk = O.unpack_block(flat, T, Dx, L, n_v, n_h)
+    assert blk["Wv"].shape == (Dx, T, n_v) and float(blk["Wv"][1, 2, 3]) == (1 * T + 2) * n_v + 3
+    assert float(blk["bv"][0]) == Dx * T * n_v
+    o2 = Dx * T * n_v + n_v + (Dx * n_h + n_h)                  # Wh_2 follows Wh_1 | bh_1
+    assert blk["Wh"][1].shape == (2, Dx, n_h) and float(blk["Wh"][1][1, 2, 3]) == o2 + (1 * Dx + 2) * n_h + 3
+    assert float(blk["bh"][2][n_h - 1]) == n - 1
+    assert torch.equal(O.pack_block(blk), flat)
+
+
+def test_explicit_backward_equals_autograd():
+    """The written-out backward against autograd of ``O.cnn`` under (pooled * dpool).sum(), at a shape with ties (torch.amax
+    splits evenly among tied positions) and closed gates."""
+    import types
+
+    c = K.Case(6, 40, 8, 4, 4, 8, 4, 3, "")
+    inp = K.make_inputs(c)
+    hp = types.SimpleNamespace(L=c.L, item_embedding_dim=c.Di, cate_embedding_dim=c.Dc)
+    PW = c.n_v + c.L * c.n_h
+    gen = torch.Generator().manual_seed(4)
+    tied = 0
+    for i, key in enumerate(("item", "cate")):
+        X = inp["X"][key].clone().requires_grad_(True)
+        blk = O.map_block(inp["blk"][key], lambda t: t.clone().requires_grad_(True))
+        dpool = torch.randn(c.Hn, PW, generator=gen, dtype=torch.float64)
+        pooled = O.cnn(X, key, _as_params(blk, hp, key), hp)
+        (pooled * dpool).sum().backward()
+        with torch.no_grad():
+            mine, m = O.block_forward(X, blk)
+            assert torch.equal(mine, pooled)
+            dX, dblk = O.explicit_backward(X, blk, dpool, m)
+        tied += sum(int(((n > 1) & g).sum()) for n, g in zip(m["n"], m["gate"]))
+        assert any(int((~g).sum()) for g in m["gate"]) and int((~m["gate_v"]).sum())
+        for name, got, exp in [("dX", dX, X.grad), ("dWv", dblk["Wv"], blk["Wv"].grad), ("dbv", dblk["bv"], blk["bv"].grad)] + \
+                [("dWh%d" % (h + 1), dblk["Wh"][h], blk["Wh"][h].grad) for h in range(c.L)] + \
+                [("dbh%d" % (h + 1), dblk["bh"][h], blk["bh"][h].grad) for h in range(c.L)]:
+            assert float((got - exp).abs().max()) <= 1e-12, (key, name, float((got - exp).abs().max()))
+    assert tied > 0
+
+
+@pytest.mark.parametrize("c", K.CASES + [K.GATES], ids=K.case_id)
+def test_kernel_cases_are_exact_in_float32_and_offer_every_pool_kind(c):
+    """Guards the grid argument: the float32 and the float64 reference forward are bit-equal (values, first maxima, tie
+    masks), so no near-tie allowance exists at kernel level; and the inputs hold an open pool with a single winner, an
+    open pool whose tied positions span two mask words (T > 32) and a closed gate.  (The widest case at n_v = 8: the
+    vertical path's exactness does not depend on the filter count.)"""
+    n_v = 8 if c == K.WS_CAPPED else None
+    inp = K.make_gate_inputs() if c == K.GATES else K.make_inputs(c, n_v=n_v)
+    masks = {}
+    for key in ("item", "cate"):
+        X, blk = inp["X"][key], inp["blk"][key]
+        assert float(X.abs().max()) <= 1 and torch.equal(X * 4, (X * 4).round())
+        assert float(blk["Wv"].abs().max()) <= 0.5 and torch.equal(blk["Wv"] * 8, (blk["Wv"] * 8).round())
+        p64, m64 = O.block_forward(X, blk)
+        p32, m32 = O.block_forward(X.float(), O.map_block(blk, lambda t: t.float()))
+        assert p32.dtype == torch.float32 and torch.equal(p32.double(), p64)
+        assert torch.equal(m32["gate_v"], m64["gate_v"])
+        for a, b in zip(m32["M"] + m32["first"] + m32["gate"], m64["M"] + m64["first"] + m64["gate"]):
+            assert torch.equal(a, b)
+        masks[key] = m64
+    ok, found = K.conditions_hold(c, masks)
+    assert ok, found
+
+
+def _bar_fails(c, ref, dX, dblk, key):
+    """Whether the comparator of the GPU test rejects (dX, dblk) as the result of table ``key``."""
+    N = O.chain_lengths(c.Hn, c.T, c.L, c.n_v, c.n_h, 16)
+    bad = [O.bar_excess(dX, ref["dX"][key], ref["SX"][key], N["dhist"])[0] > 0]
+    r, S = ref["dblk"][key], ref["Sblk"][key]
+    bad += [O.bar_excess(dblk["Wv"], r["Wv"], S["Wv"], N["Wv"])[0] > 0, O.bar_excess(dblk["bv"], r["bv"], S["bv"], N["bv"])[0] > 0]
+    for h0 in range(c.L):
+        bad += [O.bar_excess(dblk["Wh"][h0], r["Wh"][h0], S["Wh"][h0], N["Wh"][h0])[0] > 0]
+    return bad
+
+
+def test_comparator_is_sharp_at_the_config_shape():
+    """One tied position's share removed, and one window shifted by one position: each misses the bar N * 2^-23 * S of the
+    GPU test, in d hist and in the kernel gradient of its width; the unperturbed result, rounded to float32, passes."""
+    c = K.CONFIG
+    inp, ref = K.case_data(c)
+    key = "item"
+    X, blk, m = inp["X"][key], inp["blk"][key], ref["masks"][key]
+    PW = c.n_v + c.L * c.n_h
+    dp = inp["dpool"][:, :PW].double()
+    dX, dblk = O.explicit_backward(X, blk, dp, m)
+    assert not any(_bar_fails(c, ref, dX.float(), O.map_block(dblk, lambda t: t.float()), key))
+    h0 = 1                                                               # width 2
+    col = lambda f: c.n_v + h0 * c.n_h + f
+
+    def perturbed(pick, change):
+        M, n, gate = m["M"][h0], m["n"][h0], m["gate"][h0]
+        cands = [(b, f) for b, f in (gate & pick(n)).nonzero().tolist() if float(dp[b, col(f)]) != 0.0]
+        b, f = min(cands, key=lambda bf: int(n[bf[0], bf[1]]))           # (the smallest tie set: the largest share)
+        s = int(O.first_max(M.double())[b, f])
+        M2 = M.clone()
+        change(M2, b, s, f)
+        m2 = dict(m, M=[M2 if i == h0 else x for i, x in enumerate(m["M"])])     # (n stays: the share is LOST, not re-split)
+        return O.explicit_backward(X, blk, dp, m2)
+
+    def drop(M2, b, s, f):
+        M2[b, s, f] = False
+
+    def shift(M2, b, s, f):
+        s2 = s + 1 if s + 1 < M2.shape[1] else s - 1
+        M2[b, s, f], M2[b, s2, f] = False, True
+
+    for pick, change in ((lambda n: n > 1, drop), (lambda n: n == 1, shift)):
+        dX2, dblk2 = perturbed(pick, change)
+        bad = _bar_fails(c, ref, dX2, dblk2, key)
+        assert bad[0], "d hist: the perturbed reference passes"
+        assert bad[3 + h0], "d Wh_2: the perturbed reference passes"
 
 
 def test_refusals_are_reported_by_name(golden_hparams):

@@ -14,6 +14,7 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
+import caser_cases as K  # noqa: E402
 import caser_oracle as O  # noqa: E402
 from clsr_amd.params import SIB_TABLES  # noqa: E402
 from clsr_amd.seqnet import SeqNet  # noqa: E402
@@ -170,20 +171,7 @@ def test_pooled_values_at_config_width(golden_dir, golden_hparams):
 def _edge_feed(T, G, Vi, Vc):
     """Three histories -- one real step, a full one, one that ends mid-way -- each repeated for its 1 + 4 candidate rows;
     left-aligned, padded with id 0."""
-    rng = np.random.RandomState(11)
-    lens = [1, T, 33]
-    Hn, B = len(lens), len(lens) * G
-    ih, ch, mask = (np.zeros((Hn, T), np.int32) for _ in range(3))
-    for r, n in enumerate(lens):
-        ih[r, :n], ch[r, :n], mask[r, :n] = rng.randint(1, Vi, n), rng.randint(1, Vc, n), 1
-    t = np.cumsum(rng.rand(Hn, T).astype(np.float32), 1) * mask
-    rep = lambda a: np.repeat(a, G, axis=0)
-    labels = np.zeros((B, 1), np.float32)
-    labels[::G] = 1
-    return dict(users=rep(np.arange(1, Hn + 1, dtype=np.int32)), items=rng.randint(1, Vi, B).astype(np.int32),
-                cates=rng.randint(1, Vc, B).astype(np.int32), item_history=rep(ih), item_cate_history=rep(ch),
-                mask=rep(mask), time_from_first_action=rep(t), time_to_now=rep(t[:, ::-1].copy()), labels=labels,
-                time=np.zeros(B, np.float32), time_diff=rep(t))
+    return K.edge_feed(T, G, Vi, Vc)
 
 
 @pytest.mark.parametrize("dedup", [True, False])
@@ -193,6 +181,17 @@ def test_shapes_at_the_edges(golden_hparams, dedup):
     hp = O.hparams(golden_hparams, max_seq_length=65, item_embedding_dim=12, cate_embedding_dim=4, n_v=4, n_h=4, L=5)
     dims = dict(Vu=8, Vi=30, Vc=7)
     _step_matches_oracle(hp, dims, _edge_feed(65, hp.train_num_ngs + 1, dims["Vi"], dims["Vc"]), dedup)
+
+
+@pytest.mark.parametrize("dedup", [True, False])
+def test_train_step_at_config_shape(golden_hparams, dedup):
+    """caser.yaml's widths AND length (T = 50, n_v = n_h = 128, L = 3: the shape scripts/caser_step_time.py times), forward
+    and backward: five histories of 1, 50 and mid-way steps.  tests/test_caser_cpu.py pins that the feed's seed keeps the
+    float32 and the float64 oracle on the same selection."""
+    cs = K.CONFIG_STEP
+    hp = O.hparams(golden_hparams, max_seq_length=cs["T"], n_v=128, n_h=128)
+    feed = K.edge_feed(cs["T"], hp.train_num_ngs + 1, cs["dims"]["Vi"], cs["dims"]["Vc"], cs["lens"], cs["seed"])
+    _step_matches_oracle(hp, cs["dims"], feed, dedup)
 
 
 def test_two_runs_are_bit_identical(golden_dir, golden_hparams):

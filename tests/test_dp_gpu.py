@@ -277,18 +277,38 @@ def test_sibling_models_two_ranks_match_single_process(golden_dir, golden_hparam
     """The sibling models go through the same DataParallel exchange (two trained tables instead of four)."""
     import pickle
 
-    import torch.multiprocessing as mp
-
-    from clsr_amd.seqnet import SeqNet
     from oracle import sibling_oracle as O
 
     hp = copy.deepcopy(golden_hparams)
     hp.model_type, hp.user_embedding_dim, hp.attention_size = model_type, 16, 40
     dims = dict(Vu=len(pickle.load(open(hp.user_vocab, "rb"))), Vi=len(pickle.load(open(hp.item_vocab, "rb"))),
                 Vc=len(pickle.load(open(hp.cate_vocab, "rb"))))
+    _sibling_two_ranks(golden_dir, hp, dims, kind, O.init_params(dims, hp, kind, seed=5, scale_dense=8.0))
+
+
+def test_caser_two_ranks_match_single_process(golden_dir, golden_hparams):
+    """Caser adds only dense parameters (the convolution kernels and biases of both tables) to the same exchange: each rank
+    runs the convolutions over its own histories and the weight gradients are summed by the dense all-reduce."""
+    import pickle
+    import sys
+
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    import caser_oracle as O
+
+    hp = O.hparams(golden_hparams)
+    dims = dict(Vu=len(pickle.load(open(hp.user_vocab, "rb"))), Vi=len(pickle.load(open(hp.item_vocab, "rb"))),
+                Vc=len(pickle.load(open(hp.cate_vocab, "rb"))))
+    _sibling_two_ranks(golden_dir, hp, dims, "caser", O.init_params(dims, hp, **O.FIXTURE))
+
+
+def _sibling_two_ranks(golden_dir, hp, dims, kind, params):
+    import torch.multiprocessing as mp
+
+    from clsr_amd.seqnet import SeqNet
+    from oracle import sibling_oracle as O
+
     g = np.load(os.path.join(golden_dir, "iterator_train_sa.npz"))
     feed = {k[3:]: g[k] for k in g.files if k.startswith("b0_")}
-    params = O.init_params(dims, hp, kind, seed=5, scale_dense=8.0)
     sd = dict(params)
     sd.update(O.init_bn_state(params))
     single = SeqNet(hp, dims, kind=kind, device="cuda:0", seed=0)
