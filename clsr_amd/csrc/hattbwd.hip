@@ -154,15 +154,21 @@ __global__ void __launch_bounds__(256, 2) att_l0_bwd_kernel(AttL0BwdArgs s) {
           f32x4 acc[NF];
 #pragma unroll
           for (int f = 0; f < NF; ++f) acc[f] = z4;
+          // (KT is that of the width class: a k-tile at or past A0 lies past the row stride Kp, for the last weight row past
+          //  the image -- skipped, since a zero A operand does not make 0 * garbage zero)
 #pragma unroll
           for (int kt = 0; kt < KT; ++kt)
+            if (32 * kt < s.A0) {
 #pragma unroll
-            for (int f = 0; f < NF; ++f) HMFMA(acc[f], x[kt], ld8h(Wl + wrow[f] + 32 * kt));
+              for (int f = 0; f < NF; ++f) HMFMA(acc[f], x[kt], ld8h(Wl + wrow[f] + 32 * kt));
+            }
           if (WU) {   // (sum_g dz0_g) . Wu^T = sum_g (dz0_g . Wu^T): accumulated by the matrix pipe across the g loop
 #pragma unroll
             for (int kt = 0; kt < KT; ++kt)
+              if (32 * kt < s.A0) {
 #pragma unroll
-              for (int f = 0; f < NF; ++f) HMFMA(wacc[f], x[kt], ld8h(Wul + wrow[f] + 32 * kt));
+                for (int f = 0; f < NF; ++f) HMFMA(wacc[f], x[kt], ld8h(Wul + wrow[f] + 32 * kt));
+              }
           }
           // dz0^T tiles (product with the identity)
           f32x4 dzt[NZ];
@@ -263,8 +269,10 @@ __global__ void __launch_bounds__(256, 2) att_l0_bwd_f32_kernel(AttL0BwdArgsF s)
   const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
   const int j = lane & 15, g4 = lane >> 4;
   const int Kp = s.Kp;
+  // (NZ is that of the width class: with A0 <= 32 the k-chunks past A0 of the last weight row lie past the image.  Their A
+  //  operand is zero, so they only have to read something finite: ZP zeroed floats behind the image, nothing in the loop)
   float* Wl = reinterpret_cast<float*>(lds_raw);
-  float* wl = Wl + (size_t)QP * Kp + (size_t)wave * AB_GMAX * (2 * QP + ZP);
+  float* wl = Wl + (size_t)QP * Kp + ZP + (size_t)wave * AB_GMAX * (2 * QP + ZP);
   float* qs = wl;
   float* dqs = wl + AB_GMAX * QP;
   float* dvs = wl + 2 * AB_GMAX * QP;
@@ -276,6 +284,7 @@ __global__ void __launch_bounds__(256, 2) att_l0_bwd_f32_kernel(AttL0BwdArgsF s)
       const int row = e / Kq, c = e - row * Kq;
       reinterpret_cast<f32x4*>(Wl)[e] = row < nrows ? ld4(s.Wt + (long)row * Kp + 4 * c) : z;
     }
+    if (tid < ZP / 4) reinterpret_cast<f32x4*>(Wl + (size_t)QP * Kp)[tid] = z;
   }
   __syncthreads();
   const float* ldsB = Wl + (long)j * Kp + 4 * g4;   // + 16 f Kp + 16 kk
@@ -434,7 +443,7 @@ __global__ void __launch_bounds__(256, 2) att_l0_bwd_f32_kernel(AttL0BwdArgsF s)
 
 template <int NF, int NZ>
 static int att_l0_bwd_f32_launch(const AttL0BwdArgsF& a, hipStream_t stream) {
-  size_t shmem = (size_t)16 * NF * a.Kp * 4 + (size_t)4 * AB_GMAX * (2 * 16 * NF + 16 * NZ) * 4;
+  size_t shmem = (size_t)16 * NF * a.Kp * 4 + (size_t)16 * NZ * 4 + (size_t)4 * AB_GMAX * (2 * 16 * NF + 16 * NZ) * 4;
   int gx = (int)((a.Hn + 3) / 4);
   if (gx > 512) gx = 512;
   auto kernel = att_l0_bwd_f32_kernel<NF, NZ>;

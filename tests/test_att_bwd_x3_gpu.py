@@ -40,7 +40,8 @@ LONG_L0 = [(3, 5, 65, 80, 80), (2, 8, 256, 80, 80), (4, 1, 250, 40, 80)]
 
 
 @pytest.mark.parametrize("Hn,G,T,Q,A0", [(37, 5, 50, 40, 80), (64, 1, 50, 40, 80), (9, 8, 7, 44, 40), (6, 3, 17, 24, 40),
-                                         (1, 5, 1, 80, 80), (130, 2, 33, 48, 80), (2100, 2, 5, 40, 80), (5, 5, 50, 8, 16)]
+                                         (1, 5, 1, 80, 80), (130, 2, 33, 48, 80), (2100, 2, 5, 40, 80), (5, 5, 50, 8, 16),
+                                         (37, 2, 7, 80, 8), (64, 1, 10, 80, 16)]      # widest query x narrowest first layer
                          + LONG_L0)
 @pytest.mark.parametrize("entry,tol,tols", [("clsr_att_l0_bwd_x3", 1e-4, 3e-5), ("clsr_att_l0_bwd_x6", 3e-6, 3e-6)])
 def test_layer0_backward_x3_with_weight_gradient(Hn, G, T, Q, A0, entry, tol, tols):

@@ -44,7 +44,9 @@ def chunks_to_matrix(ws, parts, K, N):
 
 
 @pytest.mark.parametrize("Hn,G,T,Q,A0", [(37, 5, 50, 80, 80), (64, 1, 50, 40, 80), (9, 8, 7, 44, 40), (6, 3, 17, 24, 40),
-                                         (1, 5, 1, 80, 80), (2100, 2, 33, 48, 80), (7, 5, 16, 80, 40), (3, 2, 8, 16, 16)])
+                                         (1, 5, 1, 80, 80), (2100, 2, 33, 48, 80), (7, 5, 16, 80, 40), (3, 2, 8, 16, 16),
+                                         (4, 2, 63, 80, 80), (3, 5, 64, 40, 80), (6, 1, 65, 80, 40), (5, 2, 129, 24, 40),
+                                         (3, 5, 256, 80, 80)])
 def test_layer0_forward_one_piece_bf16_out(Hn, G, T, Q, A0):
     g = torch.Generator().manual_seed(Hn * 3 + T)
     R, M = Hn * G, Hn * G * T
@@ -162,7 +164,10 @@ def test_layer1_backward_one_piece_bf16(M, C1, C0):
 
 
 @pytest.mark.parametrize("Hn,G,T,Q,A0", [(37, 5, 50, 40, 80), (64, 1, 50, 40, 80), (9, 8, 7, 44, 40), (6, 3, 17, 24, 40),
-                                         (1, 5, 1, 80, 80), (130, 2, 33, 48, 80), (2100, 2, 5, 40, 80), (5, 5, 50, 8, 16)])
+                                         (1, 5, 1, 80, 80), (130, 2, 33, 48, 80), (2100, 2, 5, 40, 80), (5, 5, 50, 8, 16),
+                                         (4, 2, 63, 40, 80), (3, 5, 64, 40, 80), (6, 1, 65, 80, 40), (5, 2, 129, 24, 40),
+                                         (3, 5, 256, 80, 80),
+                                         (37, 2, 7, 80, 8), (64, 1, 10, 80, 16)])      # widest query x narrowest first layer
 def test_layer0_backward_one_piece_bf16(Hn, G, T, Q, A0):
     g = torch.Generator().manual_seed(Hn * 7 + T)
     R, M = Hn * G, Hn * G * T

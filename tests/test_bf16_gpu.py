@@ -49,7 +49,13 @@ def _stats(st, parts, N):
     return s[0], s[1]
 
 
-@pytest.mark.parametrize("Hn,G,T,Q,N", [(37, 5, 10, 80, 80), (64, 1, 50, 40, 80), (9, 3, 7, 256, 136), (5, 5, 50, 80, 40)])
+# histories across the 64-step chunks of the attention tail (T = 63 .. 256): the speed mode's own instantiations
+LONG_HTG = [(4, 2, 63), (3, 5, 64), (6, 1, 65), (5, 2, 129), (3, 5, 256)]
+
+
+@pytest.mark.parametrize("Hn,G,T,Q,N", [(37, 5, 10, 80, 80), (64, 1, 50, 40, 80), (9, 3, 7, 256, 136), (5, 5, 50, 80, 40),
+                                        (4, 2, 63, 80, 80), (3, 5, 64, 40, 80), (6, 1, 65, 80, 40), (5, 2, 129, 40, 40),
+                                        (3, 5, 256, 80, 80)])
 def test_hgemm_mul_uv(Hn, G, T, Q, N):
     g = torch.Generator().manual_seed(1)
     R, M = Hn * G, Hn * G * T
@@ -76,7 +82,10 @@ def test_hgemm_mul_uv(Hn, G, T, Q, N):
 
 
 @pytest.mark.parametrize("Hn,G,T,Q,N", [(37, 5, 10, 80, 80), (9, 3, 50, 40, 80), (5, 8, 17, 96, 72), (130, 2, 33, 24, 40),
-                                        (41, 5, 50, 80, 80), (6, 8, 18, 80, 80), (7, 4, 16, 40, 40), (3, 2, 5, 16, 24)])
+                                        (41, 5, 50, 80, 80), (6, 8, 18, 80, 80), (7, 4, 16, 40, 40), (3, 2, 5, 16, 24),
+                                        # chunk edges; G = 1 is not this kernel's (asserted below): clsr_hgemm_mul_uv has it
+                                        (4, 2, 63, 80, 80), (3, 5, 64, 40, 80), (6, 2, 65, 80, 40), (5, 5, 129, 24, 40),
+                                        (3, 2, 256, 80, 80)])
 def test_hgemm_layer0_one_wave_per_group(Hn, G, T, Q, N):
     """clsr_hgemm_l0_group == clsr_hgemm_mul_uv (same packed weights, same rounding points): z0 bit for bit, the
     batch-norm column sums to fp32 summation noise."""
@@ -196,7 +205,10 @@ def test_hgemm_attention_layer1_backward(M, C1, C0):
 
 
 @pytest.mark.parametrize("Hn,G,T,Q,A0", [(37, 5, 50, 80, 80), (64, 1, 50, 40, 80), (9, 8, 7, 96, 96), (6, 3, 17, 24, 40),
-                                         (1, 5, 1, 80, 80), (130, 2, 33, 48, 88)])
+                                         (1, 5, 1, 80, 80), (130, 2, 33, 48, 88), (4, 2, 63, 80, 80), (3, 5, 64, 40, 80),
+                                         (6, 1, 65, 80, 40), (5, 2, 129, 24, 40), (3, 5, 256, 80, 80),
+                                         # the last 16-feature tile of a 96-wide query with ONE 32-wide k-tile of A0
+                                         (37, 2, 7, 96, 8), (64, 1, 10, 96, 16), (19, 5, 20, 96, 32), (9, 3, 5, 88, 48)])
 def test_fused_layer0_backward_reductions(Hn, G, T, Q, A0):
     """clsr_att_l0_bwd_h: da, dq, dU, dV from ONE pass over dz0 (bf16); daq = dz0 . Wp^T never stored.  Against float64 on
     the bf16-rounded operands, and against the three-kernel path it replaces (which rounds daq to bf16)."""
@@ -308,7 +320,7 @@ def test_bf16_mfma_weight_gradient_kernel(M, K, N):
     _close(db, dYh.double().sum(0), 1e-4, 2e-3, "db (bf16 dY)")
 
 
-@pytest.mark.parametrize("Hn,G,T", [(19, 5, 10), (33, 1, 50), (7, 5, 50)])
+@pytest.mark.parametrize("Hn,G,T", [(19, 5, 10), (33, 1, 50), (7, 5, 50)] + LONG_HTG)
 def test_bf16_input_variants_equal_the_fp32_kernels_on_upcast_inputs(Hn, G, T):
     """att_out_fwd / att_dy1_stats / att_z0_bwd_reduce / att_prod_bwd with bf16 tensors == the fp32 kernels fed with
     the same values converted to fp32 (same code, only the loads differ)."""

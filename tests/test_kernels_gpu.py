@@ -474,7 +474,8 @@ def _oracle():
 
 
 @pytest.mark.parametrize("Hn,G,T,Q,col0,ld", [(19, 5, 10, 80, 0, 80), (7, 1, 50, 40, 0, 40), (11, 5, 13, 40, 40, 80),
-                                               (5, 9, 6, 128, 128, 256), (3, 5, 65, 80, 0, 80), (2, 3, 256, 40, 40, 80)])
+                                               (5, 9, 6, 128, 128, 256), (3, 5, 65, 80, 0, 80), (2, 3, 256, 40, 40, 80),
+                                               (4, 2, 63, 80, 0, 80), (3, 5, 64, 80, 0, 80), (5, 1, 129, 40, 0, 40)])
 def test_att_prod_bwd_on_column_blocks(Hn, G, T, Q, col0, ld):
     """Backward of the product feature a[h,t] * q[r]: da[h,t] = sum_g daq[r,t] * q[r], dq[r] = sum_t daq[r,t] * a[h,t]
     (clsr.py:368-370) -- the plain entry point and the leading-dimension one on a column block [col0, col0+Q) of
@@ -1086,11 +1087,14 @@ def test_weights_softmax_bwd_row_scaling_and_products():
 
 
 # histories past one 64-step chunk of the attention tail, up to max_seq_length = 256 (also tests/test_att_bwd_x3_gpu.py, test_x3_gpu.py)
-LONG_L0 = [(3, 5, 65, 80, 80), (2, 8, 256, 80, 80), (4, 1, 250, 40, 80)]
+LONG_L0 = [(3, 5, 65, 80, 80), (2, 8, 256, 80, 80), (4, 1, 250, 40, 80), (4, 2, 63, 80, 80), (3, 5, 64, 40, 80), (5, 2, 129, 24, 40),
+           (6, 1, 65, 80, 40), (3, 1, 256, 40, 80)]      # G = 1 at the chunk edges: what the bf16 twins are compared with bit for bit
 
 
 @pytest.mark.parametrize("Hn,G,T,Q,A0", [(37, 5, 50, 80, 80), (64, 1, 50, 40, 80), (9, 8, 7, 44, 36), (6, 3, 17, 24, 40),
-                                         (1, 5, 1, 80, 80), (130, 2, 33, 48, 80)] + LONG_L0)
+                                         (1, 5, 1, 80, 80), (130, 2, 33, 48, 80),
+                                         (37, 2, 7, 80, 8), (64, 1, 10, 80, 16)]      # widest query x narrowest first layer
+                         + LONG_L0)
 def test_fused_layer0_backward_reductions_fp32(Hn, G, T, Q, A0):
     """clsr_att_l0_bwd: da, dq, dU, dV of the re-associated first attention layer from one pass over dz0 on the fp32
     matrix pipe (daq = dz0 . Wp^T never stored) == float64, and == the three kernels it replaces."""
