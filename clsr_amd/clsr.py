@@ -670,6 +670,11 @@ class CaserModel(_SiblingModel):
     kind = "caser"
 
 
+class NCFModel(_SiblingModel):
+    """Reference ``NCFModel`` (models/sequential/ncf.py): hparams ``ncf_layer_sizes``, ``user_embedding_dim``."""
+    kind = "ncf"
+
+
 class SLI_RECModel(_SiblingModel):
     """Reference ``SLI_RECModel`` (models/sequential/sli_rec.py)."""
     kind = "sli_rec"

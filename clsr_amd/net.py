@@ -2808,7 +2808,7 @@ class CLSRNet(object):
         V, C = tb[key].shape
         pt = tb[partner] if partner else None
         return ops.TableDesc.row(table=tb[key], partner=pt, grad=self.tab_grad[key], m=self.tab_m.get(key), v=self.tab_v.get(key),
-                                 flags=self.tab_flags[key], sumsq_reg=ss[slot:], disc_loss=dloss, sumsq_adam=ss[base:], V=V, C=C,
+                                 flags=self.tab_flags[key], sumsq_reg=None if slot is None else ss[slot:], disc_loss=dloss, sumsq_adam=ss[base:], V=V, C=C,
                                  nsum=nsum, sumsq_stride=2, disc_scale=dscale, disc_loss_scale=dloss_scale)
 
     def _tab_halves(self, key):
@@ -2897,14 +2897,17 @@ class CLSRNet(object):
         for key, partner, slot, dscale, dloss_scale, dloss, base, nsum in spec:
             V, C = tb[key].shape
             pt = tb[partner] if partner else None
+            if slot is None and key in lists:      # (slot None: a table the regulariser does not reach -- NCF's own four)
+                continue
             if key in lists:
                 ids, count, cap = lists[key]
                 call("clsr_table_reg_rows" + self._th, tb[key], pt, ids, count, cap, C, l2e, l1e, dscale, dloss_scale,
                      self.ucount if partner else None, tg[key], ss[slot:], self.losses[1:], dloss)
             else:   # small tables: one launch sweeps all of them (blockIdx.y = table)
                 sweep.append(self._sweep_row(key, partner, slot, dscale, dloss_scale, dloss, base, nsum))
-        if sweep:
-            ops.multi("clsr_tables_reg_multi" + self._th, ops.TableDesc, sweep, l2e, l1e, self.ucount, self.losses[1:])
+        reg = [r for r in sweep if r.sumsq_reg]
+        if reg:
+            ops.multi("clsr_tables_reg_multi" + self._th, ops.TableDesc, reg, l2e, l1e, self.ucount, self.losses[1:])
         if self.capture_grads:  # test hook: pre-clip gradients (regularisers included) + squared norms
             self.captured = dict(dense={n: g.detach().clone() for n, g in self.Gd.items()},
                                  tables={k: g.detach().clone() for k, g in tg.items()},

@@ -143,7 +143,17 @@ def init_tensor(kind, shape, hp, gen):
 # (examples/00_quick_start/sequential.py:94-205): they share the embedding layer and the logit MLP of
 # SequentialBaseModel (sequential_base_model.py:55-74,354-452) and differ in _build_seq_graph.
 SIB_TABLES = OrderedDict([("item", EMB + "item_embedding"), ("cate", EMB + "cate_embedding")])
-SIBLINGS = ("gru4rec", "din", "sli_rec", "a2svd", "dien", "caser")
+SIBLINGS = ("gru4rec", "din", "sli_rec", "a2svd", "dien", "caser", "ncf")
+# NCF (ncf.py:15-42): four tables of its own beside the trunk's, all [V, user_embedding_dim] -- the item tables too.  The
+# trunk's item / cate tables stay trained tables: the involved-row regulariser reaches them, the data gradient does not.
+NCF_TABLES = OrderedDict([("item", EMB + "item_embedding"), ("cate", EMB + "cate_embedding"),
+                          ("user_gmf", EMB + "user_gmf_embedding"), ("user_mlp", EMB + "user_mlp_embedding"),
+                          ("item_gmf", EMB + "item_gmf_embedding"), ("item_mlp", EMB + "item_mlp_embedding")])
+
+
+def sibling_tables(kind):
+    """Trained embedding tables of a sibling model: key -> variable name."""
+    return NCF_TABLES if kind == "ncf" else SIB_TABLES
 
 
 def sibling_kind(model_type):
@@ -169,7 +179,23 @@ def sibling_scopes(kind):
         return dict(asvd="sequential/a2svd/Attention_layer/")
     if kind == "caser":        # caser.py:43,60-65: variable_scope("caser") / "item" | "cate" / "vertical" | "horizonal" (sic)
         return dict(item="sequential/caser/item/", cate="sequential/caser/cate/")
+    if kind == "ncf":
+        # ncf.py:75-101: name_scope('ncf') does not reach variable names, so tf.contrib.layers.fully_connected numbers its
+        # default scope under "sequential": fully_connected, fully_connected_1, ... (the tower), then the output layer.
+        # Derived from TF 1.15's scoping rules and, like every other name here, unpinned until the TF 1.15 pin is run.
+        return dict(fc="sequential/fully_connected")
     raise ValueError("unknown sibling model %r" % (kind,))
+
+
+def ncf_specs(scope, Du, sizes):
+    """Tower and output layer of NCF in creation order: weights (Xavier uniform) and zero biases per tower layer, the
+    output layer (ncf.py:93-101) weights only."""
+    fc = lambda i: scope + ("" if i == 0 else "_%d" % i) + "/"
+    specs, last = [], 2 * Du
+    for i, n in enumerate(sizes):
+        specs += [(fc(i) + "weights", (last, int(n)), "glorot"), (fc(i) + "biases", (int(n),), "zero")]
+        last = int(n)
+    return specs + [(fc(len(sizes)) + "weights", (Du + last, 1), "glorot")]
 
 
 def caser_specs(scope, Dx, hp):
@@ -186,12 +212,16 @@ def caser_specs(scope, Dx, hp):
 
 
 def sibling_specs(dims, hp, kind):
-    """Ordered (name, shape, init kind) of every variable of GRU4Rec / DIN / SLi-Rec / A2SVD / DIEN / Caser."""
+    """Ordered (name, shape, init kind) of every variable of GRU4Rec / DIN / SLi-Rec / A2SVD / DIEN / Caser / NCF."""
     Vu, Vi, Vc = dims["Vu"], dims["Vi"], dims["Vc"]
     Di, Dc, Du, H = hp.item_embedding_dim, hp.cate_embedding_dim, hp.user_embedding_dim, hp.hidden_size
     D = Di + Dc
     sc = sibling_scopes(kind)
     specs = [(UNUSED_TABLE, (Vu, Du), "w"), (SIB_TABLES["item"], (Vi, Di), "w"), (SIB_TABLES["cate"], (Vc, Dc), "w")]
+    if kind == "ncf":       # no logit MLP: NCF overrides _fcn_net (one fully_connected without bias)
+        specs += [(NCF_TABLES[k], (Vu if k.startswith("user") else Vi, Du), "w")
+                  for k in ("user_gmf", "user_mlp", "item_gmf", "item_mlp")]
+        return specs + ncf_specs(sc["fc"], Du, list(hp.ncf_layer_sizes))
     if kind == "gru4rec":
         specs += gru_specs(sc["gru"], D, H)
         out_dim = H + D

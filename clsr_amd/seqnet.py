@@ -1,4 +1,4 @@
-"""GRU4Rec, DIN, DIEN, SLi-Rec, A2SVD and Caser on the kernels of the CLSR step.
+"""GRU4Rec, DIN, DIEN, SLi-Rec, A2SVD, Caser and NCF on the kernels of the CLSR step.
 
 The reference's quick-start trains these from the same script as CLSR (examples/00_quick_start/sequential.py:94-205);
 they sit on the same ``SequentialBaseModel`` trunk (embeddings + involved-row regulariser + logit MLP + softmax loss +
@@ -14,12 +14,16 @@ clip + Adam) and differ in ``_build_seq_graph``:
   CaserModel     models/sequential/caser.py:37-106       per table: one dense contraction of the flattened history
                                                          ("vertical") ++ width-1..L convolutions, ReLU, max over time
                                                          ("horizonal"), ++ target -- no mask anywhere
+  NCFModel       models/sequential/ncf.py:15-103         four id tables of its own: user_gmf * item_gmf ++ a ReLU tower
+                                                         over user_mlp ++ item_mlp; one bias-free output layer, no
+                                                         history encoder, no logit MLP, no batch-norm
 
 ``SeqNet`` re-uses CLSRNet wholesale -- parameter store, packed weights, the position-tiled GEMMs, the fused recurrence
 launch, the attention block (forward and backward), the MLP heads, sorted segmented embedding gradients, regularisers,
 clip, Adam, the stream structure, data parallelism -- and only re-states the three graphs and their backward passes.
 New device code: the A2SVD attention and the length scaling of DIN's history sum (csrc/sibling.hip); Caser's
-convolutions, forward and backward (csrc/caser.hip).
+convolutions, forward and backward (csrc/caser.hip); all of NCF between the ids and the per-line
+gradient slices (csrc/ncf.hip, DESIGN.md section 9c: one launch to score, two to train).
 
 A2SVD and GRU4Rec, whose one ``_fcn_net`` is the logit MLP, also train with the config's dropout (``user_dropout``,
 ``dropout``: csrc/dropout.hip, ``CLSRNet._mlp_fwd_drop``); the others refuse it by name
@@ -33,7 +37,7 @@ import torch
 from clsr_amd import ops
 from clsr_amd.net import CLSRNet, _StepState, _pad4
 from clsr_amd.ops import call, query
-from clsr_amd.params import SIB_TABLES, UNUSED_TABLE, sibling_kind, sibling_scopes, sibling_specs
+from clsr_amd.params import UNUSED_TABLE, sibling_kind, sibling_scopes, sibling_specs, sibling_tables
 
 LG = "sequential/logit_fcn/nn_part/"
 
@@ -42,15 +46,26 @@ class SeqNet(CLSRNet):
     def __init__(self, hp, dims, kind=None, **kw):
         self.kind = sibling_kind(kind if kind is not None else hp.model_type)
         if self.kind is None:
-            raise ValueError("SeqNet builds gru4rec / din / dien / sli_rec / a2svd / caser, got %r"
+            raise ValueError("SeqNet builds gru4rec / din / dien / sli_rec / a2svd / caser / ncf, got %r"
                              % (kind or hp.model_type,))
         self.sc = sibling_scopes(self.kind)
         if self.kind == "caser" and hp.hidden_size is None:
             hp = copy.copy(hp)
             hp.hidden_size = 0         # (caser.yaml has no recurrent encoder: nothing reads the width)
+        if self.kind == "ncf":
+            # settings without effect in NCF's graph (ncf.py never reads them): whatever they hold, the trunk sees values
+            # it can unpack and no dropout
+            hp = copy.copy(hp)
+            hp.hidden_size, hp.user_dropout, hp.embedding_dropout = hp.hidden_size or 0, False, 0.0
+            if len(hp.layer_sizes or ()) != 2:
+                hp.layer_sizes = [4, 4]
+            if len(hp.att_fcn_layer_sizes or ()) != 2:
+                hp.att_fcn_layer_sizes = None
         super(SeqNet, self).__init__(hp, dims, **kw)
         if self.kind == "caser":
             self._caser_setup()
+        if self.kind == "ncf":
+            self._ncf_setup()
         if self.kind == "sli_rec":
             self.enc_in = self.Di          # Time4LSTM reads the item embedding only (sli_rec.py:43-57)
         self.split_query = False
@@ -58,6 +73,11 @@ class SeqNet(CLSRNet):
     # ------------------------------------------------------------------ configuration
     def _check_supported(self):
         hp, bad = self.hp, []
+        if self.kind == "ncf":
+            bad = self._ncf_limits(hp)
+            if bad:
+                raise NotImplementedError("ncf HIP path does not support: " + "; ".join(bad))
+            return
         if hp.enable_BN is not True:
             bad.append("enable_BN must be True")
         if list(hp.activation) != ["relu"] * len(hp.activation):
@@ -111,6 +131,61 @@ class SeqNet(CLSRNet):
                        % (L, int(hp.item_embedding_dim), int(hp.cate_embedding_dim), n_v, n_h))
         return bad
 
+    @staticmethod
+    def _ncf_widths(hp):
+        """(Du, number of tower layers, the four width arguments of the clsr_ncf_* entry points)"""
+        sizes = [int(w) for w in (hp.ncf_layer_sizes or ())]
+        return int(hp.user_embedding_dim), len(sizes), tuple((sizes + [0, 0, 0, 0])[:4])
+
+    @classmethod
+    def _ncf_limits(cls, hp):
+        """What NCF's graph reads, by key name; the kernel's say on the whole shape (csrc/ncf.hip) once each key is in range.
+        layer_sizes, activation, enable_BN, the dropout keys, att_fcn_layer_sizes, hidden_size and attention_size are never
+        read by the reference's NCF: any value passes."""
+        bad = []
+        if any(float(getattr(hp, k)) != 0.0 for k in ("embed_l1", "layer_l1", "cross_l1", "cross_l2")):
+            bad.append("l1 / cross regularisers must be 0")
+        if hp.loss != "softmax" or hp.method != "classification":
+            bad.append("loss must be softmax / method classification")
+        Di, Dc = int(hp.item_embedding_dim), int(hp.cate_embedding_dim)
+        if Di % 4 or Dc % 4 or Di <= 0 or Dc <= 0 or Di + Dc > 256:
+            bad.append("item / cate embedding dims must be positive multiples of 4, at most 256 together")
+        if int(hp.max_seq_length) > 256:
+            bad.append("max_seq_length must be at most 256")
+        wmax, lmax, gmax = query("clsr_ncf_max_width"), query("clsr_ncf_max_layers"), query("clsr_ncf_max_group")
+        Du, nl, w4 = cls._ncf_widths(hp)
+        sizes = [int(w) for w in (hp.ncf_layer_sizes or ())]
+        if Du <= 0 or Du % 4 or Du > wmax:
+            bad.append("user_embedding_dim must be a positive multiple of 4, at most %d, got %d" % (wmax, Du))
+        if not 1 <= nl <= lmax:
+            bad.append("ncf_layer_sizes must hold 1 to %d layers, got %d" % (lmax, nl))
+        if any(w <= 0 or w % 4 or w > wmax for w in sizes):
+            bad.append("ncf_layer_sizes must be positive multiples of 4, at most %d, got %r" % (wmax, sizes))
+        G = int(hp.train_num_ngs) + 1
+        if not 1 <= G <= gmax:
+            bad.append("train_num_ngs must be at most %d (a softmax group of %d lines is one tile of the kernel), got %d"
+                       % (gmax - 1, gmax, G - 1))
+        if not bad and not query("clsr_ncf_supported", Du, nl, *w4, G):
+            bad.append("user_embedding_dim %d with ncf_layer_sizes %r: the tower's weights and a tile of 16 lines need %d "
+                       "words of LDS, the budget is %d (64 KB)"
+                       % (Du, sizes, query("clsr_ncf_lds_floats", Du, nl, *w4), query("clsr_ncf_lds_budget_floats")))
+        return bad
+
+    def _ncf_setup(self):
+        """NCF's shape constants and the parameter block the kernel addresses by offset: tower weights and biases, then the
+        output weights, consecutive in the dense buffer in the layout csrc/ncf.hip states (checked here, once)."""
+        self.nc_Du, self.nc_nl, self.nc_w4 = self._ncf_widths(self.hp)
+        names = [n for n, _, _ in self.specs if n.startswith(self.sc["fc"])]
+        first, o = self.P[names[0]], 0
+        for n in names:
+            if self.P[n].data_ptr() != first.data_ptr() + 4 * o:
+                raise AssertionError("NCF parameter block is not contiguous at %s" % n)
+            o += self.P[n].numel()
+        if o != query("clsr_ncf_param_floats", self.nc_Du, self.nc_nl, *self.nc_w4):
+            raise AssertionError("NCF parameter block: %d floats" % o)
+        g0 = (self.Gd[names[0]].data_ptr() - self.dense_grad.data_ptr()) // 4
+        self.nc_W, self.nc_dW, self.nc_P = first, self.dense_grad[g0:g0 + o], o
+
     def _caser_setup(self):
         """Caser's shape constants and the two parameter blocks the kernels address by offset: the variables of a table are
         consecutive in the dense buffer, in the layout csrc/caser.hip states (checked here, once)."""
@@ -134,18 +209,29 @@ class SeqNet(CLSRNet):
         return sibling_specs(self.dims, self.hp, self.kind)
 
     def _table_map(self):
-        return SIB_TABLES
+        return sibling_tables(self.kind)
 
     def _unused_tables(self):
         return (UNUSED_TABLE,)
 
     def _update_spec(self):
-        return (("item", None, 4, 0.0, 0.0, None, 0, 3), ("cate", None, 5, 0.0, 0.0, None, 1, 3))
+        trunk = (("item", None, 4, 0.0, 0.0, None, 0, 3), ("cate", None, 5, 0.0, 0.0, None, 1, 3))
+        if self.kind != "ncf":
+            return trunk
+        # NCF: item / cate get the regulariser only (their lookup-site slots 0..3 stay zero); its own four tables have
+        # one lookup site each (slots 6..9, written by the kernel from the un-merged slices) and no regulariser (slot None)
+        return trunk + tuple((k, None, None, 0.0, 0.0, None, 6 + i, 1)
+                             for i, k in enumerate(("user_gmf", "user_mlp", "item_gmf", "item_mlp")))
 
     def _att_qh(self, key):
         return 0
 
     def _det_merged(self, f):
+        if self.kind == "ncf":      # (no history lookup reaches the loss: nothing to merge)
+            return {}
+        return self._det_merged_hist(f)
+
+    def _det_merged_hist(self, f):
         """As in the CLSR graph, the target rows' ids follow the history lookup's ids in ONE sorted list per table: no
         float atomics on the target site, two runs of a step give bit-identical gradient tables."""
         return {"item": ("items", f["B"]), "cate": ("cates", f["B"])}
@@ -175,6 +261,8 @@ class SeqNet(CLSRNet):
         """Width of ``model_output`` (the logit MLP's input)."""
         if self.kind == "caser":
             return 2 * (int(self.hp.n_v) + int(self.hp.L) * int(self.hp.n_h)) + self.D
+        if self.kind == "ncf":
+            return self.nc_Du + int(self.hp.ncf_layer_sizes[-1])
         return {"gru4rec": self.H + self.D, "din": 3 * self.D, "sli_rec": 2 * self.D, "a2svd": 2 * self.D,
                 "dien": 3 * self.D + self.H}[self.kind]
 
@@ -210,6 +298,10 @@ class SeqNet(CLSRNet):
 
     # ------------------------------------------------------------------ forward
     def _forward(self, f, training, after_attention=None, early_aux=None):
+        if self.kind == "ncf":
+            if training:
+                raise ValueError("NCF's training forward is part of its step (clsr_ncf_train): use train_step")
+            return self._ncf_score(f)
         hp, P, kind, sc = self.hp, self.P, self.kind, self.sc
         B, T = f["B"], f["T"]
         G = self.G_train if (training and self.dedup) else ((f.get("G") or 1) if not training else 1)
@@ -362,6 +454,8 @@ class SeqNet(CLSRNet):
 
     # ------------------------------------------------------------------ training step
     def _train_step(self, f, apply):
+        if self.kind == "ncf":
+            return self._ncf_train_step(f, apply)
         hp, P, Gd, kind, sc = self.hp, self.P, self.Gd, self.kind, self.sc
         self._step = _StepState(f)     # (these graphs set none of its other fields: the shared phases read idle ones)
         if self.drop_on:
@@ -517,6 +611,87 @@ class SeqNet(CLSRNet):
             self._hist_grad_sorted(dhist, dM, dR, Hn, T, seq_len, ls, ss)
             call("clsr_scatter_add_rows", dtarget, D, 0, f["items"], 1, B, Di, self.tab_grad["item"], ss[2:])
             call("clsr_scatter_add_rows", dtarget, D, Di, f["cates"], 1, B, Dc, self.tab_grad["cate"], ss[3:])
+        if apply:
+            self._apply_updates()
+        return out
+
+    # ------------------------------------------------------------------ NCF
+    def _ncf_tables(self):
+        tb = self.tables
+        return tb["user_gmf"], tb["user_mlp"], tb["item_gmf"], tb["item_mlp"]
+
+    def _ncf_score(self, f):
+        """Evaluation / predict: ONE launch from the ids to the logits (no history gather: nothing reads it)."""
+        B, T = f["B"], f["T"]
+        G = ((f.get("G") or 1) if self.dedup else 1) if f.get("compact") else 1
+        if B % G:
+            raise ValueError("feed rows (%d) must be a multiple of the history group (%d)" % (B, G))
+        self.last_shape = (B, T, G, B // G)
+        logit, mo = self._buf("logit", B), self._buf("model_output", B, self.out_dim)
+        # (a compact feed holds one user per group of G lines; the gathers are per line all the same)
+        call("clsr_ncf_score", f["users"], G, f["items"], *self._ncf_tables(), self.nc_W, self.nc_Du, self.nc_nl,
+             *self.nc_w4, B, logit, mo)
+        return dict(logit=logit, model_output=mo)
+
+    def _ncf_train_step(self, f, apply):
+        """Marks, the two launches of clsr_ncf_train, then the shared phases: the partial-sum reduction of the dense
+        gradients, the table-gradient path over the four slice buffers, regulariser + clip + optimiser."""
+        hp = self.hp
+        self._step = _StepState(f)
+        B, T = f["B"], f["T"]
+        G = self.G_train if self.dedup else 1
+        Gl = hp.train_num_ngs + 1
+        if B % Gl:
+            raise ValueError("training feed rows (%d) must be a multiple of 1+train_num_ngs (%d)" % (B, Gl))
+        Hn = B // G
+        hs = 1 if f.get("compact") else G
+        udiv = G if f.get("compact") else 1        # lines per entry of f["users"]
+        self.last_shape = (B, T, G, Hn)
+        Du, W, fl = self.nc_Du, self.out_dim, self.tab_flags
+        call("clsr_zero_doubles", self.losses, 8)
+        call("clsr_zero_doubles", self.sumsq_tab, 16)
+        # involved rows: item / cate as in every model of the trunk (their regulariser), the four NCF tables' touched rows
+        mark = ops.MarkDesc.row
+        ops.multi("clsr_mark_rows_multi", ops.MarkDesc, [
+            mark(idx=f["item_history"], flags=fl["item"], nrows=Hn, row_stride=hs * T, ncols=T),
+            mark(idx=f["items"], flags=fl["item"], nrows=B, row_stride=1, ncols=1),
+            mark(idx=f["item_cate_history"], flags=fl["cate"], nrows=Hn, row_stride=hs * T, ncols=T),
+            mark(idx=f["cates"], flags=fl["cate"], nrows=B, row_stride=1, ncols=1),
+            mark(idx=f["users"], flags=fl["user_gmf"], nrows=B // udiv, row_stride=1, ncols=1),
+            mark(idx=f["users"], flags=fl["user_mlp"], nrows=B // udiv, row_stride=1, ncols=1),
+            mark(idx=f["items"], flags=fl["item_gmf"], nrows=B, row_stride=1, ncols=1),
+            mark(idx=f["items"], flags=fl["item_mlp"], nrows=B, row_stride=1, ncols=1)])
+        logit, mo, dlogit = self._buf("logit", B), self._buf("model_output", B, W), self._buf("dlogit", B)
+        keys = ("user_gmf", "user_mlp", "item_gmf", "item_mlp")
+        sl = [self._buf("nc.d_" + k, B, Du) for k in keys]
+        uid = self._buf("nc.uid", B, dtype=torch.int32)
+        shape = (self.nc_Du, self.nc_nl) + self.nc_w4
+        parts = query("clsr_ncf_parts", B, Gl)
+        ws = self._buf("nc.ws", query("clsr_ncf_workspace_floats", B, Gl, *shape))
+        ss = self.sumsq_tab
+        call("clsr_ncf_train", f["users"], udiv, f["items"], f["labels"], *self._ncf_tables(), self.nc_W, *shape, B, Gl,
+             1.0 / ((B // Gl) * self.dp_world), logit, mo, dlogit, sl[0], sl[1], sl[2], sl[3], uid, ws, self.losses[0:],
+             ss[6:])
+        self._rp(ws[10 * parts:], parts, self.nc_P, self.nc_P, self.nc_dW)
+        self._dw_flush()
+        # ---- the slices reach the gradient tables (their squared norms are in slots 6..9 already: taken from the slices)
+        tg = self.tab_grad
+        ids = (uid, uid, f["items"], f["items"])
+        if self.det_grads:
+            sort = []
+            for name, idx, V in (("ncf_user", uid, self.dims["Vu"]), ("ncf_item", f["items"], self.dims["Vi"])):
+                sort.append(ops.SortIdsDesc.row(
+                    ids=idx, keys_out=self._buf("sort.keys." + name, B, dtype=torch.int32),
+                    perm_out=self._buf("sort.perm." + name, B, dtype=torch.int32), nrows=B, row_stride=1, ncols=1,
+                    bits=max(1, (V - 1).bit_length())))
+            sws = self._buf("sort.ws", query("clsr_sort_ids_stable_workspace_bytes", 2 * B, 2), dtype=torch.uint8)
+            ops.sort_ids_stable_multi(sort, sws)
+            self._segsum("ncf", [self._site_row("ncf_" + k.split("_")[0], s, Du, 0, Du, B, tg[k], None)
+                                 for k, s in zip(keys, sl)])
+        else:
+            for k, s, idx in zip(keys, sl, ids):
+                call("clsr_scatter_add_rows", s, Du, 0, idx, 1, B, Du, tg[k], None)
+        out = dict(logit=logit, model_output=mo, dlogit=dlogit, slices=dict(zip(keys, sl)))
         if apply:
             self._apply_updates()
         return out

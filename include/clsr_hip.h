@@ -781,6 +781,43 @@ int clsr_caser_hconv_bwd(const float* dpool, int ldd, const float* pooled, int l
                          long Hn, int T, int Di, int Dc, const float* Wi, const float* Wc, int L, int n_v, int n_h,
                          float* dhist, float* dWi, float* dWc, float* workspace, void* stream);
 
+/* NCF (models/sequential/ncf.py, csrc/ncf.hip): per feed line l with user u = users[l / user_div] and item i = items[l]
+ *   gmf = user_gmf[u] * item_gmf[i];  a_0 = user_mlp[u] ++ item_mlp[i];  a_j = relu(b_j + a_{j-1} . W_j), j = 1 .. nl;
+ *   model_output = gmf ++ a_nl  [B, Du + w_nl];  logit = model_output . w_out
+ * The four tables are fp32 [V, Du]; the tower has nl layers of widths w0 .. (unused widths: 0).  params: the block
+ *   W_1 [2 Du][w0] | b_1 | W_2 [w0][w1] | b_2 | ... | w_out [Du + w_nl]     (clsr_ncf_param_floats floats, no padding),
+ * held in LDS for the whole launch; a workgroup walks tiles of clsr_ncf_tile_lines(G) lines (whole softmax groups).
+ * clsr_ncf_supported: Du and every width a positive multiple of 4 up to clsr_ncf_max_width() (128), 1 .. clsr_ncf_max_layers()
+ * (4) layers, a softmax group of at most clsr_ncf_max_group() (16) lines, and clsr_ncf_lds_floats(...) -- the block with
+ * every weight row padded by one word, plus 16 lines of 3 Du + sum w + 1 words, plus 32 -- within
+ * clsr_ncf_lds_budget_floats() (64 KB less 256 bytes).  An unsupported shape: -1 from the entry points.
+ * clsr_ncf_score: one launch; logit [B], model_output [B, Du + w_nl] or NULL.
+ * clsr_ncf_train: two launches.  The first: forward, the group softmax (G consecutive lines, labels [B], scale = 1 / groups
+ * the mean runs over) with dlogit [B] (or NULL), the tower backward, the un-merged slices d_* [B, Du] of the four
+ * lookups, user_ids [B] (the user of every line), and per workgroup a row of dense-gradient partial sums: workspace
+ * (clsr_ncf_workspace_floats floats, 8-byte aligned) = [parts][5] doubles, then [parts][param floats] in the layout of
+ * params, parts = clsr_ncf_parts(B, G) -- the caller reduces the rows (clsr_reduce_parts_multi).  The second adds the
+ * workgroups' losses to loss_out[0] and STORES the squared norms of the slices in sumsq4[0..3] (user_gmf, user_mlp,
+ * item_gmf, item_mlp; may be NULL), both in ascending workgroup order.  No atomics. */
+int clsr_ncf_supported(int Du, int nl, int w0, int w1, int w2, int w3, int G);
+int clsr_ncf_max_width(void);
+int clsr_ncf_max_layers(void);
+int clsr_ncf_max_group(void);
+long clsr_ncf_lds_budget_floats(void);
+long clsr_ncf_lds_floats(int Du, int nl, int w0, int w1, int w2, int w3);
+long clsr_ncf_param_floats(int Du, int nl, int w0, int w1, int w2, int w3);
+int clsr_ncf_tile_lines(int G);
+int clsr_ncf_parts(long B, int G);
+long clsr_ncf_workspace_floats(long B, int G, int Du, int nl, int w0, int w1, int w2, int w3);
+int clsr_ncf_score(const int* users, int user_div, const int* items, const float* user_gmf, const float* user_mlp,
+                   const float* item_gmf, const float* item_mlp, const float* params, int Du, int nl, int w0, int w1,
+                   int w2, int w3, long B, float* logit, float* model_output, void* stream);
+int clsr_ncf_train(const int* users, int user_div, const int* items, const float* labels, const float* user_gmf,
+                   const float* user_mlp, const float* item_gmf, const float* item_mlp, const float* params, int Du,
+                   int nl, int w0, int w1, int w2, int w3, long B, int G, float scale, float* logit, float* model_output,
+                   float* dlogit, float* d_user_gmf, float* d_user_mlp, float* d_item_gmf, float* d_item_mlp,
+                   int* user_ids, float* workspace, double* loss_out, double* sumsq4, void* stream);
+
 /* ---- dropout of _fcn_net's hidden layers (csrc/dropout.hip, csrc/philox.h): base_model.py _active_layer, user_dropout --
  * a = relu(dropout(bn(z))), keep = 1 - dropout[layer].  The mask is a function of (seed, draw, layer, GLOBAL row, column):
  * Philox4x32-10 with counter (row0 + r, c / 4, layer, draw) and key (seed low, seed high); its four words serve columns
