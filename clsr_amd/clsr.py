@@ -675,6 +675,12 @@ class NCFModel(_SiblingModel):
     kind = "ncf"
 
 
+class NextItNetModel(_SiblingModel):
+    """Reference ``NextItNetModel`` (models/sequential/nextitnet.py): hparams ``dilations``, ``kernel_size``; built with
+    ``NextItNetIterator`` (left-padded histories, a target per position in training feeds)."""
+    kind = "nextitnet"
+
+
 class SLI_RECModel(_SiblingModel):
     """Reference ``SLI_RECModel`` (models/sequential/sli_rec.py)."""
     kind = "sli_rec"

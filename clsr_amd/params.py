@@ -130,6 +130,10 @@ def init_tensor(kind, shape, hp, gen):
         fan_out = shape[1] if len(shape) > 1 else shape[0]
         lim = math.sqrt(6.0 / (fan_in + fan_out))
         return (torch.rand(shape, generator=gen) * 2 - 1) * lim
+    if kind == "tnormal_0.02":      # tf.truncated_normal_initializer(stddev=0.02): resample beyond two sigma
+        x = torch.empty(shape)
+        torch.nn.init.trunc_normal_(x, mean=0.0, std=0.02, a=-0.04, b=0.04, generator=gen)
+        return x
     if kind == "glorot_conv":       # tf glorot_uniform on a conv kernel [width, in, out]: fans scaled by the width
         lim = math.sqrt(6.0 / (shape[0] * (shape[1] + shape[2])))
         return (torch.rand(shape, generator=gen) * 2 - 1) * lim
@@ -143,7 +147,7 @@ def init_tensor(kind, shape, hp, gen):
 # (examples/00_quick_start/sequential.py:94-205): they share the embedding layer and the logit MLP of
 # SequentialBaseModel (sequential_base_model.py:55-74,354-452) and differ in _build_seq_graph.
 SIB_TABLES = OrderedDict([("item", EMB + "item_embedding"), ("cate", EMB + "cate_embedding")])
-SIBLINGS = ("gru4rec", "din", "sli_rec", "a2svd", "dien", "caser", "ncf")
+SIBLINGS = ("gru4rec", "din", "sli_rec", "a2svd", "dien", "caser", "ncf", "nextitnet")
 # NCF (ncf.py:15-42): four tables of its own beside the trunk's, all [V, user_embedding_dim] -- the item tables too.  The
 # trunk's item / cate tables stay trained tables: the involved-row regulariser reaches them, the data gradient does not.
 NCF_TABLES = OrderedDict([("item", EMB + "item_embedding"), ("cate", EMB + "cate_embedding"),
@@ -184,6 +188,8 @@ def sibling_scopes(kind):
         # default scope under "sequential": fully_connected, fully_connected_1, ... (the tower), then the output layer.
         # Derived from TF 1.15's scoping rules and, like every other name here, unpinned until the TF 1.15 pin is run.
         return dict(fc="sequential/fully_connected")
+    if kind == "nextitnet":    # nextitnet.py:41,127-131: variable_scope("nextitnet") / one scope per residual block
+        return dict(nx="sequential/nextitnet/")
     raise ValueError("unknown sibling model %r" % (kind,))
 
 
@@ -211,8 +217,28 @@ def caser_specs(scope, Dx, hp):
     return specs
 
 
+def nextitnet_block_scope(scope, layer_id, dilation):
+    return scope + "nextitnet_residual_block_one_decoder_layer_%d_%d/" % (layer_id, dilation)
+
+
+def nextitnet_specs(scope, C, hp):
+    """Variables of the residual blocks (nextitnet.py:101-232) in creation order, one block per entry of ``dilations``:
+    conv weights are [1, width, in channels, out channels] (truncated normal, stddev 0.02), biases and beta zero, gamma one.
+    ``trainable=train`` has no effect under AUTO_REUSE (the training branch is built first): all of them train."""
+    half, k, specs = int(0.5 * int(C)), int(hp.kernel_size), []
+    for i, d in enumerate(hp.dilations):
+        b = nextitnet_block_scope(scope, i, int(d))
+        specs += [(b + "layer_norm1/beta", (C,), "zero"), (b + "layer_norm1/gamma", (C,), "one"),
+                  (b + "conv1d_1/weight", (1, 1, C, half), "tnormal_0.02"), (b + "conv1d_1/bias", (half,), "zero"),
+                  (b + "layer_norm2/beta", (half,), "zero"), (b + "layer_norm2/gamma", (half,), "one"),
+                  (b + "dilated_conv/weight", (1, k, half, half), "tnormal_0.02"), (b + "dilated_conv/bias", (half,), "zero"),
+                  (b + "layer_norm3/beta", (half,), "zero"), (b + "layer_norm3/gamma", (half,), "one"),
+                  (b + "conv1d_2/weight", (1, 1, half, C), "tnormal_0.02"), (b + "conv1d_2/bias", (C,), "zero")]
+    return specs
+
+
 def sibling_specs(dims, hp, kind):
-    """Ordered (name, shape, init kind) of every variable of GRU4Rec / DIN / SLi-Rec / A2SVD / DIEN / Caser / NCF."""
+    """Ordered (name, shape, init kind) of every variable of GRU4Rec / DIN / SLi-Rec / A2SVD / DIEN / Caser / NCF / NextItNet."""
     Vu, Vi, Vc = dims["Vu"], dims["Vi"], dims["Vc"]
     Di, Dc, Du, H = hp.item_embedding_dim, hp.cate_embedding_dim, hp.user_embedding_dim, hp.hidden_size
     D = Di + Dc
@@ -231,6 +257,9 @@ def sibling_specs(dims, hp, kind):
     elif kind == "caser":
         specs += caser_specs(sc["item"], Di, hp) + caser_specs(sc["cate"], Dc, hp)
         out_dim = 2 * (int(hp.n_v) + int(hp.L) * int(hp.n_h)) + D
+    elif kind == "nextitnet":
+        specs += nextitnet_specs(sc["nx"], D, hp)
+        out_dim = 2 * D
     elif kind == "dien":
         att = list(hp.att_fcn_layer_sizes)
         specs += gru_specs(sc["gru1"], D, H)

@@ -1,4 +1,4 @@
-"""GRU4Rec, DIN, DIEN, SLi-Rec, A2SVD, Caser and NCF on the kernels of the CLSR step.
+"""GRU4Rec, DIN, DIEN, SLi-Rec, A2SVD, Caser, NCF and NextItNet on the kernels of the CLSR step.
 
 The reference's quick-start trains these from the same script as CLSR (examples/00_quick_start/sequential.py:94-205);
 they sit on the same ``SequentialBaseModel`` trunk (embeddings + involved-row regulariser + logit MLP + softmax loss +
@@ -17,13 +17,17 @@ clip + Adam) and differ in ``_build_seq_graph``:
   NCFModel       models/sequential/ncf.py:15-103         four id tables of its own: user_gmf * item_gmf ++ a ReLU tower
                                                          over user_mlp ++ item_mlp; one bias-free output layer, no
                                                          history encoder, no logit MLP, no batch-norm
+  NextItNetModel models/sequential/nextitnet.py:21-232   a stack of residual blocks (layer norm, ReLU, 1x1 conv, causal dilated
+                                                         conv, 1x1 conv) over the history; trained on EVERY position: the
+                                                         logit MLP sees Hn T G rows -- no mask anywhere
 
 ``SeqNet`` re-uses CLSRNet wholesale -- parameter store, packed weights, the position-tiled GEMMs, the fused recurrence
 launch, the attention block (forward and backward), the MLP heads, sorted segmented embedding gradients, regularisers,
 clip, Adam, the stream structure, data parallelism -- and only re-states the three graphs and their backward passes.
 New device code: the A2SVD attention and the length scaling of DIN's history sum (csrc/sibling.hip); Caser's
 convolutions, forward and backward (csrc/caser.hip); all of NCF between the ids and the per-line
-gradient slices (csrc/ncf.hip, DESIGN.md section 9c: one launch to score, two to train).
+gradient slices (csrc/ncf.hip, DESIGN.md section 9c: one launch to score, two to train); NextItNet's whole stack of blocks,
+one launch forward and one backward (csrc/nextitnet.hip).
 
 A2SVD and GRU4Rec, whose one ``_fcn_net`` is the logit MLP, also train with the config's dropout (``user_dropout``,
 ``dropout``: csrc/dropout.hip, ``CLSRNet._mlp_fwd_drop``); the others refuse it by name
@@ -37,7 +41,7 @@ import torch
 from clsr_amd import ops
 from clsr_amd.net import CLSRNet, _StepState, _pad4
 from clsr_amd.ops import call, query
-from clsr_amd.params import UNUSED_TABLE, sibling_kind, sibling_scopes, sibling_specs, sibling_tables
+from clsr_amd.params import UNUSED_TABLE, nextitnet_block_scope, sibling_kind, sibling_scopes, sibling_specs, sibling_tables
 
 LG = "sequential/logit_fcn/nn_part/"
 
@@ -46,7 +50,7 @@ class SeqNet(CLSRNet):
     def __init__(self, hp, dims, kind=None, **kw):
         self.kind = sibling_kind(kind if kind is not None else hp.model_type)
         if self.kind is None:
-            raise ValueError("SeqNet builds gru4rec / din / dien / sli_rec / a2svd / caser / ncf, got %r"
+            raise ValueError("SeqNet builds gru4rec / din / dien / sli_rec / a2svd / caser / ncf / nextitnet, got %r"
                              % (kind or hp.model_type,))
         self.sc = sibling_scopes(self.kind)
         if self.kind == "caser" and hp.hidden_size is None:
@@ -61,9 +65,16 @@ class SeqNet(CLSRNet):
                 hp.layer_sizes = [4, 4]
             if len(hp.att_fcn_layer_sizes or ()) != 2:
                 hp.att_fcn_layer_sizes = None
+        if self.kind == "nextitnet":
+            # settings without effect in NextItNet's graph (nextitnet.py never reads them): whatever they hold, the trunk
+            # sees values it can unpack
+            hp = copy.copy(hp)
+            hp.hidden_size, hp.att_fcn_layer_sizes = 0, None       # (attention_size: the trunk never reads it for this kind)
         super(SeqNet, self).__init__(hp, dims, **kw)
         if self.kind == "caser":
             self._caser_setup()
+        if self.kind == "nextitnet":
+            self._nextitnet_setup()
         if self.kind == "ncf":
             self._ncf_setup()
         if self.kind == "sli_rec":
@@ -82,11 +93,13 @@ class SeqNet(CLSRNet):
             bad.append("enable_BN must be True")
         if list(hp.activation) != ["relu"] * len(hp.activation):
             bad.append("activation must be relu")
-        self._check_dropout(hp, bad, mlp_only=self.kind in ("a2svd", "gru4rec", "caser"))
-        if self.kind == "caser" and self.dropout_in_effect(hp):
+        self._check_dropout(hp, bad, mlp_only=self.kind in ("a2svd", "gru4rec", "caser", "nextitnet"))
+        if self.kind in ("caser", "nextitnet") and self.dropout_in_effect(hp):
             # (its one _fcn_net is the logit MLP too: the tail of A2SVD / GRU4Rec would serve; not wired up or tested yet)
-            bad.append("user_dropout with dropout %r: dropout in Caser's logit MLP is not implemented yet"
-                       % ([float(d) for d in hp.dropout],))
+            bad.append("user_dropout with dropout %r: dropout in %s's logit MLP is not implemented yet"
+                       % ([float(d) for d in hp.dropout], "Caser" if self.kind == "caser" else "NextItNet"))
+        if self.kind == "nextitnet" and self.precision != "fp32":
+            bad.append("precision must be 'fp32', got %r (NextItNet's kernels are fp32 FMA chains)" % (self.precision,))
         if any(float(getattr(hp, k)) != 0.0 for k in ("embed_l1", "layer_l1", "cross_l1", "cross_l2")):
             bad.append("l1 / cross regularisers must be 0")
         if hp.loss != "softmax" or hp.method != "classification":
@@ -106,6 +119,8 @@ class SeqNet(CLSRNet):
         bad += self._shape_limits(hp, rnn=self.kind in ("gru4rec", "sli_rec", "dien"))
         if self.kind == "caser":
             bad += self._caser_limits(hp, bool(bad))
+        if self.kind == "nextitnet":
+            bad += self._nextitnet_limits(hp)
         if self.kind in ("a2svd", "sli_rec") and int(hp.attention_size) % 4:
             bad.append("attention_size must be a multiple of 4")
         if bad:
@@ -130,6 +145,58 @@ class SeqNet(CLSRNet):
                        "the wider table must fit 64 KB of LDS, and n_v + 3 L n_h must be at most 16 384"
                        % (L, int(hp.item_embedding_dim), int(hp.cate_embedding_dim), n_v, n_h))
         return bad
+
+    @staticmethod
+    def _nextitnet_limits(hp):
+        """NextItNet's own keys, by name; the kernels' say on the whole shape (csrc/nextitnet.hip) once each key is in
+        range.  hidden_size, attention_size and att_fcn_layer_sizes are never read: any value passes."""
+        bad = []
+        if not getattr(hp, "dilations", None) or getattr(hp, "kernel_size", None) is None:
+            return ["dilations and kernel_size must be set (nextitnet.yaml: dilations [1, 2, 4, 1, 2, 4], kernel_size 3)"]
+        cmax, kmax, nbmax = (query("clsr_nextitnet_max_" + n) for n in ("channels", "kernel", "blocks"))
+        dil, k = list(hp.dilations), hp.kernel_size
+        ok_d = all(isinstance(d, (int, np.integer)) and not isinstance(d, bool) and d >= 1 for d in dil)
+        if not 1 <= len(dil) <= nbmax or not ok_d:
+            bad.append("dilations must hold 1 to %d positive integers, got %r" % (nbmax, dil))
+        if not isinstance(k, (int, np.integer)) or not 1 <= k <= kmax:
+            bad.append("kernel_size must lie in 1..%d, got %r" % (kmax, k))
+        Di, Dc, T = int(hp.item_embedding_dim), int(hp.cate_embedding_dim), int(hp.max_seq_length)
+        C = Di + Dc
+        if Di <= 0 or Dc <= 0 or C % 8 or C > cmax:
+            bad.append("item_embedding_dim + cate_embedding_dim must be a multiple of 8, at most %d (half of it is the "
+                       "blocks' inner width), got %d + %d" % (cmax, Di, Dc))
+        ngs = int(hp.train_num_ngs)
+        if not 1 <= ngs <= 255:
+            bad.append("train_num_ngs must lie in 1..255 (every position is a softmax group of 1 + train_num_ngs rows), "
+                       "got %d" % ngs)
+        if not bad and 1 <= T <= 256 and not query("clsr_nextitnet_supported", T, C, int(k), len(dil),
+                                                              min(int(max(dil)), 1 << 20)):
+            bad.append("max_seq_length %d with item_embedding_dim + cate_embedding_dim = %d: a history's backward state needs "
+                       "%d bytes of LDS, the budget is %d (64 KB)"
+                       % (T, C, query("clsr_nextitnet_lds_bytes", T, C, 1), query("clsr_nextitnet_lds_budget_bytes")))
+        return bad
+
+    def _nextitnet_setup(self):
+        """NextItNet's shape constants and the parameter block the kernels address by offset: the variables of all blocks
+        are consecutive in the dense buffer, in the layout csrc/nextitnet.hip states (checked here, once)."""
+        hp = self.hp
+        self.nx_T, self.nx_k, self.nx_nb = int(hp.max_seq_length), int(hp.kernel_size), len(hp.dilations)
+        names = [n for n, _, _ in self.specs if n.startswith(self.sc["nx"])]
+        first, o = self.P[names[0]], 0
+        for n in names:
+            if self.P[n].data_ptr() != first.data_ptr() + 4 * o:
+                raise AssertionError("NextItNet parameter block is not contiguous at %s" % n)
+            o += self.P[n].numel()
+        if o != query("clsr_nextitnet_param_floats", self.D, self.nx_k, self.nx_nb):
+            raise AssertionError("NextItNet parameter block: %d floats" % o)
+        if first.data_ptr() % 16:
+            raise AssertionError("NextItNet parameter block is not 16-byte aligned")
+        if not names[0].startswith(nextitnet_block_scope(self.sc["nx"], 0, int(hp.dilations[0])) + "layer_norm1/beta"):
+            raise AssertionError("NextItNet parameter block starts at %s" % names[0])
+        g0 = (self.Gd[names[0]].data_ptr() - self.dense_grad.data_ptr()) // 4
+        self.nx_W, self.nx_dW, self.nx_P = first, self.dense_grad[g0:g0 + o], o
+        # (a rate of T or more only ever reads the padding: every such rate computes what T does)
+        self.nx_dil = torch.tensor([min(int(d), 1 << 20) for d in hp.dilations], dtype=torch.int32, device=self.device)
 
     @staticmethod
     def _ncf_widths(hp):
@@ -229,6 +296,11 @@ class SeqNet(CLSRNet):
     def _det_merged(self, f):
         if self.kind == "ncf":      # (no history lookup reaches the loss: nothing to merge)
             return {}
+        if self.kind == "nextitnet":
+            # the Hn T G target rows of a training step, ids in (h, t, g) order (clsr_nextitnet_rows; _nextitnet_forward
+            # hangs the two id lists into the feed)
+            n = f["B"] * f["T"]
+            return {"item": ("nx_items_t", n), "cate": ("nx_cates_t", n)}
         return self._det_merged_hist(f)
 
     def _det_merged_hist(self, f):
@@ -263,6 +335,8 @@ class SeqNet(CLSRNet):
             return 2 * (int(self.hp.n_v) + int(self.hp.L) * int(self.hp.n_h)) + self.D
         if self.kind == "ncf":
             return self.nc_Du + int(self.hp.ncf_layer_sizes[-1])
+        if self.kind == "nextitnet":
+            return 2 * self.D
         return {"gru4rec": self.H + self.D, "din": 3 * self.D, "sli_rec": 2 * self.D, "a2svd": 2 * self.D,
                 "dien": 3 * self.D + self.H}[self.kind]
 
@@ -302,6 +376,8 @@ class SeqNet(CLSRNet):
             if training:
                 raise ValueError("NCF's training forward is part of its step (clsr_ncf_train): use train_step")
             return self._ncf_score(f)
+        if self.kind == "nextitnet":
+            return self._nextitnet_forward(f, training, early_aux)
         hp, P, kind, sc = self.hp, self.P, self.kind, self.sc
         B, T = f["B"], f["T"]
         G = self.G_train if (training and self.dedup) else ((f.get("G") or 1) if not training else 1)
@@ -456,6 +532,8 @@ class SeqNet(CLSRNet):
     def _train_step(self, f, apply):
         if self.kind == "ncf":
             return self._ncf_train_step(f, apply)
+        if self.kind == "nextitnet":
+            return self._nextitnet_train_step(f, apply)
         hp, P, Gd, kind, sc = self.hp, self.P, self.Gd, self.kind, self.sc
         self._step = _StepState(f)     # (these graphs set none of its other fields: the shared phases read idle ones)
         if self.drop_on:
@@ -692,6 +770,119 @@ class SeqNet(CLSRNet):
             for k, s, idx in zip(keys, sl, ids):
                 call("clsr_scatter_add_rows", s, Du, 0, idx, 1, B, Du, tg[k], None)
         out = dict(logit=logit, model_output=mo, dlogit=dlogit, slices=dict(zip(keys, sl)))
+        if apply:
+            self._apply_updates()
+        return out
+
+    # ------------------------------------------------------------------ NextItNet
+    def _nextitnet_forward(self, f, training, early_aux=None):
+        """History gather, ONE launch for the stack of blocks, the target rows into columns C .. 2C of model_output, the
+        logit MLP.  Training: model_output holds Hn T G rows in (h, t, g) order (row (h, t, g) = x_L[h, t] ++ the target of
+        feed row h G + g at position t) and every block's input is saved; scoring: one row per feed line, x_L[:, T - 1]."""
+        B, T = f["B"], f["T"]
+        D, Di, Dc, W = self.D, self.Di, self.Dc, self.out_dim
+        if T != self.nx_T:
+            raise ValueError("NextItNet's feed must hold max_seq_length = %d steps, got %d" % (self.nx_T, T))
+        # (the reference's graph itself takes every G-th history of a training feed: nextitnet.py:29-38)
+        G = self.G_train if training else ((f.get("G") or 1) if f.get("compact") else 1)
+        if B % G:
+            raise ValueError("feed rows (%d) must be a multiple of %d" % (B, G))
+        Hn = B // G
+        R = Hn * T * G if training else B
+        if f["items"].numel() != R or f["cates"].numel() != R:
+            raise ValueError("NextItNet %s feed: items / cates must hold %d ids per row (NextItNetIterator), got shape %r"
+                             % ("training" if training else "scoring", T if training else 1, tuple(f["items"].shape)))
+        self.last_shape = (R, T, G, Hn)
+        self._pack_all(training)
+        hs = 1 if f.get("compact") else G
+        items, cates, labels = f["items"], f["cates"], f["labels"]
+        if training:
+            items = f["nx_items_t"] = self._buf("nx.items_t", R, dtype=torch.int32)
+            cates = f["nx_cates_t"] = self._buf("nx.cates_t", R, dtype=torch.int32)
+            labels = self._buf("nx.labels_t", R)
+            call("clsr_nextitnet_rows", f["items"], f["cates"], f["labels"], Hn, T, G, items, cates, labels)
+        step_start = self._fork_point()
+        hist = self._buf("hist", Hn, T, D)
+        # (the trunk's gather also writes the masked mean and the recent mean, 2 Hn D floats that nothing in this graph
+        # reads: the entry point takes no NULL for them, and they are 1 / T of the launch's traffic)
+        call("clsr_gather_hist_fwd", self.tables["item"], self.tables["cate"], f["item_history"],
+             f["item_cate_history"], hs * T, f["seq_len"], hs, Hn, T, Di, Dc, 1, hist, self._buf("hist_mean", Hn, D),
+             self._buf("hist_recent", Hn, D))
+        mo = self._buf("model_output", R, W)
+        tb = self.tables
+        ops.multi("clsr_gather_rows_multi", ops.GatherDesc, [
+            ops.GatherDesc.row(table=tb["item"], idx=items, out=mo, idx_stride=1, N=R, C=Di, ldo=W, col0=D),
+            ops.GatherDesc.row(table=tb["cate"], idx=cates, out=mo, idx_stride=1, N=R, C=Dc, ldo=W, col0=D + Di)])
+        if early_aux is not None or training:
+            with self._branch("@aux", after=step_start):
+                if early_aux is not None:
+                    early_aux()
+                if training:
+                    self._sort_hist_ids(f, Hn, T, hs)
+        saved = self._buf("nx.saved", self.nx_nb, Hn, T, D) if training else None
+        call("clsr_nextitnet_fwd", hist, Hn, T, D, self.nx_W, self.nx_k, self.nx_nb, self.nx_dil, saved, mo, W, G,
+             0 if training else 1)
+        self._join()
+        logit = self._mlp_fwd("lg", LG, mo, W, W, (self.L0, self.L1), R, training)
+        return dict(hist_input=hist, model_output=mo, logit=logit, labels_t=labels, saved=saved)
+
+    def _nextitnet_train_step(self, f, apply):
+        """Marks (the 2-D items / cates included), the forward, the group softmax over G consecutive rows of every
+        position, the logit MLP's backward over Hn T G rows, ONE launch back through the blocks, then the shared phases:
+        the partial-sum reduction of the dense gradients, the table-gradient path, regulariser + clip + optimiser."""
+        self._step = _StepState(f)
+        B, T = f["B"], f["T"]
+        G = self.G_train
+        if B % G:
+            raise ValueError("training feed rows (%d) must be a multiple of 1+train_num_ngs (%d)" % (B, G))
+        Hn = B // G
+        R = Hn * T * G
+        D, Di, Dc, W = self.D, self.Di, self.Dc, self.out_dim
+        hs = 1 if f.get("compact") else G
+        zpool = self._buf("zero_pool", 2 * Hn * D)
+        fl = self.tab_flags
+
+        def zero_and_mark():
+            call("clsr_zero_doubles", self.losses, 8)
+            call("clsr_zero_doubles", self.sumsq_tab, 16)
+            call("clsr_zero_floats", zpool, zpool.numel())
+            mark = ops.MarkDesc.row
+            ops.multi("clsr_mark_rows_multi", ops.MarkDesc, [
+                mark(idx=f["item_history"], flags=fl["item"], nrows=Hn, row_stride=hs * T, ncols=T),
+                mark(idx=f["items"], flags=fl["item"], nrows=B, row_stride=T, ncols=T),
+                mark(idx=f["item_cate_history"], flags=fl["cate"], nrows=Hn, row_stride=hs * T, ncols=T),
+                mark(idx=f["cates"], flags=fl["cate"], nrows=B, row_stride=T, ncols=T)])
+        take = self._carver(zpool)
+        # no masked mean / recent mean in this graph: the segmented sums take their gradients as arguments all the same, so
+        # they get 2 Hn D zeros (zeroed with the step's other accumulators, 1 / T of d hist)
+        dM, dR = take(Hn, D), take(Hn, D)
+        out = self._forward(f, True, None, zero_and_mark)
+        dlogit = self._buf("dlogit", R)
+        call("clsr_softmax_loss", out["logit"], out["labels_t"], Hn * T, G, 1.0 / (Hn * T * self.dp_world),
+             self.losses[0:], dlogit)
+        dmo = self._mlp_bwd("lg", LG, dlogit, out["model_output"], W, W, W, (self.L0, self.L1), R)
+        dxl, dtarget = self._buf("nx.dxl", Hn, T, D), self._buf("nx.dtarget", R, D)
+        call("clsr_group_sum_cols", dmo, W, 0, G, Hn * T, D, dxl, D, 0, 0)
+        call("clsr_copy_cols", dmo, W, D, 1, R, D, dtarget, D, 0, 0)
+        shape = (Hn, T, D, self.nx_k, self.nx_nb)
+        parts = query("clsr_nextitnet_parts", *shape)
+        ws = self._buf("nx.ws", query("clsr_nextitnet_workspace_floats", *shape))
+        dhist = self._buf("nx.dhist", Hn, T, D)
+        # d hist (padded steps included: their rows reach table row 0) and a row of dense-gradient sums per workgroup
+        call("clsr_nextitnet_bwd", dxl, out["saved"], Hn, T, D, self.nx_W, self.nx_k, self.nx_nb, self.nx_dil, dhist, ws)
+        self._rp(ws, parts, self.nx_P, self.nx_P, self.nx_dW)
+        self._dw_flush()
+        self._join()
+        # ---- embedding gradients
+        ss = self.sumsq_tab
+        if self.det_grads:
+            # the target rows ride in the sorted lists of the history lookups: every gradient row summed in a fixed order
+            self._hist_grad_sorted(dhist, dM, dR, Hn, T, f["seq_len"], hs, ss, dtarget=dtarget)
+        else:
+            self._hist_grad_sorted(dhist, dM, dR, Hn, T, f["seq_len"], hs, ss)
+            call("clsr_scatter_add_rows", dtarget, D, 0, f["nx_items_t"], 1, R, Di, self.tab_grad["item"], ss[2:])
+            call("clsr_scatter_add_rows", dtarget, D, Di, f["nx_cates_t"], 1, R, Dc, self.tab_grad["cate"], ss[3:])
+        out = dict(out, dlogit=dlogit, dhist=dhist, dxl=dxl)
         if apply:
             self._apply_updates()
         return out

@@ -22,7 +22,7 @@ import numpy as np
 
 from clsr_amd.deeprec_utils import load_dict
 
-__all__ = ["BaseIterator", "SequentialIterator", "SASequentialIterator"]
+__all__ = ["BaseIterator", "SequentialIterator", "SASequentialIterator", "NextItNetIterator"]
 
 _FIELDS = (
     "labels users items cates item_history item_cate_history mask time time_diff "
@@ -700,3 +700,78 @@ class SASequentialIterator(SequentialIterator):
         else:
             feed[self.attn_labels] = data_dict["attn_labels"]
         return feed
+
+
+class NextItNetIterator(SequentialIterator):
+    """Feeds of the NextItNet model (ref ``io/nextitnet_iterator.py``): histories are LEFT-padded (the most recent action
+    sits at step ``T - 1``), and a training instance carries a target per position -- ``items`` / ``cates`` / ``labels`` are
+    ``[n * (1 + ngs), T]``: row 0 of a group is the history shifted by one step with the target appended, the other rows
+    are negatives drawn per position from the batch's targets (``random.randint`` over the instances, a draw equal to the
+    positive of that position is rejected).  Evaluation feeds are those of ``SequentialIterator`` with left padding.
+
+    The literal conversion path: per-line tuples, no column store, no native sampler (the draws are ``random.randint``
+    calls in the reference's order, so ``random.seed`` reproduces its stream)."""
+
+    lazy_histories = False
+
+    def _load_columns(self, infile):
+        lines = self.parse_file(infile)
+        self.iter_data[infile] = lines
+        cols = dict(n=len(lines), lines=lines, full_len=np.fromiter((len(l[4]) for l in lines), np.int64, len(lines)))
+        self._columns[infile] = cols
+        return cols
+
+    def _convert_rows(self, cols, sel, batch_num_ngs):
+        return self._convert_chunk([cols["lines"][int(i)] for i in sel], batch_num_ngs)
+
+    def _left_pad(self, seqs, dtype, repeat):
+        T = self.max_seq_length
+        out = np.zeros((len(seqs), T), dtype=dtype)
+        for i, s in enumerate(seqs):
+            n = min(len(s), T)
+            if n:       # (a slice [-0:] would take the whole row)
+                out[i, T - n:] = np.asarray(s[len(s) - n:], dtype=dtype)
+        return np.repeat(out, repeat, axis=0) if repeat > 1 else out
+
+    def _convert_data(self, label_list, user_list, item_list, item_cate_list, item_history_batch,
+                      item_cate_history_batch, time_list, time_diff_list,
+                      time_from_first_action_list, time_to_now_list, batch_num_ngs):
+        n, T = len(label_list), self.max_seq_length
+        if batch_num_ngs and n < 5:
+            return None
+        G = batch_num_ngs + 1 if batch_num_ngs else 1
+        res = {}
+        res["item_history"] = self._left_pad(item_history_batch, np.int32, G)
+        res["item_cate_history"] = self._left_pad(item_cate_history_batch, np.int32, G)
+        res["mask"] = self._left_pad([[1.0] * len(h) for h in item_history_batch], np.float32, G)
+        res["time_diff"] = self._left_pad(time_diff_list, np.float32, G)
+        res["time_from_first_action"] = self._left_pad(time_from_first_action_list, np.float32, G)
+        res["time_to_now"] = self._left_pad(time_to_now_list, np.float32, G)
+        if not batch_num_ngs:
+            res["labels"] = np.asarray(label_list, dtype=np.float32).reshape(-1, 1)
+            res["users"] = np.asarray(user_list, dtype=np.float32)
+            res["items"] = np.asarray(item_list, dtype=np.int32).reshape(-1, 1)
+            res["cates"] = np.asarray(item_cate_list, dtype=np.int32).reshape(-1, 1)
+            res["time"] = np.asarray(time_list, dtype=np.float32)
+            return res
+        items = np.zeros((n * G, T), dtype=np.int32)
+        cates = np.zeros((n * G, T), dtype=np.int32)
+        labels = np.zeros((n * G, T), dtype=np.float32)
+        randint = random.randint
+        for i in range(n):
+            r0 = i * G
+            # the positive row: the history one step on, the instance's target last
+            items[r0, :T - 1], items[r0, T - 1] = res["item_history"][r0, 1:], item_list[i]
+            cates[r0, :T - 1], cates[r0, T - 1] = res["item_cate_history"][r0, 1:], item_cate_list[i]
+            labels[r0] = 1.0
+            pos = items[r0].tolist()
+            for g in range(1, G):
+                for t in range(T):
+                    j = randint(0, n - 1)
+                    while item_list[j] == pos[t]:
+                        j = randint(0, n - 1)
+                    items[r0 + g, t], cates[r0 + g, t] = item_list[j], item_cate_list[j]
+        res["labels"], res["items"], res["cates"] = labels, items, cates
+        res["users"] = np.repeat(np.asarray(user_list, dtype=np.int32), G)
+        res["time"] = np.repeat(np.asarray(time_list, dtype=np.float32), G)
+        return res

@@ -818,6 +818,40 @@ int clsr_ncf_train(const int* users, int user_div, const int* items, const float
                    float* dlogit, float* d_user_gmf, float* d_user_mlp, float* d_item_gmf, float* d_item_mlp,
                    int* user_ids, float* workspace, double* loss_out, double* sumsq4, void* stream);
 
+/* NextItNet (models/sequential/nextitnet.py, csrc/nextitnet.hip): nblocks residual blocks over hist [Hn, T, C] (contiguous,
+ * C = Di + Dc a multiple of 8, half = C / 2), block l with rate dilations[l] (int32 on the DEVICE, any positive value) and
+ * width k:  x' = x + conv1x1(relu(LN3(dilated_conv(relu(LN2(conv1x1(relu(LN1(x))))))))), LN over channels with biased
+ * variance and eps 1e-8 inside the root, causal taps t - (k - 1 - j) d (before the history: zero).  No mask.
+ * params: per block  beta1 [C] | gamma1 [C] | W1 [C][half] | b1 [half] | beta2 | gamma2 [half] | Wd [k][half][half] |
+ * bd [half] | beta3 | gamma3 [half] | W2 [half][C] | b2 [C], blocks consecutive (clsr_nextitnet_param_floats, no padding).
+ * clsr_nextitnet_supported: T <= 256, C a multiple of 8 up to clsr_nextitnet_max_channels() (128), k in 1 ..
+ * clsr_nextitnet_max_kernel() (8), 1 .. clsr_nextitnet_max_blocks() (16) blocks, and the backward's one-history slice
+ * clsr_nextitnet_lds_bytes(T, C, 1) = 4 (T (2 (C + 1) + 3 (half + 1)) + 8 C) within clsr_nextitnet_lds_budget_bytes()
+ * (64 KB: neither kernel opts into more).  An unsupported shape: an error from the entry points.
+ * clsr_nextitnet_fwd: ONE launch for all blocks; a history's activations stay in LDS.  saved (training; NULL: scoring)
+ * [nblocks][Hn][T][C] receives every block's input, the only training state.  out receives x_L: row (h T + t) rep + g
+ * (last_only = 0) or h rep + g (last_only = 1: position T - 1 only), g < rep, rows ldo floats apart, columns 0 .. C.
+ * clsr_nextitnet_bwd: ONE launch.  dout [Hn, T, C] = d x_L; dhist [Hn, T, C] is WRITTEN (padded steps included); partial
+ * [clsr_nextitnet_parts][param floats] receives one row of gradient sums per workgroup in the layout of params -- the
+ * caller reduces the rows in ascending order (clsr_reduce_parts_multi).  No atomics: two runs are bit-identical.
+ * clsr_nextitnet_rows: items / cates / labels of the training feed [Hn G, T] in the (h, t, g) row order of model_output. */
+int clsr_nextitnet_supported(int T, int C, int k, int nblocks, int max_dilation);
+int clsr_nextitnet_max_channels(void);
+int clsr_nextitnet_max_kernel(void);
+int clsr_nextitnet_max_blocks(void);
+long clsr_nextitnet_lds_budget_bytes(void);
+long clsr_nextitnet_lds_bytes(int T, int C, int training);
+long clsr_nextitnet_param_floats(int C, int k, int nblocks);
+int clsr_nextitnet_slice(int T, int C, int training);
+int clsr_nextitnet_parts(long Hn, int T, int C, int k, int nblocks);
+long clsr_nextitnet_workspace_floats(long Hn, int T, int C, int k, int nblocks);
+int clsr_nextitnet_rows(const int* items, const int* cates, const float* labels, long Hn, int T, int G, int* items_t,
+                        int* cates_t, float* labels_t, void* stream);
+int clsr_nextitnet_fwd(const float* hist, long Hn, int T, int C, const float* params, int k, int nblocks,
+                       const int* dilations, float* saved, float* out, int ldo, int rep, int last_only, void* stream);
+int clsr_nextitnet_bwd(const float* dout, const float* saved, long Hn, int T, int C, const float* params, int k,
+                       int nblocks, const int* dilations, float* dhist, float* partial, void* stream);
+
 /* ---- dropout of _fcn_net's hidden layers (csrc/dropout.hip, csrc/philox.h): base_model.py _active_layer, user_dropout --
  * a = relu(dropout(bn(z))), keep = 1 - dropout[layer].  The mask is a function of (seed, draw, layer, GLOBAL row, column):
  * Philox4x32-10 with counter (row0 + r, c / 4, layer, draw) and key (seed low, seed high); its four words serve columns
