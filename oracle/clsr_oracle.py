@@ -474,7 +474,7 @@ def forward(params, bn_state, feed, hp, training, new_bn=None, sites=None):
         logit=logit, pred=torch.sigmoid(logit), alpha=alpha, hist_input=hist_input, target=target,
         u_long=u_long, u_short=u_short, att_fea_long=att_fea_long, att_fea_short=att_fea_short,
         hist_mean=hist_mean, hist_recent=hist_recent, short_intention=short_int, rnn_out=rnn_out,
-        w_long=w_long, w_short=w_short, seq_len=seq_len, user_embed=user_embed,
+        w_long=w_long, w_short=w_short, seq_len=seq_len, user_embed=user_embed, model_output=model_output,
         involved=dict(item=inv_item_emb, cate=inv_cate_emb, user_long=inv_ul, user_short=inv_us),
     ))
     return out
@@ -548,11 +548,22 @@ def _clip_factor(sumsq, clip_norm):
     return clip_norm / max(norm, clip_norm)
 
 
-def gradients(params, bn_state, feed, hp):
+def site_sumsq(sname, grad, dedup_group=None):
+    """Squared norm of one lookup site's IndexedSlices values.  ``dedup_group`` (G = 1 + train_num_ngs): the norm the HIP
+    step takes with de-duplicated histories (deliberate differences) -- the history sites and the per-row user
+    lookups hold the same ids in the G rows of a group, and the step sums a group's G slices BEFORE the norm; the target and
+    involved-row sites are unchanged."""
+    gr = grad.double()
+    if dedup_group and sname.split("/")[-1] in ("history", "row"):
+        gr = gr.reshape((-1, int(dedup_group)) + tuple(gr.shape[1:])).sum(1)
+    return float((gr ** 2).sum())
+
+
+def gradients(params, bn_state, feed, hp, dedup_group=None):
     """Loss + per-variable gradients with the reference's clipping semantics
     (base_model.py:281-297).  Embedding tables: the gradient is an IndexedSlices whose
     values are the concatenation of every lookup site's slice; ``clip_by_norm`` uses the
-    norm of those un-deduplicated values.  Returns (loss dict, dense grads dict,
+    norm of those un-deduplicated values (``dedup_group``: see :func:`site_sumsq`).  Returns (loss dict, dense grads dict,
     clip-norm dict, new_bn, forward outputs)."""
     leaf = OrderedDict((k, v.detach().clone().requires_grad_(not k.endswith("/user_embedding")))
                        for k, v in params.items())
@@ -571,7 +582,7 @@ def gradients(params, bn_state, feed, hp):
             sumsq = 0.0
             for sname, (g, idx) in sites.items():
                 if sname.startswith(key + "/") and g.grad is not None:
-                    sumsq += float((g.grad.double() ** 2).sum())
+                    sumsq += site_sumsq(sname, g.grad, dedup_group)
             norms[name] = math.sqrt(sumsq)
             gr = p.grad if p.grad is not None else torch.zeros_like(p)
         else:
@@ -640,7 +651,11 @@ def init_adam(params):
 def adam_apply(params, grads, adam, step, lr, beta1=0.9, beta2=0.999, eps=1e-8, lazy_rows=None):
     """tf.train.AdamOptimizer: lr_t = lr*sqrt(1-b2^t)/(1-b1^t); var -= lr_t*m/(sqrt(v)+eps).
     For IndexedSlices the TF op decays m, v over the WHOLE table and updates every row, which
-    equals this dense update with zero gradient on untouched rows (base_model.py:263-264)."""
+    equals this dense update with zero gradient on untouched rows (base_model.py:263-264).
+
+    ``lazy_rows`` (LazyAdamOptimizer, base_model.py:265-266): table name -> ids of the rows the step involves.  A table
+    named there is updated in those rows only: every other row keeps its value AND its moments, bit for bit (dense
+    Adam keeps decaying m, v there and keeps moving the row).  Variables not named are updated as above."""
     lr_t = lr * math.sqrt(1 - beta2 ** step) / (1 - beta1 ** step)
     new_p, new_a = OrderedDict(), OrderedDict()
     for k, v in params.items():
@@ -651,15 +666,41 @@ def adam_apply(params, grads, adam, step, lr, beta1=0.9, beta2=0.999, eps=1e-8, 
         g = grads[k]
         m2 = beta1 * m + (1 - beta1) * g
         s2 = beta2 * s + (1 - beta2) * g * g
+        p2 = v - lr_t * m2 / (torch.sqrt(s2) + eps)
+        if lazy_rows is not None and k in lazy_rows:
+            on = torch.zeros(v.shape[0], dtype=torch.bool)
+            on[torch.as_tensor(lazy_rows[k], dtype=torch.long).reshape(-1)] = True
+            on = on.reshape((-1,) + (1,) * (v.dim() - 1))
+            m2, s2, p2 = torch.where(on, m2, m), torch.where(on, s2, s), torch.where(on, p2, v)
         new_a[k] = (m2, s2)
-        new_p[k] = v - lr_t * m2 / (torch.sqrt(s2) + eps)
+        new_p[k] = p2
     return new_p, new_a
 
 
-def train_step(params, bn_state, adam, step, feed, hp):
-    """One ``CLSRModel.train`` call: forward, backward, per-tensor clip, Adam, BN moving stats."""
-    ls, grads, norms, new_bn, out = gradients(params, bn_state, feed, hp)
-    new_params, new_adam = adam_apply(params, grads, adam, step, hp.learning_rate)
+def touched_rows(feed, tables=None):
+    """Rows a step involves per table NAME (the reference's IndexedSlices rows: the ids of every lookup site) -- what
+    ``adam_apply(lazy_rows=...)`` takes.  ``tables``: table key -> name, TABLES by default; keys item / cate / user*."""
+    tables = TABLES if tables is None else tables
+    ids = lambda *keys: _unique(torch.cat([torch.as_tensor(np.asarray(feed[k])).reshape(-1).long() for k in keys]))
+    rows = {}
+    for key, name in tables.items():
+        if key == "item":
+            rows[name] = ids("item_history", "items")
+        elif key == "cate":
+            rows[name] = ids("item_cate_history", "cates")
+        elif key.startswith("user"):
+            rows[name] = ids("users")
+        else:
+            raise KeyError(key)
+    return rows
+
+
+def train_step(params, bn_state, adam, step, feed, hp, lazy=False, dedup_group=None):
+    """One ``CLSRModel.train`` call: forward, backward, per-tensor clip, Adam (``lazy``: LazyAdam on the tables, the
+    involved rows derived from the feed's lookup sites), BN moving stats."""
+    ls, grads, norms, new_bn, out = gradients(params, bn_state, feed, hp, dedup_group)
+    new_params, new_adam = adam_apply(params, grads, adam, step, hp.learning_rate,
+                                      lazy_rows=touched_rows(feed) if lazy else None)
     bn2 = OrderedDict(bn_state)
     bn2.update(new_bn)
     return new_params, bn2, new_adam, ls, grads, norms, out

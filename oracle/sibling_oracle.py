@@ -227,7 +227,7 @@ def losses(params, out, feed, hp):
     return dict(loss=data_loss + reg, data_loss=data_loss, regular_loss=reg)
 
 
-def gradients(params, bn_state, feed, hp, kind):
+def gradients(params, bn_state, feed, hp, kind, dedup_group=None):
     leaf = OrderedDict((k, v.detach().clone().requires_grad_(not k.endswith("/user_embedding")))
                        for k, v in params.items())
     new_bn, sites = OrderedDict(), {}
@@ -241,7 +241,7 @@ def gradients(params, bn_state, feed, hp, kind):
             continue
         if name in tables:
             key = [k for k, v in TABLES.items() if v == name][0]
-            sumsq = sum(float((g.grad.double() ** 2).sum()) for sname, (g, _) in sites.items()
+            sumsq = sum(C.site_sumsq(sname, g.grad, dedup_group) for sname, (g, _) in sites.items()
                         if sname.startswith(key + "/") and g.grad is not None)
             norms[name] = math.sqrt(sumsq)
             gr = p.grad if p.grad is not None else torch.zeros_like(p)
@@ -256,9 +256,15 @@ def gradients(params, bn_state, feed, hp, kind):
     return {k: v.detach() for k, v in ls.items()}, grads, norms, new_bn, out
 
 
-def train_step(params, bn_state, adam, step, feed, hp, kind):
-    ls, grads, norms, new_bn, out = gradients(params, bn_state, feed, hp, kind)
-    new_params, new_adam = adam_apply(params, grads, adam, step, hp.learning_rate)
+touched_rows = lambda feed: C.touched_rows(feed, TABLES)
+
+
+def train_step(params, bn_state, adam, step, feed, hp, kind, lazy=False, dedup_group=None):
+    """``lazy``: LazyAdam on the two tables (rows outside the feed's lookup sites keep values and moments);
+    ``dedup_group``: the clip norms of the step with de-duplicated histories (clsr_oracle.site_sumsq)."""
+    ls, grads, norms, new_bn, out = gradients(params, bn_state, feed, hp, kind, dedup_group)
+    new_params, new_adam = adam_apply(params, grads, adam, step, hp.learning_rate,
+                                      lazy_rows=touched_rows(feed) if lazy else None)
     bn2 = OrderedDict(bn_state)
     bn2.update(new_bn)
     return new_params, bn2, new_adam, ls, grads, norms, out

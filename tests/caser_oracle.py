@@ -196,7 +196,7 @@ def abs_terms(X, params, hp, key):
 losses = S.losses
 
 
-def gradients(params, bn_state, feed, hp, select=None):
+def gradients(params, bn_state, feed, hp, select=None, dedup_group=None):
     leaf = OrderedDict((k, v.detach().clone().requires_grad_(not k.endswith("/user_embedding")))
                        for k, v in params.items())
     new_bn, sites = OrderedDict(), {}
@@ -210,7 +210,7 @@ def gradients(params, bn_state, feed, hp, select=None):
             continue
         if name in tables:
             key = [k for k, v in TABLES.items() if v == name][0]
-            sumsq = sum(float((g.grad.double() ** 2).sum()) for sname, (g, _) in sites.items()
+            sumsq = sum(C.site_sumsq(sname, g.grad, dedup_group) for sname, (g, _) in sites.items()
                         if sname.startswith(key + "/") and g.grad is not None)
             norms[name] = math.sqrt(sumsq)
             gr = p.grad if p.grad is not None else torch.zeros_like(p)
@@ -225,9 +225,12 @@ def gradients(params, bn_state, feed, hp, select=None):
     return {k: v.detach() for k, v in ls.items()}, grads, norms, new_bn, out
 
 
-def train_step(params, bn_state, adam, step, feed, hp, select=None):
-    ls, grads, norms, new_bn, out = gradients(params, bn_state, feed, hp, select)
-    new_params, new_adam = C.adam_apply(params, grads, adam, step, hp.learning_rate)
+def train_step(params, bn_state, adam, step, feed, hp, select=None, lazy=False, dedup_group=None):
+    """``lazy``: LazyAdam on the two tables (rows outside the feed's lookup sites keep values and moments);
+    ``dedup_group``: the clip norms of the step with de-duplicated histories (clsr_oracle.site_sumsq)."""
+    ls, grads, norms, new_bn, out = gradients(params, bn_state, feed, hp, select, dedup_group)
+    new_params, new_adam = C.adam_apply(params, grads, adam, step, hp.learning_rate,
+                                        lazy_rows=S.touched_rows(feed) if lazy else None)
     bn2 = OrderedDict(bn_state)
     bn2.update(new_bn)
     return new_params, bn2, new_adam, ls, grads, norms, out

@@ -199,14 +199,10 @@ def gradients(params, feed, hp):
 
 def train_step(params, adam, step, feed, hp, lazy=False):
     """One ``train`` call: forward, backward, per-variable clip, Adam (``lazy``: LazyAdam -- a table's untouched rows keep
-    their values and moments)."""
+    their values and moments,
+    by the shared ``adam_apply(lazy_rows=...)``)."""
     ls, grads, norms, out = gradients(params, feed, hp)
-    new_p, new_a = C.adam_apply(params, grads, adam, step, hp.learning_rate)
-    if lazy:
-        for name, rows in out["touched"].items():
-            keep = torch.ones(params[name].shape[0], dtype=torch.bool)
-            keep[rows] = False
-            new_p[name] = torch.where(keep.unsqueeze(1), params[name], new_p[name])
+    new_p, new_a = C.adam_apply(params, grads, adam, step, hp.learning_rate, lazy_rows=out["touched"] if lazy else None)
     return new_p, new_a, ls, grads, norms, out
 
 

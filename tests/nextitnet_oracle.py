@@ -434,13 +434,7 @@ def gradients(params, bn_state, feed, hp):
 def lazy_adam_apply(params, grads, adam, step, lr, touched, beta1=0.9, beta2=0.999, eps=1e-8):
     """LazyAdam: as ``adam_apply``, but a table's moments and rows move only where the step touched a row (``touched``:
     table name -> row ids); dense variables as Adam."""
-    new_p, new_a = C.adam_apply(params, grads, adam, step, lr, beta1, beta2, eps)
-    for name, rows in touched.items():
-        keep = torch.ones(params[name].shape[0], dtype=torch.bool)
-        keep[rows] = False
-        new_p[name] = torch.where(keep.unsqueeze(1), params[name], new_p[name])
-        new_a[name] = tuple(torch.where(keep.unsqueeze(1), old, new) for old, new in zip(adam[name], new_a[name]))
-    return new_p, new_a
+    return C.adam_apply(params, grads, adam, step, lr, beta1, beta2, eps, lazy_rows=touched)
 
 
 def train_step(params, bn_state, adam, step, feed, hp, lazy=False):

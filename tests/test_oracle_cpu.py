@@ -7,6 +7,7 @@ facts of the reference graph (variable set and sizes from SURVEY.md 8a, loss com
 import math
 
 import numpy as np
+import pytest
 import torch
 
 from oracle import clsr_oracle as O
@@ -192,3 +193,66 @@ def test_hoisted_rnn_projections_equal_the_literal_per_step_form(golden_hparams,
     assert abs(float(ls0["loss"]) - float(ls1["loss"])) < 1e-12
     for k in g0:
         assert float((g0[k] - g1[k]).abs().max()) < 1e-11, k
+
+
+def _two_steps(orc, params, hp, feeds, lazy, *extra):
+    p, bn, adam = params, orc.init_bn_state(params), orc.init_adam(params)
+    states = []
+    for step, feed in enumerate(feeds, 1):
+        p, bn, adam = orc.train_step(p, bn, adam, step, orc.to_torch_feed(feed, dtype=torch.float64), hp, *extra, lazy=lazy)[:3]
+        states.append((p, adam))
+    return states
+
+
+@pytest.mark.parametrize("model", ["clsr", "gru4rec"])
+def test_lazy_adam_freezes_rows_the_step_does_not_involve(golden_hparams, model):
+    """Dense Adam and LazyAdam are the same arithmetic on a first step; they part on the SECOND, at rows touched earlier and
+    not now: dense Adam keeps decaying m, v and keeps moving the row, LazyAdam leaves all three as they were.  Rows touched
+    in both steps see the same update, rows never touched stay put under both."""
+    import copy
+
+    from clsr_amd.synthetic import synthetic_feed
+    from oracle import sibling_oracle as S
+
+    dims = dict(Vu=50, Vi=200, Vc=12)
+    hp = copy.deepcopy(golden_hparams)
+    if model == "clsr":
+        orc, extra, tables = O, (), O.TABLES
+        params = O.init_params(dims, hp, seed=2, dtype=torch.float64, scale_dense=8.0)
+    else:
+        hp.model_type, hp.user_embedding_dim, hp.attention_size = "GRU4Rec", 16, 40
+        orc, extra, tables = S, (model,), S.TABLES
+        params = S.init_params(dims, hp, model, seed=2, dtype=torch.float64, scale_dense=8.0)
+    feeds = [synthetic_feed(4, 10, dims["Vu"], dims["Vi"], dims["Vc"], G=hp.train_num_ngs + 1, lengths="uniform",
+                            ids="uniform", seed=s) for s in (11, 12)]
+    feeds[1]["users"][:hp.train_num_ngs + 1] = feeds[0]["users"][0]      # one user is seen in both steps
+    lazy, dense = (_two_steps(orc, params, hp, feeds, flag, *extra) for flag in (True, False))
+    rows = [O.touched_rows(f, tables) for f in feeds]
+    # step 1: zero moments -- the two optimisers agree everywhere, bit for bit
+    for name in tables.values():
+        assert torch.equal(lazy[0][0][name], dense[0][0][name])
+    for key, name in tables.items():
+        V = params[name].shape[0]
+        first, second = (torch.zeros(V, dtype=torch.bool) for _ in range(2))
+        first[rows[0][name]], second[rows[1][name]] = True, True
+        both, only_first, never = first & second, first & ~second, ~first & ~second
+        assert both.any() and only_first.any() and (never.any() or key == "cate")
+        (pl, al), (pd, ad) = lazy[1], dense[1]
+        # touched in both steps: the same update, the same moments
+        assert torch.equal(pl[name][both], pd[name][both])
+        assert torch.equal(al[name][0][both], ad[name][0][both]) and torch.equal(al[name][1][both], ad[name][1][both])
+        # touched in the first step only: LazyAdam leaves the row and its moments bit-identical, dense Adam moves all three
+        p1, a1 = lazy[0]
+        assert torch.equal(pl[name][only_first], p1[name][only_first])
+        assert torch.equal(al[name][0][only_first], a1[name][0][only_first])
+        assert torch.equal(al[name][1][only_first], a1[name][1][only_first])
+        moved = (pd[name][only_first] - p1[name][only_first]).abs().reshape(int(only_first.sum()), -1).max(1)[0]
+        assert float(moved.min()) > 0.02 * hp.learning_rate, (key, float(moved.min()))
+        assert not torch.equal(ad[name][0][only_first], a1[name][0][only_first])
+        assert torch.allclose(ad[name][0][only_first], 0.9 * a1[name][0][only_first], rtol=1e-12, atol=0)
+        assert torch.allclose(ad[name][1][only_first], 0.999 * a1[name][1][only_first], rtol=1e-12, atol=0)
+        # never touched: the loaded values under both
+        assert torch.equal(pl[name][never], params[name][never]) and torch.equal(pd[name][never], params[name][never])
+    # ``lazy_rows=None`` is the dense update exactly, and dense variables are never frozen
+    dense_name = [n for n in params if n not in set(tables.values()) and not n.endswith("/user_embedding")][0]
+    assert torch.equal(lazy[1][0][dense_name], dense[1][0][dense_name])
