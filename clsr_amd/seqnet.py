@@ -607,8 +607,10 @@ class SeqNet(CLSRNet):
             self._dw(hprev2, H, dPin2[:, 2 * H:], 3 * H, B * T, H, H, Gd[g2 + "candidate/kernel"][H:], H, Xmul=gates2,
                      ldmul=3 * H)
             if G > 1:       # the rows of a group share the inputs: sum their d(input projections)
+                # (as 3 T steps of H columns -- the same memory, the same sums over the group's rows: the kernel takes at
+                # most 256 columns, and 3 H passes that from hidden_size 88 on)
                 dPin2h = self._buf("a2.dPinH", M, 3 * H)
-                call("clsr_att_z0_bwd_reduce", dPin2, Hn, G, T, 3 * H, dPin2h, self._buf("a2.dV", B, 3 * H))
+                call("clsr_att_z0_bwd_reduce", dPin2, Hn, G, 3 * T, H, dPin2h, self._buf("a2.dV", B, 3 * H))
             else:
                 dPin2h = dPin2
             self._dw(rnn1, H, dPin2h, 3 * H, M, H, 2 * H, Gd[g2 + "gates/kernel"][0:H], 2 * H,

@@ -293,6 +293,10 @@ def draw_case(rng, idx, kind="clsr", pin=None):
         if kind in ("sli_rec", "a2svd"):
             over["attention_size"] = D   # the A2SVD query is contracted with the projected history (base_model.py:622)
     D, Dc, T, P, G = (int(pin.pop(k, v)) for k, v in (("D", D), ("Dc", Dc), ("T", T), ("P", P), ("G", G)))
+    if kind == "sli_rec":                # the sibling overrides above follow a pinned D (an unpinned one: the same values)
+        over["hidden_size"] = D
+    if kind in ("sli_rec", "a2svd"):
+        over["attention_size"] = D
     over["train_num_ngs"] = G - 1
     pin_lengths = pin.pop("lengths", None)
     over.update(pin)
@@ -507,6 +511,96 @@ def long_cases(kinds=None, redrawn=None):
                 if kinds is None or kind in kinds:
                     cases.append(c)
                 idx += 1
+    return cases
+
+
+BOUNDARY_SEED = 4096
+# Draws of boundary_cases() the float32 ORACLE does not hold within LONG_ADMIT of every bar: case number -> the attempt of
+# np.random.default_rng([BOUNDARY_SEED, idx, attempt]) that replaces it (same kind, same pinned shape).  At most one case in
+# twenty (tests/test_boundaries_cpu.py); the HIP step never decides what is in the list.
+BOUNDARY_REDRAWN = {86: 1, 167: 1}       # clsr-golden-G9 (0.594 of the worst bar), sli_rec-H48 (0.560)
+BOUNDARY_TINY = dict(T=6, P=3, G=3, lengths="uniform")
+BOUNDARY_ENC = ("time4lstm", "gru", "lstm")
+BOUNDARY_D_EVERY_ENC = (8, 12, 44, 48, 52, 60, 64, 68, 80, 84, 88, 124, 128)       # widths every encoder runs at
+BOUNDARY_A0 = (4, 8, 44, 76, 80, 84, 88, 96, 100, 104, 128, 132, 256)
+BOUNDARY_A1 = (4, 8, 12, 44, 48, 52, 56, 80)
+BOUNDARY_LAYERS = ((4, 4), (100, 60), (100, 64), (100, 68), (260, 64), (1024, 128))
+BOUNDARY_G = (2, 8, 9, 16)
+# per-row query columns of DIN / DIEN (= D: SeqNet splits no query; DIN's keys are D wide as well)
+BOUNDARY_Q = (48, 52, 64, 68, 80, 84, 88, 128, 132, 160, 164)
+BOUNDARY_SIB_H = (4, 8, 44, 48, 52, 64, 68, 80, 84, 100, 124, 128)      # (sli_rec: H = D is its query width as well)
+BOUNDARY_SIB_ATT = (4, 44, 48, 52, 128)
+BOUNDARY_SIB_DU = (4, 44)
+BOUNDARY_SIBLINGS = ("gru4rec", "dien", "din", "a2svd", "sli_rec")
+
+
+def _boundary_specs():
+    """(axis, id, kind, pin) of every boundary case, in the committed order: a new case is APPENDED (its number seeds its
+    stream, so no other case moves).  One axis moves per case; the rest sits well inside every dispatch boundary of
+    clsr_amd/net.py / seqnet.py (widths 24 / 16 / 8: multiples of 8, so that every fused kernel admits them)."""
+    small = dict(att_fcn_layer_sizes=[16, 8], layer_sizes=[16, 8])
+    clsr = dict(BOUNDARY_TINY, D=24, Dc=4, **small)
+    sib = dict(BOUNDARY_TINY, D=24, Dc=4, hidden_size=24, attention_size=24, user_embedding_dim=16, **small)
+    every = dict(interest_evolve=True, predict_long_short=True, manual_alpha=False)     # every encoder and head in the graph
+    golden = dict(clsr, D=40, Dc=8, att_fcn_layer_sizes=[80, 40], layer_sizes=[100, 64], sequential_model="time4lstm", **every)
+    specs = []
+    # ---- D of the CLSR graph (= Du = H): every multiple of 4 in 8 .. 128
+    n = 0
+    for D in range(8, 129, 4):
+        for e in (range(3) if D in BOUNDARY_D_EVERY_ENC else (n % 3,)):
+            Dc = 4 if (n % 2 == 0 or D < 16) else 4 * (D // 8)     # item / category column offsets of the segmented sums vary
+            specs.append(("D", "clsr-D%d-%s" % (D, BOUNDARY_ENC[e]), "clsr", dict(clsr, D=D, Dc=Dc, sequential_model=BOUNDARY_ENC[e])))
+            n += 1
+    for A0 in BOUNDARY_A0:
+        specs.append(("A0", "clsr-A0_%d" % A0, "clsr", dict(clsr, att_fcn_layer_sizes=[A0, 8])))
+    for A1 in BOUNDARY_A1:
+        specs.append(("A1", "clsr-A1_%d" % A1, "clsr", dict(clsr, att_fcn_layer_sizes=[16, A1])))
+    for L in BOUNDARY_LAYERS:
+        specs.append(("L", "clsr-L%dx%d" % L, "clsr", dict(clsr, layer_sizes=list(L))))
+    for G in BOUNDARY_G:      # the golden widths: the fused heads and the fused encoder tail
+        specs.append(("G", "clsr-golden-G%d" % G, "clsr", dict(golden, G=G)))
+    for G in BOUNDARY_G:
+        specs.append(("G", "clsr-D24-G%d" % G, "clsr", dict(clsr, G=G, sequential_model="time4lstm", **every)))
+    # ---- the siblings: per-row query columns, encoder input width, hidden / attention / user widths
+    for kind in ("din", "dien"):
+        for Q in BOUNDARY_Q:
+            specs.append(("Q", "%s-Q%d" % (kind, Q), kind, dict(sib, D=Q, Dc=4 * (Q // 8))))
+    for D in (128, 132, 136):
+        specs.append(("Q", "gru4rec-D%d" % D, "gru4rec", dict(sib, D=D)))
+    for kind in BOUNDARY_SIBLINGS:
+        for H in BOUNDARY_SIB_H:
+            if kind == "sli_rec" and H == 4:
+                continue      # (sli_rec: H = D, and D = 4 leaves no room for an item and a category width of 4 each)
+            specs.append(("H", "%s-H%d" % (kind, H), kind, dict(sib, D=H) if kind == "sli_rec" else dict(sib, hidden_size=H)))
+    for kind in ("din", "dien"):
+        for A in BOUNDARY_SIB_ATT:
+            specs.append(("att", "%s-att%d" % (kind, A), kind, dict(sib, attention_size=A)))
+    for kind in BOUNDARY_SIBLINGS:
+        for Du in BOUNDARY_SIB_DU:
+            specs.append(("Du", "%s-Du%d" % (kind, Du), kind, dict(sib, user_embedding_dim=Du)))
+    return specs
+
+
+def boundary_cases(kinds=None, axes=None, redrawn=None):
+    """The committed dispatch-boundary cases: tiny shapes (T = 6, three positives, three rows each) that put one width at a
+    time on the last admitted and on the first refused value of every shape-dependent branch of the step (DESIGN.md section
+    6 has the table; tests/test_boundaries_cpu.py holds the list to it by the kernels' own ``clsr_*_supported`` queries).
+    Case ``idx`` is draw_case on np.random.default_rng([BOUNDARY_SEED, idx]) with the shape pinned: adding or replacing one
+    case moves no other.  ``c.axis``: the swept argument; ``c.x3``: also run with precision="fp32x3" (the CLSR cases at a
+    boundary of a kernel with a two-piece instance: every CLSR axis but the logit MLP's widths)."""
+    redrawn = BOUNDARY_REDRAWN if redrawn is None else redrawn
+    cases = []
+    for idx, (axis, cid, kind, pin) in enumerate(_boundary_specs()):
+        if (kinds is not None and kind not in kinds) or (axes is not None and axis not in axes):
+            continue
+        attempt = redrawn.get(idx, 0)
+        # (widths the model ties to D -- sli_rec: hidden and attention size, a2svd: attention size -- follow D: draw_case)
+        pin = {k: v for k, v in pin.items() if not ((k == "hidden_size" and kind == "sli_rec")
+                                                    or (k == "attention_size" and kind in ("sli_rec", "a2svd")))}
+        c = draw_case(np.random.default_rng([BOUNDARY_SEED, idx] + ([attempt] if attempt else [])), idx, kind, pin=pin)
+        c.axis, c.id, c.attempt, c.pin = axis, cid, attempt, dict(pin)
+        c.x3 = kind == "clsr" and axis != "L"
+        cases.append(c)
     return cases
 
 
