@@ -675,6 +675,30 @@ class NCFModel(_SiblingModel):
     kind = "ncf"
 
 
+class LGNModel(_SiblingModel):
+    """Reference ``LGNModel`` (models/sequential/lgn.py).  The user-item graph is built from ``train_data`` beside the
+    vocabularies, as the reference builds it (clsr_amd/lgn_graph.py; nothing is written there); checkpoints carry the variables
+    only, the graph is rebuilt from the data.  Data parallelism is refused: the clip norm of a dense table gradient is not a
+    sum of per-rank terms, unlike every slice norm the exchange handles."""
+    kind = "lgn"
+
+    def __init__(self, hparams, iterator_creator, *args, **kw):
+        if kw.get("dist") is not None:
+            raise NotImplementedError("LGNModel(dist=...): data parallelism is not available for LGN (the clip norms of its dense "
+                                      "user / item table gradients need an exchange of their own)")
+        super(LGNModel, self).__init__(hparams, iterator_creator, *args, **kw)
+
+    def _make_net(self, hp, dims):
+        from clsr_amd import lgn_graph
+        from clsr_amd.seqnet import SeqNet
+
+        if self._precision != "fp32" or self._table_dtype != "fp32" or self._table_master:
+            raise NotImplementedError("LGNModel: precision='fp32' and fp32 tables only (precision=%r, table_dtype=%r, "
+                                      "table_master=%r)" % (self._precision, self._table_dtype, self._table_master))
+        return SeqNet(hp, dims, kind=self.kind, device=self._device, seed=self.seed, dedup_histories=self._dedup,
+                      graph=lgn_graph.build_graph(hp))
+
+
 class NextItNetModel(_SiblingModel):
     """Reference ``NextItNetModel`` (models/sequential/nextitnet.py): hparams ``dilations``, ``kernel_size``; built with
     ``NextItNetIterator`` (left-padded histories, a target per position in training feeds)."""

@@ -137,6 +137,8 @@ def init_tensor(kind, shape, hp, gen):
     if kind == "glorot_conv":       # tf glorot_uniform on a conv kernel [width, in, out]: fans scaled by the width
         lim = math.sqrt(6.0 / (shape[0] * (shape[1] + shape[2])))
         return (torch.rand(shape, generator=gen) * 2 - 1) * lim
+    if kind == "normal_0.01":       # tf.random_normal_initializer(stddev=0.01): not truncated (lgn.py:21)
+        return torch.randn(shape, generator=gen) * 0.01
     if kind == "one":
         return torch.ones(shape)
     return torch.zeros(shape)
@@ -147,7 +149,7 @@ def init_tensor(kind, shape, hp, gen):
 # (examples/00_quick_start/sequential.py:94-205): they share the embedding layer and the logit MLP of
 # SequentialBaseModel (sequential_base_model.py:55-74,354-452) and differ in _build_seq_graph.
 SIB_TABLES = OrderedDict([("item", EMB + "item_embedding"), ("cate", EMB + "cate_embedding")])
-SIBLINGS = ("gru4rec", "din", "sli_rec", "a2svd", "dien", "caser", "ncf", "nextitnet")
+SIBLINGS = ("gru4rec", "din", "sli_rec", "a2svd", "dien", "caser", "ncf", "nextitnet", "lgn")
 # NCF (ncf.py:15-42): four tables of its own beside the trunk's, all [V, user_embedding_dim] -- the item tables too.  The
 # trunk's item / cate tables stay trained tables: the involved-row regulariser reaches them, the data gradient does not.
 NCF_TABLES = OrderedDict([("item", EMB + "item_embedding"), ("cate", EMB + "cate_embedding"),
@@ -155,9 +157,14 @@ NCF_TABLES = OrderedDict([("item", EMB + "item_embedding"), ("cate", EMB + "cate
                           ("item_gmf", EMB + "item_gmf_embedding"), ("item_mlp", EMB + "item_mlp_embedding")])
 
 
+# LGN (lgn.py:47-61,113): user_embedding is a trained table here -- the node table is [user_embedding ; item ++ cate[item2cate]]
+LGN_TABLES = OrderedDict([("item", EMB + "item_embedding"), ("cate", EMB + "cate_embedding"), ("user", UNUSED_TABLE)])
+LGN_LAYERS = 2      # n_layers is hard-coded (lgn.py:67)
+
+
 def sibling_tables(kind):
     """Trained embedding tables of a sibling model: key -> variable name."""
-    return NCF_TABLES if kind == "ncf" else SIB_TABLES
+    return NCF_TABLES if kind == "ncf" else LGN_TABLES if kind == "lgn" else SIB_TABLES
 
 
 def sibling_kind(model_type):
@@ -188,6 +195,10 @@ def sibling_scopes(kind):
         # default scope under "sequential": fully_connected, fully_connected_1, ... (the tower), then the output layer.
         # Derived from TF 1.15's scoping rules and, like every other name here, unpinned until the TF 1.15 pin is run.
         return dict(fc="sequential/fully_connected")
+    if kind == "lgn":
+        # lgn.py:19-28: plain tf.Variable(name='W_gc_k') created from _build_embedding after its variable_scope("embedding")
+        # has closed, inside variable_scope("sequential"): sequential/W_gc_0, sequential/b_gc_0, ...  Unpinned like the rest.
+        return dict(gc="sequential/")
     if kind == "nextitnet":    # nextitnet.py:41,127-131: variable_scope("nextitnet") / one scope per residual block
         return dict(nx="sequential/nextitnet/")
     raise ValueError("unknown sibling model %r" % (kind,))
@@ -202,6 +213,14 @@ def ncf_specs(scope, Du, sizes):
         specs += [(fc(i) + "weights", (last, int(n)), "glorot"), (fc(i) + "biases", (int(n),), "zero")]
         last = int(n)
     return specs + [(fc(len(sizes)) + "weights", (Du + last, 1), "glorot")]
+
+
+def lgn_specs(scope, C):
+    """W_gc_k [C, C] and b_gc_k [C] in creation order, both random_normal(stddev 0.01) (lgn.py:19-28)."""
+    specs = []
+    for k in range(LGN_LAYERS):
+        specs += [(scope + "W_gc_%d" % k, (C, C), "normal_0.01"), (scope + "b_gc_%d" % k, (C,), "normal_0.01")]
+    return specs
 
 
 def caser_specs(scope, Dx, hp):
@@ -248,6 +267,8 @@ def sibling_specs(dims, hp, kind):
         specs += [(NCF_TABLES[k], (Vu if k.startswith("user") else Vi, Du), "w")
                   for k in ("user_gmf", "user_mlp", "item_gmf", "item_mlp")]
         return specs + ncf_specs(sc["fc"], Du, list(hp.ncf_layer_sizes))
+    if kind == "lgn":       # no logit MLP: LGN overrides _fcn_net (the logit is the dot product itself)
+        return specs + lgn_specs(sc["gc"], D)
     if kind == "gru4rec":
         specs += gru_specs(sc["gru"], D, H)
         out_dim = H + D

@@ -32,6 +32,11 @@ one launch forward and one backward (csrc/nextitnet.hip).
 A2SVD and GRU4Rec, whose one ``_fcn_net`` is the logit MLP, also train with the config's dropout (``user_dropout``,
 ``dropout``: csrc/dropout.hip, ``CLSRNet._mlp_fwd_drop``); the others refuse it by name
 (Caser for now: its tail is the same one).
+
+  LGNModel       models/sequential/lgn.py:47-132         kind "lgn": no history encoder and no logit MLP either.  All Vu + Vi
+                                                         rows [user_embedding ; item ++ cate[item2cate]] go twice through the
+                                                         normalised user-item adjacency (``graph=``, clsr_amd/lgn_graph.py) and
+                                                         a C x C layer; logit = F[user] . F[Vu + item] (csrc/lgn.hip)
 """
 import copy
 
@@ -50,7 +55,7 @@ class SeqNet(CLSRNet):
     def __init__(self, hp, dims, kind=None, **kw):
         self.kind = sibling_kind(kind if kind is not None else hp.model_type)
         if self.kind is None:
-            raise ValueError("SeqNet builds gru4rec / din / dien / sli_rec / a2svd / caser / ncf / nextitnet, got %r"
+            raise ValueError("SeqNet builds gru4rec / din / dien / sli_rec / a2svd / caser / ncf / nextitnet / lgn, got %r"
                              % (kind or hp.model_type,))
         self.sc = sibling_scopes(self.kind)
         if self.kind == "caser" and hp.hidden_size is None:
@@ -61,6 +66,16 @@ class SeqNet(CLSRNet):
             # it can unpack and no dropout
             hp = copy.copy(hp)
             hp.hidden_size, hp.user_dropout, hp.embedding_dropout = hp.hidden_size or 0, False, 0.0
+            if len(hp.layer_sizes or ()) != 2:
+                hp.layer_sizes = [4, 4]
+            if len(hp.att_fcn_layer_sizes or ()) != 2:
+                hp.att_fcn_layer_sizes = None
+        self._lg_graph = kw.pop("graph", None)
+        if self.kind == "lgn":
+            # settings without effect in LGN's graph (lgn.py never reads them): whatever they hold, the trunk sees values it
+            # can unpack and no dropout in an MLP that does not exist (embedding_dropout stays as it is: refused when set)
+            hp = copy.copy(hp)
+            hp.hidden_size, hp.user_dropout = hp.hidden_size or 0, False
             if len(hp.layer_sizes or ()) != 2:
                 hp.layer_sizes = [4, 4]
             if len(hp.att_fcn_layer_sizes or ()) != 2:
@@ -77,6 +92,8 @@ class SeqNet(CLSRNet):
             self._nextitnet_setup()
         if self.kind == "ncf":
             self._ncf_setup()
+        if self.kind == "lgn":
+            self._lgn_setup()
         if self.kind == "sli_rec":
             self.enc_in = self.Di          # Time4LSTM reads the item embedding only (sli_rec.py:43-57)
         self.split_query = False
@@ -88,6 +105,11 @@ class SeqNet(CLSRNet):
             bad = self._ncf_limits(hp)
             if bad:
                 raise NotImplementedError("ncf HIP path does not support: " + "; ".join(bad))
+            return
+        if self.kind == "lgn":
+            bad = self._lgn_limits(hp)
+            if bad:
+                raise NotImplementedError("lgn HIP path does not support: " + "; ".join(bad))
             return
         if hp.enable_BN is not True:
             bad.append("enable_BN must be True")
@@ -238,6 +260,71 @@ class SeqNet(CLSRNet):
                        % (Du, sizes, query("clsr_ncf_lds_floats", Du, nl, *w4), query("clsr_ncf_lds_budget_floats")))
         return bad
 
+    def _lgn_limits(self, hp):
+        """What LGN's graph reads, by key name.  layer_sizes, activation, enable_BN, user_dropout / dropout, hidden_size,
+        attention_size and the other models' keys are never read by the reference's LGN: any value passes."""
+        from clsr_amd.net import resolve_optimizer
+
+        bad = []
+        if any(float(getattr(hp, k)) != 0.0 for k in ("embed_l1", "layer_l1", "cross_l1", "cross_l2")):
+            bad.append("l1 / cross regularisers must be 0")
+        if hp.loss != "softmax" or hp.method != "classification":
+            bad.append("loss must be softmax / method classification")
+        if float(hp.embedding_dropout or 0.0) != 0.0:
+            bad.append("embedding_dropout must be 0 (no model of this project has embedding dropout), got %r" % (hp.embedding_dropout,))
+        Di, Dc, Du = int(hp.item_embedding_dim), int(hp.cate_embedding_dim), int(hp.user_embedding_dim)
+        cmax = query("clsr_lgn_max_width")
+        if Di <= 0 or Dc <= 0 or Di % 4 or Dc % 4 or Di + Dc > cmax:
+            bad.append("item_embedding_dim and cate_embedding_dim must be positive multiples of 4, at most %d together, got %d + %d"
+                       % (cmax, Di, Dc))
+        if Du != Di + Dc:
+            bad.append("user_embedding_dim must equal item_embedding_dim + cate_embedding_dim (the tables are concatenated "
+                       "along rows into one node table), got %d against %d + %d" % (Du, Di, Dc))
+        if self.precision != "fp32":
+            bad.append("precision must be 'fp32', got %r (LGN's kernels are fp32 FMA chains)" % (self.precision,))
+        if resolve_optimizer(hp.optimizer) not in ("adam", "lazyadam"):
+            bad.append("optimizer must be adam or lazyadam, got %r" % (hp.optimizer,))
+        if int(hp.max_seq_length) > 256:
+            bad.append("max_seq_length must be at most 256")
+        return bad
+
+    def _lgn_setup(self):
+        """The device image of the graph (clsr_amd/lgn.py: Propagation), item2cate and its sorted form for the category
+        gradient's segment sums, the id lists that mark every row of the two dense-gradient tables, and the parameter
+        block: W_gc_k | b_gc_k consecutive in the dense gradient buffer, the layout of a partial row of csrc/lgn.hip."""
+        from clsr_amd import lgn
+
+        g, dev = self._lg_graph, self.device
+        if g is None:
+            raise ValueError("SeqNet kind 'lgn' needs the user-item graph: SeqNet(..., graph=lgn_graph.build_graph(hparams))")
+        Vu, Vi, Vc, C = self.dims["Vu"], self.dims["Vi"], self.dims["Vc"], self.D
+        i2c = np.ascontiguousarray(g.item2cate, dtype=np.int32)
+        if len(g.indptr) - 1 != Vu + Vi or i2c.shape != (Vi,) or (len(i2c) and (i2c.min() < 0 or i2c.max() >= Vc)):
+            raise ValueError("graph: expected %d + %d rows and item2cate [%d] with values below %d" % (Vu, Vi, Vi, Vc))
+        self.lg_prop = lgn.Propagation(g, C, device=dev)        # (refuses rows / entries past int32 by name)
+        i32 = lambda x: torch.as_tensor(np.ascontiguousarray(x, dtype=np.int32), device=dev)
+        self.lg_i2c, self.lg_all_users, self.lg_all_items = i32(i2c), i32(np.arange(Vu)), i32(np.arange(Vi))
+        # item2cate never changes: sorted once; category c owns the items perm[seg[c] .. seg[c + 1])
+        seg = np.zeros(Vc + 1, dtype=np.int64)
+        np.cumsum(np.bincount(i2c, minlength=Vc), out=seg[1:])
+        self.lg_cate = lgn._Csr(seg, np.argsort(i2c, kind="stable"), None, self.Dc, dev)
+        # involved items | involved categories, one buffer (zeroed together): the rows the regulariser reaches -- of F's
+        # item part and of the raw cate_embedding; the table flags say which rows an update visits, which is more
+        self.lg_inv_all = torch.zeros(_pad4(Vi) + _pad4(Vc), dtype=torch.uint8, device=dev)
+        self.lg_inv, self.lg_inv_c = self.lg_inv_all[:_pad4(Vi)], self.lg_inv_all[_pad4(Vi):]
+        self.lg_stats = torch.zeros(query("clsr_lgn_stats_workspace_doubles"), dtype=torch.float64, device=dev)
+        sc, pf = self.sc["gc"], self.lg_prop.part_floats
+        self.lg_W = [self.P[sc + "W_gc_%d" % k] for k in range(lgn.N_LAYERS)]
+        self.lg_b = [self.P[sc + "b_gc_%d" % k] for k in range(lgn.N_LAYERS)]
+        self.lg_dWb = []
+        for k in range(lgn.N_LAYERS):
+            gw, gb = self.Gd[sc + "W_gc_%d" % k], self.Gd[sc + "b_gc_%d" % k]
+            if gb.data_ptr() != gw.data_ptr() + 4 * C * C:
+                raise AssertionError("LGN parameter block of layer %d is not contiguous" % k)
+            g0 = (gw.data_ptr() - self.dense_grad.data_ptr()) // 4
+            self.lg_dWb.append(self.dense_grad[g0:g0 + pf])
+        self.lg_F, self.lg_F_valid = None, False
+
     def _ncf_setup(self):
         """NCF's shape constants and the parameter block the kernel addresses by offset: tower weights and biases, then the
         output weights, consecutive in the dense buffer in the layout csrc/ncf.hip states (checked here, once)."""
@@ -279,10 +366,17 @@ class SeqNet(CLSRNet):
         return sibling_tables(self.kind)
 
     def _unused_tables(self):
-        return (UNUSED_TABLE,)
+        return () if self.kind == "lgn" else (UNUSED_TABLE,)      # (LGN trains user_embedding)
 
     def _update_spec(self):
         trunk = (("item", None, 4, 0.0, 0.0, None, 0, 3), ("cate", None, 5, 0.0, 0.0, None, 1, 3))
+        if self.kind == "lgn":
+            # user / item: dense gradients (they enter through concat), ONE norm over the whole summed gradient (slots 6 / 0),
+            # no regulariser on the raw rows (slot None: it acts on F).  cate: the Vi slices of the item2cate lookup (slot 1)
+            # plus the involved-rows slice, which is the usual regulariser term (its norm in slot 5); slot 3 stays zero
+            # (the step applies cate's term itself, to the involved rows only: the table's flags also hold set(item2cate))
+            return (("item", None, None, 0.0, 0.0, None, 0, 1), ("cate", None, None, 0.0, 0.0, None, 1, 3),
+                    ("user", None, None, 0.0, 0.0, None, 6, 1))
         if self.kind != "ncf":
             return trunk
         # NCF: item / cate get the regulariser only (their lookup-site slots 0..3 stay zero); its own four tables have
@@ -294,7 +388,7 @@ class SeqNet(CLSRNet):
         return 0
 
     def _det_merged(self, f):
-        if self.kind == "ncf":      # (no history lookup reaches the loss: nothing to merge)
+        if self.kind in ("ncf", "lgn"):      # (no history lookup reaches the loss: nothing to merge)
             return {}
         if self.kind == "nextitnet":
             # the Hn T G target rows of a training step, ids in (h, t, g) order (clsr_nextitnet_rows; _nextitnet_forward
@@ -376,6 +470,10 @@ class SeqNet(CLSRNet):
             if training:
                 raise ValueError("NCF's training forward is part of its step (clsr_ncf_train): use train_step")
             return self._ncf_score(f)
+        if self.kind == "lgn":
+            if training:
+                raise ValueError("LGN's training forward is part of its step: use train_step")
+            return self._lgn_score(f)
         if self.kind == "nextitnet":
             return self._nextitnet_forward(f, training, early_aux)
         hp, P, kind, sc = self.hp, self.P, self.kind, self.sc
@@ -532,6 +630,8 @@ class SeqNet(CLSRNet):
     def _train_step(self, f, apply):
         if self.kind == "ncf":
             return self._ncf_train_step(f, apply)
+        if self.kind == "lgn":
+            return self._lgn_train_step(f, apply)
         if self.kind == "nextitnet":
             return self._nextitnet_train_step(f, apply)
         hp, P, Gd, kind, sc = self.hp, self.P, self.Gd, self.kind, self.sc
@@ -772,6 +872,119 @@ class SeqNet(CLSRNet):
             for k, s, idx in zip(keys, sl, ids):
                 call("clsr_scatter_add_rows", s, Du, 0, idx, 1, B, Du, tg[k], None)
         out = dict(logit=logit, model_output=mo, dlogit=dlogit, slices=dict(zip(keys, sl)))
+        if apply:
+            self._apply_updates()
+        return out
+
+    # ------------------------------------------------------------------ LGN
+    def _lgn_node_table(self):
+        """E_0 = [user_embedding ; item_embedding ++ cate_embedding[item2cate]]: three row gathers, one launch."""
+        Vu, Vi, C, Di, Dc, tb = self.dims["Vu"], self.dims["Vi"], self.D, self.Di, self.Dc, self.tables
+        E0 = self._buf("lg.E0", Vu + Vi, C)
+        row = ops.GatherDesc.row
+        ops.multi("clsr_gather_rows_multi", ops.GatherDesc, [
+            row(table=tb["user"], idx=self.lg_all_users, out=E0, idx_stride=1, N=Vu, C=C, ldo=C),
+            row(table=tb["item"], idx=self.lg_all_items, out=E0[Vu:], idx_stride=1, N=Vi, C=Di, ldo=C),
+            row(table=tb["cate"], idx=self.lg_i2c, out=E0[Vu:], idx_stride=1, N=Vi, C=Dc, ldo=C, col0=Di)])
+        return E0
+
+    # F depends on the parameters only: evaluation propagates ONCE after the parameters changed (a training step,
+    # load_state_dict), outside the recorded launch sequence of a batch, which is then the scoring launch alone
+    def forward(self, f, training, after_attention=None, early_aux=None):
+        if self.kind == "lgn" and not training and not self.lg_F_valid:
+            with ops.stream_scope():
+                self.lg_F = self.lg_prop.forward(self._lgn_node_table(), self.lg_W, self.lg_b, training=False)
+            self.lg_F_valid = True
+        return super(SeqNet, self).forward(f, training, after_attention, early_aux)
+
+    def train_step(self, f, apply=True):
+        if self.kind == "lgn":
+            self.lg_F_valid = False
+        return super(SeqNet, self).train_step(f, apply)
+
+    def load_state_dict(self, sd, strict=True):
+        if self.kind == "lgn":
+            self.lg_F_valid = False
+        return super(SeqNet, self).load_state_dict(sd, strict=strict)
+
+    def _lgn_score(self, f):
+        """Evaluation / predict: ONE launch from the ids to the logits, over the cached F."""
+        B, T = f["B"], f["T"]
+        G = ((f.get("G") or 1) if self.dedup else 1) if f.get("compact") else 1
+        if B % G:
+            raise ValueError("feed rows (%d) must be a multiple of the history group (%d)" % (B, G))
+        self.last_shape = (B, T, G, B // G)
+        logit = self._buf("logit", B)
+        call("clsr_lgn_score", f["users"], G, f["items"], self.lg_F, self.dims["Vu"], self.dims["Vi"], self.D, B, logit)
+        return dict(logit=logit)
+
+    def _lgn_train_step(self, f, apply):
+        """Marks and the node table, two propagation launches, scoring + group softmax, the logit backward's rows summed
+        per id in sorted order into a zeroed dF, the regulariser on F's involved item rows, the propagation backward over the
+        transposed graph, dE_0 split into the three table gradients with their norms, then the shared update phase."""
+        hp = self.hp
+        self._step = _StepState(f)
+        B, T = f["B"], f["T"]
+        G = self.G_train if self.dedup else 1
+        Gl = hp.train_num_ngs + 1
+        if B % Gl:
+            raise ValueError("training feed rows (%d) must be a multiple of 1+train_num_ngs (%d)" % (B, Gl))
+        Hn = B // G
+        hs = 1 if f.get("compact") else G
+        udiv = G if f.get("compact") else 1        # lines per entry of f["users"]
+        self.last_shape = (B, T, G, Hn)
+        Vu, Vi, C, Di, Dc = self.dims["Vu"], self.dims["Vi"], self.D, self.Di, self.Dc
+        N, fl, prop, ss = Vu + Vi, self.tab_flags, self.lg_prop, self.sumsq_tab
+        dF = self._buf("lg.dF", N, C)
+        call("clsr_zero_doubles", self.losses, 8)
+        call("clsr_zero_doubles", ss, 16)
+        call("clsr_zero_floats", dF, dF.numel())
+        call("clsr_zero_floats", self.lg_inv_all.view(torch.float32), self.lg_inv_all.numel() // 4)
+        # rows an update visits: every row of the two dense-gradient tables; cate: set(item2cate) | involved.  lg_inv: the
+        # involved items (history ids included), whose rows of F the regulariser reaches
+        mark = ops.MarkDesc.row
+        ops.multi("clsr_mark_rows_multi", ops.MarkDesc, [
+            mark(idx=f["item_history"], flags=self.lg_inv, nrows=Hn, row_stride=hs * T, ncols=T),
+            mark(idx=f["items"], flags=self.lg_inv, nrows=B, row_stride=1, ncols=1),
+            mark(idx=f["item_cate_history"], flags=fl["cate"], nrows=Hn, row_stride=hs * T, ncols=T),
+            mark(idx=f["cates"], flags=fl["cate"], nrows=B, row_stride=1, ncols=1),
+            mark(idx=f["item_cate_history"], flags=self.lg_inv_c, nrows=Hn, row_stride=hs * T, ncols=T),
+            mark(idx=f["cates"], flags=self.lg_inv_c, nrows=B, row_stride=1, ncols=1),
+            mark(idx=self.lg_i2c, flags=fl["cate"], nrows=Vi, row_stride=1, ncols=1),
+            mark(idx=self.lg_all_items, flags=fl["item"], nrows=Vi, row_stride=1, ncols=1),
+            mark(idx=self.lg_all_users, flags=fl["user"], nrows=Vu, row_stride=1, ncols=1)])
+        F = prop.forward(self._lgn_node_table(), self.lg_W, self.lg_b, training=True)
+        logit, dlogit = self._buf("logit", B), self._buf("dlogit", B)
+        call("clsr_lgn_score", f["users"], udiv, f["items"], F, Vu, Vi, C, B, logit)
+        call("clsr_softmax_loss", logit, f["labels"], B // Gl, Gl, 1.0 / ((B // Gl) * self.dp_world), self.losses[0:], dlogit)
+        du, di = self._buf("lg.d_user", B, C), self._buf("lg.d_item", B, C)
+        uid = self._buf("lg.uid", B, dtype=torch.int32)
+        call("clsr_lgn_logit_bwd", f["users"], udiv, f["items"], F, Vu, Vi, C, B, dlogit, du, di, uid)
+        sort = []
+        for name, idx, V in (("lgn_user", uid, Vu), ("lgn_item", f["items"], Vi)):
+            sort.append(ops.SortIdsDesc.row(
+                ids=idx, keys_out=self._buf("sort.keys." + name, B, dtype=torch.int32),
+                perm_out=self._buf("sort.perm." + name, B, dtype=torch.int32), nrows=B, row_stride=1, ncols=1,
+                bits=max(1, (V - 1).bit_length())))
+        sws = self._buf("sort.ws", query("clsr_sort_ids_stable_workspace_bytes", 2 * B, 2), dtype=torch.uint8)
+        ops.sort_ids_stable_multi(sort, sws)
+        self._segsum("lgn", [self._site_row("lgn_user", du, C, 0, C, B, dF[:Vu], None),
+                             self._site_row("lgn_item", di, C, 0, C, B, dF[Vu:], None)])
+        call("clsr_lgn_reg_rows", self.lg_inv, F[Vu:], dF[Vu:], Vi, C, float(hp.embed_l2), self.lg_stats, self.losses[1:], None)
+        dE0, parts = prop.backward(dF, reduce=False)
+        for k, part in enumerate(parts):
+            self._rp(part, prop.parts, prop.part_floats, prop.part_floats, self.lg_dWb[k])
+        self._dw_flush()
+        # ---- dE_0 reaches the three gradient tables: user and item as they are (dense), cate as segment sums by item2cate
+        tg, cs = self.tab_grad, self.lg_cate
+        call("clsr_copy_cols", dE0, C, 0, 1, Vu, C, tg["user"], C, 0, 0)
+        call("clsr_copy_cols", dE0[Vu:], C, 0, 1, Vi, Di, tg["item"], Di, 0, 0)
+        call("clsr_lgn_rows_sum", *cs.head(), Vi, dE0[Vu:, Di:], C, Dc, tg["cate"], Dc, cs.ws)
+        # (the raw cate_embedding's involved rows: the usual regulariser term, its slice's norm in slot 5)
+        call("clsr_lgn_reg_rows", self.lg_inv_c, self.tables["cate"], tg["cate"], self.dims["Vc"], Dc, float(hp.embed_l2),
+             self.lg_stats, self.losses[1:], ss[5:])
+        call("clsr_lgn_grad_sumsq", dE0, Vu, N, C, Di, self.lg_stats, ss[6:], ss[0:], ss[1:])
+        out = dict(logit=logit, dlogit=dlogit, F=F, dF=dF, dE0=dE0)
         if apply:
             self._apply_updates()
         return out

@@ -852,6 +852,63 @@ int clsr_nextitnet_fwd(const float* hist, long Hn, int T, int C, const float* pa
 int clsr_nextitnet_bwd(const float* dout, const float* saved, long Hn, int T, int C, const float* params, int k,
                        int nblocks, const int* dilations, float* dhist, float* partial, void* stream);
 
+/* LGN (models/sequential/lgn.py, csrc/lgn.hip): all N node rows [N, C] (fp32, contiguous, C a multiple of 4 up to
+ * clsr_lgn_max_width() = 128) propagated through a CSR matrix (indptr [N + 1], indices, values: int32 / fp32 on the DEVICE,
+ * N and the entry count within int32: clsr_lgn_supported), a dense layer fused behind the product.  W [C][C] (in x out) and
+ * b [C] stay in LDS for the launch (clsr_lgn_lds_floats); slope of the leaky ReLU 0.2, derivative 0.2 at zero.
+ * Skewed rows: a row longer than clsr_lgn_row_chunk() (128) entries is split into chunks of that many entries, each summed
+ * by one wave in a launch of its own, the chunk sums added in chunk order: a row's value does not depend on the launch
+ * geometry.  The caller names those rows once (the graph is fixed): long_rows [nlong] ascending, long_off [nlong + 1]
+ * (row long_rows[q] owns chunks long_off[q] .. long_off[q + 1]; nchunks = long_off[nlong]), and workspace of
+ * clsr_lgn_workspace_floats(nchunks, C) floats, 16-byte aligned (nlong = 0: all three may be NULL).  No float atomics
+ * anywhere: two runs are bit-identical.  Entries that point outside the matrix are skipped, never read.
+ * clsr_lgn_layer_fwd:  S = A E_in;  E_out = lrelu(S W + b);  S_out [N, C] receives S (training) or is NULL;  with F_out,
+ *   F_out = (E0 + E_in + E_out) / 3 (the last of the two layers).  E_out / S_out must not be E_in.
+ * clsr_lgn_layer_bwd:  the CSR is A^T's.  d_out = (dF / 3 + (A^T P) W^T) * lrelu'(E_gate)  (E_gate NULL: no gate; the
+ *   derivative is read off the layer OUTPUT E_gate: 1 where positive, else 0.2), and per workgroup one row
+ *   [C * C | C] of partial (clsr_lgn_parts(N) rows of clsr_lgn_part_floats(C)): the sums of S^T P and of P's columns over
+ *   the workgroup's rows -- the caller reduces the rows in ascending order (clsr_reduce_parts_multi).  d_out must not be P.
+ * clsr_lgn_gate: out = scale * d * lrelu'(E), n elements (n a multiple of 4).
+ * clsr_lgn_rows_sum: the product alone, out [N, ldo] columns 0 .. width = sum of values * X [ncols, ldx] rows (values
+ *   NULL: ones) -- the category gradient: segments of item rows.
+ * clsr_lgn_score: logit[l] = F[users[l / user_div]] . F[Vu + items[l]], one launch.  clsr_lgn_logit_bwd: one launch, the
+ *   un-merged rows d_user[l] = dlogit[l] F[Vu + items[l]], d_item[l] = dlogit[l] F[user] ([B, C] each) and user_ids [B]
+ *   (the user of every line): the caller sums duplicate ids in a fixed order.  Ids outside their table: logit 0, zero rows.
+ * clsr_lgn_reg_rows: the involved-row regulariser over a table of rows F [V, C] (F's item part: the regulariser through the
+ *   graph; the raw cate_embedding) -- for every row r < V with flags[r], dF[r] += l2 F[r]; reg_loss[0] += l2 / 2 * sum
+ *   F[r]^2; sumsq (may be NULL) receives the squared norm of the added rows.  clsr_lgn_grad_sumsq: STORES the squared norms of dE0 [N, C]'s three pieces: rows
+ *   below Vu (user table), the other rows' columns 0 .. Di (item table) and Di .. C (the item2cate lookup's slices).  Both:
+ *   workspace of clsr_lgn_stats_workspace_doubles() doubles, per-workgroup sums added in a fixed order, no atomics. */
+int clsr_lgn_row_chunk(void);
+long clsr_lgn_stats_workspace_doubles(void);
+int clsr_lgn_reg_rows(const unsigned char* flags, const float* F, float* dF, long V, int C, float l2, double* workspace,
+                      double* reg_loss, double* sumsq, void* stream);
+int clsr_lgn_grad_sumsq(const float* dE0, long Vu, long N, int C, int Di, double* workspace, double* ss_user,
+                        double* ss_item, double* ss_cate, void* stream);
+int clsr_lgn_max_width(void);
+int clsr_lgn_tile_rows(void);
+int clsr_lgn_supported(long N, long entries, int C);
+long clsr_lgn_lds_floats(int C, int backward);
+int clsr_lgn_parts(long N);
+long clsr_lgn_part_floats(int C);
+long clsr_lgn_workspace_floats(long chunks, int width);
+int clsr_lgn_layer_fwd(const int* indptr, const int* indices, const float* values, const int* long_rows,
+                       const int* long_off, int nlong, long nchunks, long N, int C, const float* E_in, const float* W,
+                       const float* b, float* S_out, float* E_out, const float* E0, float* F_out, float* workspace,
+                       void* stream);
+int clsr_lgn_layer_bwd(const int* indptr, const int* indices, const float* values, const int* long_rows,
+                       const int* long_off, int nlong, long nchunks, long N, int C, const float* P, const float* W,
+                       const float* dF, const float* S, const float* E_gate, float* d_out, float* partial,
+                       float* workspace, void* stream);
+int clsr_lgn_rows_sum(const int* indptr, const int* indices, const float* values, const int* long_rows,
+                      const int* long_off, int nlong, long nchunks, long N, long ncols, const float* X, int ldx, int width,
+                      float* out, int ldo, float* workspace, void* stream);
+int clsr_lgn_gate(const float* d, const float* E, long n, float scale, float* out, void* stream);
+int clsr_lgn_score(const int* users, int user_div, const int* items, const float* F, long Vu, long Vi, int C, long B,
+                   float* logit, void* stream);
+int clsr_lgn_logit_bwd(const int* users, int user_div, const int* items, const float* F, long Vu, long Vi, int C, long B,
+                       const float* dlogit, float* d_user, float* d_item, int* user_ids, void* stream);
+
 /* ---- dropout of _fcn_net's hidden layers (csrc/dropout.hip, csrc/philox.h): base_model.py _active_layer, user_dropout --
  * a = relu(dropout(bn(z))), keep = 1 - dropout[layer].  The mask is a function of (seed, draw, layer, GLOBAL row, column):
  * Philox4x32-10 with counter (row0 + r, c / 4, layer, draw) and key (seed low, seed high); its four words serve columns
