@@ -164,8 +164,13 @@ class BaseModel(object):
 class SequentialBaseModel(BaseModel):
     def __init__(self, hparams, iterator_creator, graph=None, seed=None, device="cuda:0", use_graph=False,
                  dedup_histories=True, dist=None, sync_bn=True, group=None, precision="fp32", table_dtype="fp32",
-                 table_master=False, shard_eval=False):
+                 table_master=False, shard_eval=False, resident_data=False):
         """Reference ``SequentialBaseModel.__init__`` (:19-48): requires ``train_num_ngs``.
+
+        ``resident_data=True``: the padded column store of every training file is kept in HBM (clsr_amd/resident.py,
+        about ``N * (16 T + 16)`` bytes per file) and a training batch is gathered there from the ``(file, sel, src)``
+        recipe its feed carries; only ``sel`` and ``src`` cross PCIe.  The step sees the device feed it always saw.
+        Evaluation and ``predict`` feeds, and feeds without a recipe, take the host path.
 
         ``dist`` (an initialised ``torch.distributed`` module, one process per GPU) turns ``train`` / ``fit``
         into single-node data parallelism: every rank iterates the SAME global batches (same files, same
@@ -193,6 +198,7 @@ class SequentialBaseModel(BaseModel):
         self._table_dtype = table_dtype      # "bf16": embedding tables stored as bf16 (CLSRNet(table_dtype=...))
         self._table_master = bool(table_master)     # ... with an exact fp32 master kept as optimiser state (table_master=...)
         self._shard_eval = bool(shard_eval) and dist is not None
+        self._resident_data, self._resident = bool(resident_data), None
         self.eval_rows_scored = 0
         self.dp_dropped_positives = self.dp_skipped_batches = 0
         self._use_graph = use_graph and dist is None
@@ -207,6 +213,13 @@ class SequentialBaseModel(BaseModel):
     # ------------------------------------------------------------------ construction
     def _build_graph(self):
         hp = self.hparams
+        if self._resident_data:
+            it = self.iterator
+            if not getattr(it, "lazy_histories", False) or not hasattr(it, "defer_compact"):
+                raise NotImplementedError(
+                    "%s(resident_data=True): %s converts its batches line by line and keeps no padded column store to "
+                    "hold on the device" % (type(self).__name__, type(it).__name__))
+            it.defer_compact = True
         self.keep_prob_train = 1 - np.array(hp.dropout)
         self.keep_prob_test = np.ones_like(hp.dropout)
         self.embedding_keep_prob_train = 1.0 - hp.embedding_dropout
@@ -215,6 +228,10 @@ class SequentialBaseModel(BaseModel):
                     Vc=len(load_dict(hp.cate_vocab)))
         self.user_vocab_length, self.item_vocab_length, self.cate_vocab_length = dims["Vu"], dims["Vi"], dims["Vc"]
         self.net = self._make_net(hp, dims)
+        if self._resident_data:
+            from clsr_amd.resident import ResidentStore
+
+            self._resident = ResidentStore(self.iterator, self.net.device)
 
     def _make_net(self, hp, dims):
         return CLSRNet(hp, dims, device=self._device, seed=self.seed, dedup_histories=self._dedup,
@@ -226,6 +243,9 @@ class SequentialBaseModel(BaseModel):
         feed that carries the compact history-level arrays (sequential_iterator.LazyFeed) is passed on
         in that form, so the (1 + train_num_ngs)-fold repeated histories are never built or uploaded."""
         it = self.iterator
+        if training and self._resident is not None and getattr(feed_dict, "recipe", None) is not None:
+            # resident columns: the recipe is the batch (``_stage_resident``); no host array is read
+            return {"_recipe": feed_dict.recipe, "_cols": feed_dict._cols}
         compact = getattr(feed_dict, "compact", None) if training else None
         if compact is not None:
             arrays = {name: feed_dict[getattr(it, name)] for name in ("labels", "items", "cates")}
@@ -308,9 +328,51 @@ class SequentialBaseModel(BaseModel):
             self._stream = torch.cuda.Stream(device=self.net.device, priority=prio)
         return torch.cuda.stream(self._stream)
 
+    def _stage_resident(self, feed, lookahead):
+        """A training batch given as its recipe -> the device feed, gathered from the file's resident columns by
+        ``clsr_feed_build`` on the compute stream.  Under ``dist`` the rank builds the shard ``dp.shard_feed`` would cut:
+        ``per = n // world`` whole groups from line ``rank * per`` on (``src`` still points into the global batch)."""
+        from clsr_amd.resident import check_recipe
+
+        infile, sel, src = feed["_recipe"]
+        rc = self._resident.get(infile, feed["_cols"])
+        n = check_recipe(sel, src, rc.N, self.net.G_train)
+        h0, per = 0, n
+        if self._dist is not None:
+            from clsr_amd.dp import DataParallel
+
+            if self._dp is None:
+                self._dp = DataParallel(self.net, self._dist, sync_bn=self._sync_bn, group=self._group)
+            per = n // self._dp.world
+            if per == 0:
+                raise ValueError("global batch of %d positives cannot feed %d ranks" % (n, self._dp.world))
+            h0 = self._dp.rank * per
+        key = ("resident", per, rc.T, True, self.net.G_train)
+        if not lookahead:
+            f = self._static[key] = self.net.build_feed(rc, sel, src, h0, per, into=self._static.get(key))
+            return key, f
+        # two arenas filled in turn: batch N + 1 is built (same stream, a few microseconds) before step N is launched
+        st = self._static.get(("2x",) + key)
+        if st is None:
+            st = self._static[("2x",) + key] = [[None, None], 0]
+        i = st[1]
+        st[1] ^= 1
+        st[0][i] = self.net.build_feed(rc, sel, src, h0, per, into=st[0][i])
+        return key, st[0][i]
+
+    def check_resident(self):
+        """Raise if ``clsr_feed_build`` refused a batch since the last call (an index outside the file or the batch; the
+        host-side recipe check makes this unreachable).  Synchronises the model's stream."""
+        if self._resident is not None:
+            with self._stream_ctx():
+                for rc in self._resident.files.values():
+                    ops.call("clsr_feed_error", rc.err)
+
     def _stage(self, feed, lookahead=False):
         """Host arrays of one training batch -> an uploaded (or uploading) device feed."""
         with self._stream_ctx():
+            if "_recipe" in feed:
+                return self._stage_resident(feed, lookahead and not self._use_graph)
             if self._dist is not None:
                 from clsr_amd.dp import DataParallel, shard_feed
 
@@ -417,7 +479,8 @@ class SequentialBaseModel(BaseModel):
                 if self._dist is not None:
                     # a last batch with fewer positives than ranks cannot be sharded: every rank sees the same
                     # global batch and skips it alike; a remainder (positives % world) is truncated by shard_feed
-                    n_pos = arrays["labels"].shape[0] // (self.train_num_ngs + 1)
+                    n_pos = (arrays["_recipe"][1].shape[0] if "_recipe" in arrays
+                             else arrays["labels"].shape[0] // (self.train_num_ngs + 1))
                     self.dp_dropped_positives += n_pos % world if n_pos >= world else n_pos
                     if n_pos < world:
                         self.dp_skipped_batches += 1
@@ -433,6 +496,7 @@ class SequentialBaseModel(BaseModel):
                   "a multiple of %d ranks" % (self.dp_dropped_positives, self.dp_skipped_batches, world))
         with self._stream_ctx():
             total = float(acc[:4].sum().item())
+            self.check_resident()
             net.check_abort()       # end of an epoch: an aborted step (bounded wait gave up) must not reach evaluation / checkpoints
             return total
 

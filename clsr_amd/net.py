@@ -1404,6 +1404,72 @@ class CLSRNet(object):
         into["_stage"][slot][1] = ev
         return into
 
+    def build_feed(self, resident, sel, src, h0=0, n=None, into=None):
+        """The device feed ``upload`` would return for a training batch, built ON the device from the batch's recipe
+        and the file's resident columns (clsr_amd/resident.py, ``clsr_feed_build``): ``sel`` int32 ``[n_sel]`` file
+        lines, ``src`` int32 ``[n_sel, G_train]`` batch positions (checked by the caller:
+        :func:`clsr_amd.resident.check_recipe`).  ``h0``, ``n``: the lines of the batch to build (a data-parallel
+        rank's shard; default: all).  Only ``sel`` and ``src`` cross PCIe, through a ring of pinned slots like the
+        arenas of ``upload``; everything is enqueued on the current stream.  ``into``: an earlier result of the same
+        shape, re-used."""
+        G, T = self.G_train, resident.T
+        n_sel = int(sel.shape[0])
+        n = n_sel - h0 if n is None else int(n)
+        compact = self.dedup
+        R, B = (n if compact else n * G), n * G
+        if not query("clsr_feed_build_supported", resident.N, n_sel, T, G):
+            raise NotImplementedError("clsr_feed_build: N = %d, batch of %d lines, T = %d, G = %d is not supported"
+                                      % (resident.N, n_sel, T, G))
+        if into is None:
+            i32, f32 = torch.int32, torch.float32
+            spec = (("users", (R,), i32), ("items", (B,), i32), ("cates", (B,), i32), ("item_history", (R, T), i32),
+                    ("item_cate_history", (R, T), i32), ("time_from_first_action", (R, T), f32),
+                    ("time_to_now", (R, T), f32), ("labels", (B,), f32), ("seq_len", (R,), i32), ("denom", (1,), f32))
+            lay, off = {}, 0
+            for k, shape, _ in spec:           # (the layout of ``upload``: 16-byte aligned pieces of one arena)
+                nb = 4 * int(np.prod(shape))
+                lay[k] = (off, nb)
+                off += (nb + 15) // 16 * 16
+            dev = torch.empty(off, dtype=torch.uint8, device=self.device)
+            into = {"B": B, "T": T, "compact": compact, "G": G if compact else 0, "_lay": lay, "_nbytes": off,
+                    "_dev": dev, "_slot": 0, "_stage": [None] * self._STAGE_SLOTS, "_rcap": 0, "_rdev": None,
+                    "_rslot": 0, "_rstage": [None] * self._STAGE_SLOTS, "_desc": None}
+            for k, shape, dt in spec:
+                o, nb = lay[k]
+                into[k] = dev[o:o + nb].view(dt).view(shape)
+        assert into["B"] == B and into["T"] == T and into["compact"] == compact
+        self._last_group = into["G"]
+        src_off = (4 * n_sel + 15) // 16 * 16
+        nbytes = src_off + (4 * n_sel * G + 15) // 16 * 16
+        if nbytes > into["_rcap"]:
+            for st in into["_rstage"]:      # (a pinned slot a queued kernel still reads is not let go of)
+                if st is not None and st[1] is not None:
+                    st[1].synchronize()
+            into["_rcap"], into["_rstage"], into["_desc"] = nbytes, [None] * self._STAGE_SLOTS, None
+            into["_rdev"] = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        slot = into["_rslot"]
+        into["_rslot"] = (slot + 1) % self._STAGE_SLOTS
+        if into["_rstage"][slot] is None:
+            pin = torch.empty(into["_rcap"], dtype=torch.uint8, pin_memory=True)
+            into["_rstage"][slot] = [pin, None, pin.numpy()]
+        pin, ev, pin_np = into["_rstage"][slot]
+        if ev is not None:
+            ev.synchronize()
+        np.copyto(pin_np[:4 * n_sel], sel.view(np.uint8))
+        np.copyto(pin_np[src_off:src_off + 4 * n_sel * G], src.reshape(-1).view(np.uint8))
+        rdev = into["_rdev"]
+        call("clsr_stage_feed", rdev, pin.data_ptr(), nbytes)
+        ev = torch.cuda.Event()
+        ev.record()
+        into["_rstage"][slot][1] = ev
+        ent = into["_desc"]
+        if ent is None or ent[0] is not resident:
+            ent = into["_desc"] = (resident, ops.feed_pointers(resident.dev, {k: into[k] for k in ops.FEED_OUTPUTS}))
+        thr = int(getattr(self.hp, "contrastive_length_threshold", None) or 0)     # (unset for the sibling models)
+        ops.feed_build(ent[1], resident.N, rdev.data_ptr(), n_sel, rdev.data_ptr() + src_off, int(h0), n, T, G,
+                       not compact, thr, resident.err)
+        return into
+
     # ------------------------------------------------------------------ attention block
     def _att_fwd(self, key, scope, keys, q, Hn, G, T, Dk, Q, seq_len, len_stride, training, q_hist=None):
         P, A0, A1 = self.P, self.A0, self.A1

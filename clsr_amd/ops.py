@@ -387,6 +387,32 @@ def heads_fused(step, desc):
     call("clsr_heads_fused_step%d" % step, ctypes.addressof(desc))
 
 
+FEED_COLUMNS = ("item_history", "item_cate_history", "time_from_first_action", "time_to_now", "lens", "users", "items", "cates")
+FEED_OUTPUTS = ("users", "items", "cates", "item_history", "item_cate_history", "time_from_first_action", "time_to_now",
+                "labels", "seq_len", "denom")
+
+
+def feed_pointers(cols, outs):
+    """The two host pointer arrays of clsr_feed_build from dicts of tensors (``FEED_COLUMNS`` / ``FEED_OUTPUTS``), with the
+    dtypes the entry point reads them as checked here (it sees addresses only)."""
+    f32 = ("time_from_first_action", "time_to_now", "labels", "denom")
+    for d in (cols, outs):
+        for k, t in d.items():
+            want = torch.float32 if k in f32 else torch.int32
+            if not (t.is_cuda and t.is_contiguous() and t.dtype == want):
+                raise TypeError("clsr_feed_build %s: a contiguous %s GPU tensor is required, got %s" % (k, want, t.dtype))
+    return ((ctypes.c_void_p * len(FEED_COLUMNS))(*[cols[k].data_ptr() for k in FEED_COLUMNS]),
+            (ctypes.c_void_p * len(FEED_OUTPUTS))(*[outs[k].data_ptr() for k in FEED_OUTPUTS]))
+
+
+def feed_build(ptrs, N, sel, n_sel, src, h0, n, T, G, expanded, thr, err):
+    """clsr_feed_build: the two launches that build (lines h0 .. h0 + n - 1 of) a training feed from resident columns.
+    ``ptrs``: the result of :func:`feed_pointers`; ``sel`` / ``src``: int32 tensors or device addresses."""
+    keep_alive(ptrs)
+    call("clsr_feed_build", ctypes.addressof(ptrs[0]), N, sel, n_sel, src, h0, n, T, G, int(expanded), thr,
+         ctypes.addressof(ptrs[1]), err)
+
+
 DW_MULTI_MAX = 12
 
 

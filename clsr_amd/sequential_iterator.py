@@ -112,6 +112,12 @@ class LazyFeed(dict):
     ``values``/``get``) materialises everything first, so this behaves like the plain dict.
     """
 
+    #: ``(file, sel, src)`` of a training feed drawn from a column store: ``sel`` int32 ``[n]``, the file lines of the batch
+    #: in batch order; ``src`` int32 ``[n, 1 + ngs]``, the batch line whose (item, cate) every output row carries.  Together
+    #: with the file's columns (``_cols``) that is the whole batch: clsr_amd/resident.py rebuilds the feed on the device.
+    recipe = None
+    _cols = None
+
     def __init__(self, eager, thunks, compact):
         dict.__init__(self, eager)
         self._thunks = dict(thunks)
@@ -288,7 +294,10 @@ class SequentialIterator(BaseIterator):
         keep = order[cols["full_len"][order] >= min_seq_length]
         for a in range(0, len(keep), self.batch_size):
             sel = keep[a:a + self.batch_size]
-            feed = self.gen_feed_dict(self._convert_rows(cols, sel, batch_num_ngs))
+            data = self._convert_rows(cols, sel, batch_num_ngs)
+            feed = self.gen_feed_dict(data)
+            if isinstance(data, LazyFeed) and data.recipe is not None:
+                feed.recipe, feed._cols = (infile,) + data.recipe, cols
             yield feed if feed else None
 
     def _load_columns(self, infile):
@@ -458,14 +467,24 @@ class SequentialIterator(BaseIterator):
             res["time"] = cols["time"][sel]
         big = ("item_history", "item_cate_history", "mask", "time_diff", "time_from_first_action", "time_to_now")
         if batch_num_ngs and self.lazy_histories:
-            compact = {k: cols[k][sel] for k in big if k != "time_diff"}
-            compact["users"] = cols["users"][sel]
-            compact["hist_group"] = batch_num_ngs + 1
+            if self.defer_compact:
+                # (a consumer that rebuilds the batch on the device from ``recipe`` never reads these: no work
+                # proportional to n * T is left in the batch)
+                ct = {k: (lambda k=k: cols[k][sel]) for k in big if k != "time_diff"}
+                ct["users"] = lambda: cols["users"][sel]
+                compact = LazyFeed({"hist_group": batch_num_ngs + 1}, ct, None)
+            else:
+                compact = {k: cols[k][sel] for k in big if k != "time_diff"}
+                compact["users"] = cols["users"][sel]
+                compact["hist_group"] = batch_num_ngs + 1
             thunks = {k: (lambda k=k: cols[k][rows]) for k in big}
             if self._with_attn_labels:
                 thunks["attn_labels"] = lambda: self._attn_labels(
                     cols["item_cate_history"][rows], cols["mask"][rows], cols["lens"][rows], row_cates)
-            return LazyFeed(res, thunks, compact)
+            out = LazyFeed(res, thunks, compact)
+            if n < (1 << 31) // G and cols["n"] < (1 << 31):
+                out.recipe = (np.ascontiguousarray(sel, dtype=np.int32), np.ascontiguousarray(src, dtype=np.int32))
+            return out
         for k in big:
             res[k] = cols[k][rows]
         return res
@@ -481,6 +500,9 @@ class SequentialIterator(BaseIterator):
     _with_attn_labels = False
     #: training feeds defer the (1 + ngs)-fold repetition of the padded histories (see LazyFeed)
     lazy_histories = True
+    #: also defer the history-level arrays of ``feed.compact`` (set by a model built with ``resident_data=True``, which
+    #: reads ``feed.recipe`` instead); whoever reads them still gets today's values
+    defer_compact = False
 
     def _pad_histories(self, item_history_batch, item_cate_history_batch, time_diff_list,
                        time_from_first_action_list, time_to_now_list):

@@ -74,6 +74,9 @@ def get_flags():
                    help="comma list, one rate per layer of layer_sizes")
     p.add_argument("--shard_eval", type=str2bool, default=False,
                    help="data parallel only: the ranks share validation / test (same metrics, to the bit)")
+    p.add_argument("--resident_data", type=str2bool, default=False,
+                   help="keep the padded columns of the training file in HBM (about N * (16 T + 16) bytes) and gather every "
+                        "training batch there; not for NEXTITNET")
     return p.parse_args()
 
 
@@ -107,7 +110,8 @@ def get_model(flags_obj, model_path, summary_path, user_vocab, item_vocab, cate_
             hparams.save_model = False
         # (NextItNet's feeds carry a target per position and left-padded histories: an iterator of its own)
         iterator = NextItNetIterator if flags_obj.model == "NEXTITNET" else SequentialIterator
-        return cls(hparams, iterator, seed=None, device=device, dist=dist, shard_eval=flags_obj.shard_eval)
+        return cls(hparams, iterator, seed=None, device=device, dist=dist, shard_eval=flags_obj.shard_eval,
+                   resident_data=flags_obj.resident_data)
     if flags_obj.model != "CLSR":
         raise SystemExit("--model must be CLSR, SLIREC, GRU4REC, DIN, DIEN, A2SVD, CASER, NCF, NEXTITNET or LGN")
     hparams = prepare_hparams(
@@ -127,7 +131,7 @@ def get_model(flags_obj, model_path, summary_path, user_vocab, item_vocab, cate_
     # data parallel: save_model stays on for EVERY rank -- CLSRModel.save_model is collective (rank 0 writes the
     # file atomically, then all ranks pass a barrier), so nobody loads a checkpoint that is still being written
     return CLSRModel(hparams, SASequentialIterator, seed=None, device=device, dist=dist,
-                     shard_eval=flags_obj.shard_eval)
+                     shard_eval=flags_obj.shard_eval, resident_data=flags_obj.resident_data)
 
 
 def init_data_parallel(flags_obj):

@@ -1200,6 +1200,34 @@ int clsr_eval_finalize(void* acc, int n, int scale, void* stream);
 int clsr_host_mt_shuffle(unsigned* key, int* pos, long* perm, long n);
 int clsr_host_mt_sample_negatives(unsigned* key, int* pos, const long* items, long n, int ngs, long* src);
 
+/* ---- training feeds built on the device from a resident column store (csrc/feed.hip, clsr_amd/resident.py): the padded
+ *      per-line columns of a file stay in HBM -- item_history, item_cate_history (int32 [N, T]), time_from_first_action,
+ *      time_to_now (fp32 [N, T]), lens, users, items, cates (int32 [N]) -- and a batch is its recipe: sel [n_sel] (int32 line
+ *      numbers of the global batch) and src [n_sel, G] (int32 positions inside the batch: the line whose item / category
+ *      output row h * G + g carries).  cols_host: HOST array of the eight device pointers in that order; outs_host: HOST
+ *      array of the ten output pointers out_users, out_items, out_cates, out_item_history, out_item_cate_history,
+ *      out_time_from_first_action, out_time_to_now, out_labels, out_seq_len, out_denom.  The call builds lines h0 .. h0 + n - 1
+ *      of the batch (a data-parallel rank's shard; h0 = 0, n = n_sel: the whole batch) in the layout of CLSRNet.host_arrays:
+ *        out_items / out_cates [n G] = items / cates [sel[src[h0 + h, g]]],  out_labels [n G] = 1 at g = 0, else 0,
+ *        out_item_history .. out_time_to_now [R, T] = the rows sel[h0 + h] of the four [N, T] columns, out_users /
+ *        out_seq_len [R] = users / lens [sel[h0 + h]],  R = n (expanded = 0: one row per history) or n G (expanded = 1:
+ *        every row of a group repeats its history),  out_denom [1] = float(#{h : lens[sel[h0 + h]] > thr} * G), the count an
+ *        integer.
+ *      Rows move in 16-byte words when T % 4 == 0 and the eight [., T] pointers are 16-byte aligned, in 4-byte words otherwise.
+ *      Two launches, asynchronous.  The first holds every sel against N and every src of the shard against n_sel; a value that
+ *      cannot be served raises err (4 ints, ZERO when first used: code 1 sel / 2 src, index, value -- sticky until
+ *      clsr_feed_clear_error -- and the status of this call) and the call then writes NOTHING to the outputs: no index is used
+ *      as an address before it passed.  clsr_feed_error (synchronises `stream`): 0, or -1 with clsr_last_error naming the
+ *      index.  clsr_feed_build_supported: 1 <= N < 2^31, 1 <= T <= clsr_feed_build_max_steps() (4096), 1 <= G <=
+ *      clsr_feed_build_max_group() (1024), n_sel (G + 1) < 2^31; otherwise -3 from the entry point. */
+int clsr_feed_build_supported(long N, long n_sel, int T, int G);
+int clsr_feed_build_max_group(void);
+int clsr_feed_build_max_steps(void);
+int clsr_feed_build(const void* const* cols_host, long N, const int* sel, long n_sel, const int* src, long h0, long n, int T,
+                    int G, int expanded, int thr, void* const* outs_host, int* err, void* stream);
+int clsr_feed_clear_error(int* err, void* stream);
+int clsr_feed_error(const int* err, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
