@@ -164,13 +164,19 @@ class BaseModel(object):
 class SequentialBaseModel(BaseModel):
     def __init__(self, hparams, iterator_creator, graph=None, seed=None, device="cuda:0", use_graph=False,
                  dedup_histories=True, dist=None, sync_bn=True, group=None, precision="fp32", table_dtype="fp32",
-                 table_master=False, shard_eval=False, resident_data=False):
+                 table_master=False, shard_eval=False, resident_data=False, resident_eval=False):
         """Reference ``SequentialBaseModel.__init__`` (:19-48): requires ``train_num_ngs``.
 
         ``resident_data=True``: the padded column store of every training file is kept in HBM (clsr_amd/resident.py,
         about ``N * (16 T + 16)`` bytes per file) and a training batch is gathered there from the ``(file, sel, src)``
         recipe its feed carries; only ``sel`` and ``src`` cross PCIe.  The step sees the device feed it always saw.
         Evaluation and ``predict`` feeds, and feeds without a recipe, take the host path.
+
+        ``resident_eval=True`` (independent of ``resident_data``): ``run_eval`` / ``run_weighted_eval`` / the validation
+        pass of ``fit`` build their feeds on the device too, from an image of the evaluated file of its own
+        (clsr_amd/resident.py: ``N * (16 T + 20)`` bytes plus ``4`` per line scored; a file that is also trained on under
+        ``resident_data`` is held twice).  The chunks, their shapes and every metric are those of the host path, bit for
+        bit.  ``predict``, ``eval``, ``eval_with_user*`` and ``infer`` stay on the host path.
 
         ``dist`` (an initialised ``torch.distributed`` module, one process per GPU) turns ``train`` / ``fit``
         into single-node data parallelism: every rank iterates the SAME global batches (same files, same
@@ -199,6 +205,7 @@ class SequentialBaseModel(BaseModel):
         self._table_master = bool(table_master)     # ... with an exact fp32 master kept as optimiser state (table_master=...)
         self._shard_eval = bool(shard_eval) and dist is not None
         self._resident_data, self._resident = bool(resident_data), None
+        self._resident_eval_flag, self._resident_eval = bool(resident_eval), None
         self.eval_rows_scored = 0
         self.dp_dropped_positives = self.dp_skipped_batches = 0
         self._use_graph = use_graph and dist is None
@@ -220,6 +227,10 @@ class SequentialBaseModel(BaseModel):
                     "%s(resident_data=True): %s converts its batches line by line and keeps no padded column store to "
                     "hold on the device" % (type(self).__name__, type(it).__name__))
             it.defer_compact = True
+        if self._resident_eval_flag and not getattr(self.iterator, "lazy_histories", False):
+            raise NotImplementedError(
+                "%s(resident_eval=True): %s converts its batches line by line and keeps no padded column store to hold "
+                "on the device" % (type(self).__name__, type(self.iterator).__name__))
         self.keep_prob_train = 1 - np.array(hp.dropout)
         self.keep_prob_test = np.ones_like(hp.dropout)
         self.embedding_keep_prob_train = 1.0 - hp.embedding_dropout
@@ -232,6 +243,10 @@ class SequentialBaseModel(BaseModel):
             from clsr_amd.resident import ResidentStore
 
             self._resident = ResidentStore(self.iterator, self.net.device)
+        if self._resident_eval_flag:
+            from clsr_amd.resident import ResidentEvalStore
+
+            self._resident_eval = ResidentEvalStore(self.iterator, self.net.device)
 
     def _make_net(self, hp, dims):
         return CLSRNet(hp, dims, device=self._device, seed=self.seed, dedup_histories=self._dedup,
@@ -574,7 +589,9 @@ class SequentialBaseModel(BaseModel):
             self.eval_rows_scored = 0
 
             def score(feeds):
-                n = sum(int(np.asarray(x["labels"]).shape[0]) for x in feeds)
+                # ``feeds``: the host feeds of a chunk, or (resident_eval) the chunk itself as (lines, k0, n, g)
+                resident = isinstance(feeds, tuple)
+                n = feeds[2] if resident else sum(int(np.asarray(x["labels"]).shape[0]) for x in feeds)
                 if part is not None:
                     owner = DM.chunk_owner(loads)
                     loads[owner] += n
@@ -582,10 +599,15 @@ class SequentialBaseModel(BaseModel):
                         acc.append_zeros(n, mean_alpha)
                         return
                 self.eval_rows_scored += n
-                feed = feeds[0] if len(feeds) == 1 else {
-                    k: (v if k == "hist_group" else np.concatenate([np.asarray(x[k]) for x in feeds], axis=0))
-                    for k, v in feeds[0].items()}
-                key, f, _ = self._static_feed(feed, False)
+                if resident:
+                    lines, k0, _, g = feeds
+                    key = ("resident_eval", n, lines.rc.T, g)
+                    f = self._static[key] = self.net.build_eval_feed(lines, k0, n, g, into=self._static.get(key))
+                else:
+                    feed = feeds[0] if len(feeds) == 1 else {
+                        k: (v if k == "hist_group" else np.concatenate([np.asarray(x[k]) for x in feeds], axis=0))
+                        for k, v in feeds[0].items()}
+                    key, f, _ = self._static_feed(feed, False)
                 out = self.net.forward(f, False)
                 pred = torch.sigmoid(out["logit"]) if self.hparams.method == "classification" else out["logit"]
                 acc.append(pred, f["labels"], f["users_rows"] if "users_rows" in f else f["users"],
@@ -594,8 +616,17 @@ class SequentialBaseModel(BaseModel):
             # the iterator's batches (hparams.batch_size LINES each) are scored several at a time: a forward pass is
             # ~100 launches whatever its size, and nothing here waits for the device between batches
             pend, rows, target = [], 0, int(os.environ.get("CLSR_EVAL_ROWS", "32768"))
-            for batch_data_input in self.iterator.load_data_from_file(
-                    filename, min_seq_length=self.min_seq_length, batch_num_ngs=0):
+            batches = ()
+            if self._resident_eval is not None:
+                # the same chunks from the plan: three integers a chunk, the feed is built where the file already is
+                from clsr_amd.resident import eval_chunk_plan
+
+                lines = self._resident_eval.get(filename, self.min_seq_length, flags=self._dedup)
+                for k0, n, g in eval_chunk_plan(lines.flags, lines.n_keep, self.iterator.batch_size, target, self._dedup):
+                    score((lines, k0, n, g))
+            else:
+                batches = self.iterator.load_data_from_file(filename, min_seq_length=self.min_seq_length, batch_num_ngs=0)
+            for batch_data_input in batches:
                 if not batch_data_input:
                     continue
                 feed = self._to_arrays(batch_data_input)

@@ -197,3 +197,205 @@ extern "C" int clsr_feed_error(const int* err, void* stream) {
     clsr_set_error("clsr_feed_build: src[%d] = %d is not a line of the batch", e[FEED_ERR_INDEX], e[FEED_ERR_VALUE]);
   return CLSR_EINVAL;
 }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Evaluation feeds from a resident column store (clsr_amd/resident.py, ResidentEvalStore).
+//
+// An evaluation pass yields the file lines keep[0 .. n_keep) in order (every entry checked against [0, N) on the host
+// before keep is uploaded), batch_size lines a batch; lines of one positive share a history.  clsr_feed_same_rows marks,
+// once per (file, keep), every line whose history-level columns equal those of the line before it; the host turns the
+// marks into chunks (k0, n, g) and clsr_feed_build_eval writes the arena CLSRNet.upload(feed, False) would have filled for
+// a chunk: history-level tensors from every g-th line, line-level tensors from every line.  One launch each.
+struct FeedEvalArgs {
+  const int* item_history; const int* item_cate_history; const float* time_from_first_action; const float* time_to_now;
+  const int* lens; const int* users; const int* items; const int* cates; const float* labels;
+  const int* keep;
+  int* out_users; int* out_items; int* out_cates; int* out_item_history; int* out_item_cate_history;
+  float* out_time_from_first_action; float* out_time_to_now; float* out_labels; int* out_users_rows; int* out_seq_len;
+  float* out_denom;
+  long k0, n;
+  int g, T, thr;
+};
+
+static void feed_eval_cols(FeedEvalArgs& d, const void* const* cols_host, int with_labels) {
+  d.item_history = (const int*)cols_host[0];
+  d.item_cate_history = (const int*)cols_host[1];
+  d.time_from_first_action = (const float*)cols_host[2];
+  d.time_to_now = (const float*)cols_host[3];
+  d.lens = (const int*)cols_host[4];
+  d.users = (const int*)cols_host[5];
+  d.items = (const int*)cols_host[6];
+  d.cates = (const int*)cols_host[7];
+  d.labels = with_labels ? (const float*)cols_host[8] : nullptr;
+}
+
+// the user id as the host path carries it: through the float32 placeholder of the reference and back
+__device__ __forceinline__ int feed_user_id(int id) { return (int)(float)id; }
+
+// words of the integer columns differ by bits, words of the float columns as numpy's == has it (-0.0 equals 0.0, a NaN
+// equals nothing)
+__device__ __forceinline__ bool feed_differ(unsigned a, unsigned b, bool fp) {
+  return fp ? !(__uint_as_float(a) == __uint_as_float(b)) : a != b;
+}
+__device__ __forceinline__ bool feed_differ(feed_u32x4 a, feed_u32x4 b, bool fp) {
+  return feed_differ(a.x, b.x, fp) | feed_differ(a.y, b.y, fp) | feed_differ(a.z, b.z, fp) | feed_differ(a.w, b.w, fp);
+}
+
+// A wave per pair of lines (keep[i - 1], keep[i]); lanes on consecutive words, the four [N, T] columns together; the pair
+// is left at the first 64-word slice that holds a difference.  i, and so every branch below, is uniform in the wave.
+template <typename W>
+__global__ void __launch_bounds__(256) feed_same_rows_kernel(FeedEvalArgs d, long n_keep, int Tq, unsigned char* flags) {
+  const int lane = threadIdx.x & 63;
+  const long wave = (long)blockIdx.x * 4 + (threadIdx.x >> 6), nwave = (long)gridDim.x * 4;
+  if (wave == 0 && lane == 0) flags[0] = 0;
+  const W* __restrict__ c0 = (const W*)d.item_history;
+  const W* __restrict__ c1 = (const W*)d.item_cate_history;
+  const W* __restrict__ c2 = (const W*)d.time_from_first_action;
+  const W* __restrict__ c3 = (const W*)d.time_to_now;
+  for (long i = 1 + wave; i < n_keep; i += nwave) {
+    const long a = d.keep[i], b = d.keep[i - 1];
+    bool diff = feed_user_id(d.users[a]) != feed_user_id(d.users[b]) || d.lens[a] != d.lens[b];
+    for (int s = 0; s < Tq && !diff; s += 64) {
+      const int c = s + lane;
+      bool mine = false;
+      if (c < Tq) {
+        const long pa = a * Tq + c, pb = b * Tq + c;
+        const W x0 = c0[pa], x1 = c1[pa], x2 = c2[pa], x3 = c3[pa];
+        const W y0 = c0[pb], y1 = c1[pb], y2 = c2[pb], y3 = c3[pb];
+        mine = feed_differ(x0, y0, false) | feed_differ(x1, y1, false) | feed_differ(x2, y2, true) | feed_differ(x3, y3, true);
+      }
+      diff = __any(mine) != 0;
+    }
+    if (lane == 0) flags[i] = diff ? 0 : 1;
+  }
+}
+
+// Blocks [0, big_blocks): the four [n / g, T] arrays, a lane per word.  The next blocks: the line-level arrays and, from
+// the first line of every group, users / seq_len.  The last block counts the histories longer than thr (an integer) and
+// writes denom.
+template <typename W>
+__global__ void __launch_bounds__(256) feed_build_eval_kernel(FeedEvalArgs d, long nq, int Tq, int big_blocks) {
+  const int g = d.g;
+  const int* __restrict__ keep = d.keep + d.k0;
+  if ((int)blockIdx.x < big_blocks) {
+    const W* __restrict__ c0 = (const W*)d.item_history;
+    const W* __restrict__ c1 = (const W*)d.item_cate_history;
+    const W* __restrict__ c2 = (const W*)d.time_from_first_action;
+    const W* __restrict__ c3 = (const W*)d.time_to_now;
+    W* __restrict__ o0 = (W*)d.out_item_history;
+    W* __restrict__ o1 = (W*)d.out_item_cate_history;
+    W* __restrict__ o2 = (W*)d.out_time_from_first_action;
+    W* __restrict__ o3 = (W*)d.out_time_to_now;
+    for (long q = (long)blockIdx.x * 256 + threadIdx.x; q < nq; q += (long)big_blocks * 256) {
+      const long h = q / Tq;
+      const int c = (int)(q - h * Tq);
+      const long s = (long)keep[h * g] * Tq + c;
+      const W v0 = c0[s], v1 = c1[s], v2 = c2[s], v3 = c3[s];
+      o0[q] = v0;
+      o1[q] = v1;
+      o2[q] = v2;
+      o3[q] = v3;
+    }
+    return;
+  }
+  const int small_blocks = (int)gridDim.x - big_blocks - 1;
+  if ((int)blockIdx.x < big_blocks + small_blocks) {
+    for (long b = (long)(blockIdx.x - big_blocks) * 256 + threadIdx.x; b < d.n; b += (long)small_blocks * 256) {
+      const int line = keep[b];
+      d.out_items[b] = d.items[line];
+      d.out_cates[b] = d.cates[line];
+      d.out_labels[b] = d.labels[line];
+      const int user = feed_user_id(d.users[line]);
+      if (d.out_users_rows) d.out_users_rows[b] = user;
+      const long h = b / g;
+      if (b == h * g) {
+        d.out_users[h] = user;
+        d.out_seq_len[h] = d.lens[line];
+      }
+    }
+    return;
+  }
+  __shared__ int s_cnt;
+  if (threadIdx.x == 0) s_cnt = 0;
+  __syncthreads();
+  int cnt = 0;
+  for (long h = threadIdx.x; h < d.n / g; h += 256) cnt += d.lens[keep[h * g]] > d.thr ? 1 : 0;
+  if (cnt) atomicAdd(&s_cnt, cnt);          // integer sum: the value does not depend on the order
+  __syncthreads();
+  if (threadIdx.x == 0) d.out_denom[0] = (float)((long)s_cnt * g);
+}
+
+extern "C" int clsr_feed_build_eval_supported(long N, long n_keep, long k0, long n, int g, int T) {
+  return N >= 1 && N <= INT_MAX && n_keep >= 1 && n_keep <= INT_MAX && T >= 1 && T <= clsr_feed_build_max_steps() &&
+         g >= 1 && n >= 1 && n % g == 0 && k0 >= 0 && k0 <= n_keep && n <= n_keep - k0 && (n / g) * (long)T <= INT_MAX;
+}
+
+extern "C" int clsr_feed_same_rows(const void* const* cols_host, long N, const int* keep, long n_keep, int T,
+                                   unsigned char* flags, void* stream) {
+  CLSR_CHECK_ARG(cols_host && keep && flags);
+  FeedEvalArgs d = {};
+  feed_eval_cols(d, cols_host, 0);
+  d.keep = keep;
+  d.T = T;
+  CLSR_CHECK_ARG(d.item_history && d.item_cate_history && d.time_from_first_action && d.time_to_now && d.lens && d.users);
+  CLSR_CHECK_ARG(N >= 1 && N <= INT_MAX && n_keep >= 1 && n_keep <= INT_MAX && T >= 1 && T <= clsr_feed_build_max_steps());
+  uintptr_t a = 0;
+  for (const void* p : {(const void*)d.item_history, (const void*)d.item_cate_history, (const void*)d.time_from_first_action,
+                        (const void*)d.time_to_now})
+    a |= (uintptr_t)p;
+  const bool wide = T % 4 == 0 && a % 16 == 0;
+  const int Tq = wide ? T / 4 : T;
+  long blocks = (n_keep + 3) / 4;            // four waves, four pairs a workgroup
+  if (blocks > 8192) blocks = 8192;
+  hipStream_t st = (hipStream_t)stream;
+  if (wide)
+    hipLaunchKernelGGL(feed_same_rows_kernel<feed_u32x4>, dim3((int)blocks), dim3(256), 0, st, d, n_keep, Tq, flags);
+  else
+    hipLaunchKernelGGL(feed_same_rows_kernel<unsigned>, dim3((int)blocks), dim3(256), 0, st, d, n_keep, Tq, flags);
+  CLSR_CHECK_LAUNCH();
+  return CLSR_OK;
+}
+
+extern "C" int clsr_feed_build_eval(const void* const* cols_host, long N, const int* keep, long n_keep, long k0, long n,
+                                    int g, int T, int thr, void* const* outs_host, void* stream) {
+  CLSR_CHECK_ARG(cols_host && outs_host && keep);
+  FeedEvalArgs d = {};
+  feed_eval_cols(d, cols_host, 1);
+  d.keep = keep;
+  d.out_users = (int*)outs_host[0];
+  d.out_items = (int*)outs_host[1];
+  d.out_cates = (int*)outs_host[2];
+  d.out_item_history = (int*)outs_host[3];
+  d.out_item_cate_history = (int*)outs_host[4];
+  d.out_time_from_first_action = (float*)outs_host[5];
+  d.out_time_to_now = (float*)outs_host[6];
+  d.out_labels = (float*)outs_host[7];
+  d.out_users_rows = (int*)outs_host[8];     // may be null: a g == 1 feed has no such tensor
+  d.out_seq_len = (int*)outs_host[9];
+  d.out_denom = (float*)outs_host[10];
+  d.k0 = k0, d.n = n, d.g = g, d.T = T, d.thr = thr;
+  CLSR_CHECK_ARG(d.item_history && d.item_cate_history && d.time_from_first_action && d.time_to_now);
+  CLSR_CHECK_ARG(d.lens && d.users && d.items && d.cates && d.labels);
+  CLSR_CHECK_ARG(d.out_users && d.out_items && d.out_cates && d.out_item_history && d.out_item_cate_history);
+  CLSR_CHECK_ARG(d.out_time_from_first_action && d.out_time_to_now && d.out_labels && d.out_seq_len && d.out_denom);
+  CLSR_CHECK_ARG(d.out_users_rows || g == 1);
+  CLSR_CHECK_ARG(clsr_feed_build_eval_supported(N, n_keep, k0, n, g, T));
+  uintptr_t a = 0;
+  for (const void* p : {(const void*)d.item_history, (const void*)d.item_cate_history, (const void*)d.time_from_first_action,
+                        (const void*)d.time_to_now, (const void*)d.out_item_history, (const void*)d.out_item_cate_history,
+                        (const void*)d.out_time_from_first_action, (const void*)d.out_time_to_now})
+    a |= (uintptr_t)p;
+  const bool wide = T % 4 == 0 && a % 16 == 0;
+  const int Tq = wide ? T / 4 : T;
+  const long nq = (n / g) * Tq;
+  long big = (nq + 255) / 256, small = (n + 255) / 256;
+  if (big > 16384) big = 16384;
+  if (small > 1024) small = 1024;
+  hipStream_t st = (hipStream_t)stream;
+  if (wide)
+    hipLaunchKernelGGL(feed_build_eval_kernel<feed_u32x4>, dim3((int)(big + small + 1)), dim3(256), 0, st, d, nq, Tq, (int)big);
+  else
+    hipLaunchKernelGGL(feed_build_eval_kernel<unsigned>, dim3((int)(big + small + 1)), dim3(256), 0, st, d, nq, Tq, (int)big);
+  CLSR_CHECK_LAUNCH();
+  return CLSR_OK;
+}

@@ -1470,6 +1470,48 @@ class CLSRNet(object):
                        not compact, thr, resident.err)
         return into
 
+    def build_eval_feed(self, lines, k0, n, g, into=None):
+        """The device feed ``upload(feed, False)`` would return for the evaluation chunk of lines ``keep[k0 : k0 + n]`` in
+        groups of ``g`` consecutive lines with one history, built ON the device by ``clsr_feed_build_eval`` from the
+        file's resident columns.  ``lines``: a :class:`clsr_amd.resident.EvalLines` (``keep`` was checked against the
+        file there).  ``g > 1`` needs ``dedup_histories``; ``g == 1`` gives the row layout without ``users_rows``.  One
+        launch on the current stream, nothing crosses PCIe.  ``into``: an earlier result of the same shape, re-used."""
+        rc, T = lines.rc, lines.rc.T
+        k0, n, g = int(k0), int(n), int(g)
+        if g > 1 and not self.dedup:
+            raise ValueError("build_eval_feed: groups of %d lines need dedup_histories=True" % g)
+        if not query("clsr_feed_build_eval_supported", rc.N, lines.n_keep, k0, n, g, T):
+            raise ValueError("clsr_feed_build_eval: lines %d .. %d + %d of %d in groups of %d (N = %d, T = %d) cannot be "
+                             "built" % (k0, k0, n, lines.n_keep, g, rc.N, T))
+        H, compact = n // g, g > 1
+        if into is None:
+            i32, f32 = torch.int32, torch.float32
+            spec = [("users", (H,), i32), ("items", (n,), i32), ("cates", (n,), i32), ("item_history", (H, T), i32),
+                    ("item_cate_history", (H, T), i32), ("time_from_first_action", (H, T), f32),
+                    ("time_to_now", (H, T), f32), ("labels", (n,), f32)]
+            if compact:
+                spec.append(("users_rows", (n,), i32))
+            spec += [("seq_len", (H,), i32), ("denom", (1,), f32)]
+            lay, off = {}, 0
+            for k, shape, _ in spec:           # (the layout of ``upload``: 16-byte aligned pieces of one arena)
+                nb = 4 * int(np.prod(shape))
+                lay[k] = (off, nb)
+                off += (nb + 15) // 16 * 16
+            dev = torch.empty(off, dtype=torch.uint8, device=self.device)
+            into = {"B": n, "T": T, "compact": compact, "G": g if compact else 0, "_lay": lay, "_nbytes": off, "_dev": dev,
+                    "_desc": None}
+            for k, shape, dt in spec:
+                o, nb = lay[k]
+                into[k] = dev[o:o + nb].view(dt).view(shape)
+        assert into["B"] == n and into["T"] == T and into["G"] == (g if compact else 0)
+        self._last_group = into["G"]
+        ent = into["_desc"]
+        if ent is None or ent[0] is not rc:
+            ent = into["_desc"] = (rc, ops.feed_eval_pointers(rc.dev, {k: into[k] for k in ops.FEED_EVAL_OUTPUTS if k in into}))
+        thr = int(getattr(self.hp, "contrastive_length_threshold", None) or 0)     # (unset for the sibling models)
+        ops.feed_build_eval(ent[1], rc.N, lines.keep_dev, lines.n_keep, k0, n, g, T, thr)
+        return into
+
     # ------------------------------------------------------------------ attention block
     def _att_fwd(self, key, scope, keys, q, Hn, G, T, Dk, Q, seq_len, len_stride, training, q_hist=None):
         P, A0, A1 = self.P, self.A0, self.A1

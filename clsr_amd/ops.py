@@ -413,6 +413,45 @@ def feed_build(ptrs, N, sel, n_sel, src, h0, n, T, G, expanded, thr, err):
          ctypes.addressof(ptrs[1]), err)
 
 
+FEED_EVAL_COLUMNS = FEED_COLUMNS + ("labels",)
+FEED_EVAL_OUTPUTS = ("users", "items", "cates", "item_history", "item_cate_history", "time_from_first_action", "time_to_now",
+                     "labels", "users_rows", "seq_len", "denom")
+
+
+def feed_eval_pointers(cols, outs=None):
+    """The host pointer arrays of clsr_feed_same_rows / clsr_feed_build_eval from dicts of tensors (``FEED_EVAL_COLUMNS``;
+    ``FEED_EVAL_OUTPUTS``, where ``users_rows`` may be missing: a null pointer), dtypes checked as in
+    :func:`feed_pointers`.  ``outs=None``: the column array alone."""
+    f32 = ("time_from_first_action", "time_to_now", "labels", "denom")
+    for d in (cols, outs or {}):
+        for k, t in d.items():
+            want = torch.float32 if k in f32 else torch.int32
+            if not (t.is_cuda and t.is_contiguous() and t.dtype == want):
+                raise TypeError("clsr_feed_build_eval %s: a contiguous %s GPU tensor is required, got %s" % (k, want, t.dtype))
+    cp = (ctypes.c_void_p * len(FEED_EVAL_COLUMNS))(*[cols[k].data_ptr() for k in FEED_EVAL_COLUMNS])
+    if outs is None:
+        return cp
+    missing = [k for k in FEED_EVAL_OUTPUTS if k not in outs and k != "users_rows"]
+    if missing:
+        raise KeyError("clsr_feed_build_eval: no output tensor %s" % ", ".join(missing))
+    return cp, (ctypes.c_void_p * len(FEED_EVAL_OUTPUTS))(*[outs[k].data_ptr() if k in outs else None
+                                                            for k in FEED_EVAL_OUTPUTS])
+
+
+def feed_same_rows(cols_ptrs, N, keep, n_keep, T, flags):
+    """clsr_feed_same_rows: ``flags`` uint8 ``[n_keep]``, 1 where line ``keep[i]`` repeats the history-level columns of
+    ``keep[i - 1]``.  ``keep`` must have been checked against ``[0, N)`` by the caller."""
+    keep_alive(cols_ptrs)
+    call("clsr_feed_same_rows", ctypes.addressof(cols_ptrs), N, keep, n_keep, T, flags)
+
+
+def feed_build_eval(ptrs, N, keep, n_keep, k0, n, g, T, thr):
+    """clsr_feed_build_eval: the one launch that builds the scoring feed of lines ``keep[k0 : k0 + n]`` in groups of ``g``.
+    ``ptrs``: the pair :func:`feed_eval_pointers` returns."""
+    keep_alive(ptrs)
+    call("clsr_feed_build_eval", ctypes.addressof(ptrs[0]), N, keep, n_keep, k0, n, g, T, thr, ctypes.addressof(ptrs[1]))
+
+
 DW_MULTI_MAX = 12
 
 

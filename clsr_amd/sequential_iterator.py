@@ -291,7 +291,7 @@ class SequentialIterator(BaseIterator):
         if batch_num_ngs > 0:
             shuffle_like_random(perm)
         order = perm.copy()
-        keep = order[cols["full_len"][order] >= min_seq_length]
+        keep = self._kept(cols, order, min_seq_length)
         for a in range(0, len(keep), self.batch_size):
             sel = keep[a:a + self.batch_size]
             data = self._convert_rows(cols, sel, batch_num_ngs)
@@ -299,6 +299,23 @@ class SequentialIterator(BaseIterator):
             if isinstance(data, LazyFeed) and data.recipe is not None:
                 feed.recipe, feed._cols = (infile,) + data.recipe, cols
             yield feed if feed else None
+
+    @staticmethod
+    def _kept(cols, order, min_seq_length):
+        return order[cols["full_len"][order] >= min_seq_length]
+
+    def eval_lines(self, infile, min_seq_length=1):
+        """``(cols, keep)``: the column store of ``infile`` and the file lines ``load_data_from_file(infile,
+        batch_num_ngs=0, min_seq_length=...)`` would yield, in its order, ``batch_size`` of them a batch (the order a
+        training pass left behind when the file was trained on).  Read-only: nothing is shuffled, no random number is
+        drawn; a file not seen yet is parsed as ``load_data_from_file`` would parse it."""
+        cols = self._columns.get(infile) if infile in self.iter_data else None
+        if cols is None:
+            cols = self._load_columns(infile)
+        n = len(self.iter_data[infile])
+        perm = self._order.get(infile)
+        order = perm.copy() if perm is not None and len(perm) == n else np.arange(n, dtype=np.int64)
+        return cols, self._kept(cols, order, min_seq_length)
 
     def _load_columns(self, infile):
         """Column store of ``infile``.  Fast path: the native tokenizer (``clsr_host_tsv_parse``: vocabulary look-ups

@@ -77,6 +77,9 @@ def get_flags():
     p.add_argument("--resident_data", type=str2bool, default=False,
                    help="keep the padded columns of the training file in HBM (about N * (16 T + 16) bytes) and gather every "
                         "training batch there; not for NEXTITNET")
+    p.add_argument("--resident_eval", type=str2bool, default=False,
+                   help="keep the padded columns of every validation / test file in HBM (about N * (16 T + 20) bytes, an "
+                        "image of its own) and build the evaluation feeds there; not for NEXTITNET")
     return p.parse_args()
 
 
@@ -111,7 +114,7 @@ def get_model(flags_obj, model_path, summary_path, user_vocab, item_vocab, cate_
         # (NextItNet's feeds carry a target per position and left-padded histories: an iterator of its own)
         iterator = NextItNetIterator if flags_obj.model == "NEXTITNET" else SequentialIterator
         return cls(hparams, iterator, seed=None, device=device, dist=dist, shard_eval=flags_obj.shard_eval,
-                   resident_data=flags_obj.resident_data)
+                   resident_data=flags_obj.resident_data, resident_eval=flags_obj.resident_eval)
     if flags_obj.model != "CLSR":
         raise SystemExit("--model must be CLSR, SLIREC, GRU4REC, DIN, DIEN, A2SVD, CASER, NCF, NEXTITNET or LGN")
     hparams = prepare_hparams(
@@ -131,7 +134,8 @@ def get_model(flags_obj, model_path, summary_path, user_vocab, item_vocab, cate_
     # data parallel: save_model stays on for EVERY rank -- CLSRModel.save_model is collective (rank 0 writes the
     # file atomically, then all ranks pass a barrier), so nobody loads a checkpoint that is still being written
     return CLSRModel(hparams, SASequentialIterator, seed=None, device=device, dist=dist,
-                     shard_eval=flags_obj.shard_eval, resident_data=flags_obj.resident_data)
+                     shard_eval=flags_obj.shard_eval, resident_data=flags_obj.resident_data,
+                     resident_eval=flags_obj.resident_eval)
 
 
 def init_data_parallel(flags_obj):

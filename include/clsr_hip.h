@@ -1228,6 +1228,32 @@ int clsr_feed_build(const void* const* cols_host, long N, const int* sel, long n
 int clsr_feed_clear_error(int* err, void* stream);
 int clsr_feed_error(const int* err, void* stream);
 
+/* ---- evaluation feeds built on the device from a resident column store (csrc/feed.hip, clsr_amd/resident.py): the eight
+ *      columns above plus labels (fp32 [N]) stay in HBM; cols_host is the HOST array of the nine device pointers in that
+ *      order (clsr_feed_same_rows reads the first six).  keep [n_keep] (int32, device): the file lines an evaluation pass
+ *      yields, in its order.  EVERY entry must lie in [0, N): the caller checks keep on the host before it uploads it, the
+ *      kernels use it as an address unchecked.
+ *      clsr_feed_same_rows: flags [n_keep] (uint8).  flags[0] = 0; flags[i] = 1 exactly when lines keep[i] and keep[i - 1]
+ *        agree in users (as the feed carries them, see below), lens and all T words of item_history, item_cate_history,
+ *        time_from_first_action and time_to_now; float words compare as IEEE == does (-0.0 equals 0.0, a NaN equals
+ *        nothing).  A wave per pair, 16-byte words when T % 4 == 0 and the four bases are 16-byte aligned; one launch.
+ *      clsr_feed_build_eval: the feed of lines keep[k0 .. k0 + n) in groups of g consecutive lines with one history.
+ *        outs_host: HOST array of eleven device pointers --
+ *          users [n / g], items [n], cates [n], item_history, item_cate_history (int32 [n / g, T]), time_from_first_action,
+ *          time_to_now (fp32 [n / g, T]), labels (fp32 [n]), users_rows (int32 [n]; may be NULL when g == 1), seq_len
+ *          [n / g], denom [1].
+ *        History-level outputs come from line keep[k0 + h g], line-level outputs from keep[k0 + b]; seq_len = lens;
+ *        denom[0] = g #{h : seq_len[h] > thr}, counted as an integer.  users and users_rows hold (int)(float)id: the host
+ *        feed carries evaluation user ids through a float32 array.  Rows move as in clsr_feed_build.  One launch,
+ *        asynchronous, no atomics on global memory.
+ *      clsr_feed_build_eval_supported: 1 <= N, n_keep < 2^31, 1 <= T <= clsr_feed_build_max_steps(), g >= 1, n >= 1,
+ *        n % g == 0, 0 <= k0, k0 + n <= n_keep, (n / g) T < 2^31; otherwise the entry point returns -1 and launches nothing. */
+int clsr_feed_build_eval_supported(long N, long n_keep, long k0, long n, int g, int T);
+int clsr_feed_same_rows(const void* const* cols_host, long N, const int* keep, long n_keep, int T, unsigned char* flags,
+                        void* stream);
+int clsr_feed_build_eval(const void* const* cols_host, long N, const int* keep, long n_keep, long k0, long n, int g, int T,
+                         int thr, void* const* outs_host, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
