@@ -231,6 +231,10 @@ class SequentialBaseModel(BaseModel):
             raise NotImplementedError(
                 "%s(resident_eval=True): %s converts its batches line by line and keeps no padded column store to hold "
                 "on the device" % (type(self).__name__, type(self.iterator).__name__))
+        if self._resident_eval_flag and getattr(self.iterator, "per_position_targets", False):
+            raise NotImplementedError(
+                "%s(resident_eval=True): evaluation feeds of %s are not built on the device (left-padded columns); "
+                "resident_data=True covers its training feeds" % (type(self).__name__, type(self.iterator).__name__))
         self.keep_prob_train = 1 - np.array(hp.dropout)
         self.keep_prob_test = np.ones_like(hp.dropout)
         self.embedding_keep_prob_train = 1.0 - hp.embedding_dropout
@@ -345,13 +349,17 @@ class SequentialBaseModel(BaseModel):
 
     def _stage_resident(self, feed, lookahead):
         """A training batch given as its recipe -> the device feed, gathered from the file's resident columns by
-        ``clsr_feed_build`` on the compute stream.  Under ``dist`` the rank builds the shard ``dp.shard_feed`` would cut:
+        ``clsr_feed_build`` (``clsr_feed_build_pos`` for NextItNet's ``(sel, psrc)``) on the compute stream.  Under ``dist``
+        the rank builds the shard ``dp.shard_feed`` would cut:
         ``per = n // world`` whole groups from line ``rank * per`` on (``src`` still points into the global batch)."""
-        from clsr_amd.resident import check_recipe
+        from clsr_amd.resident import check_position_recipe, check_recipe
 
         infile, sel, src = feed["_recipe"]
         rc = self._resident.get(infile, feed["_cols"])
-        n = check_recipe(sel, src, rc.N, self.net.G_train)
+        if getattr(self.iterator, "per_position_targets", False):      # (sel, psrc): a target per position
+            n = check_position_recipe(sel, src, rc.N, self.net.G_train, rc.T)
+        else:
+            n = check_recipe(sel, src, rc.N, self.net.G_train)
         h0, per = 0, n
         if self._dist is not None:
             from clsr_amd.dp import DataParallel
@@ -796,7 +804,8 @@ class LGNModel(_SiblingModel):
 
 class NextItNetModel(_SiblingModel):
     """Reference ``NextItNetModel`` (models/sequential/nextitnet.py): hparams ``dilations``, ``kernel_size``; built with
-    ``NextItNetIterator`` (left-padded histories, a target per position in training feeds)."""
+    ``NextItNetIterator`` (left-padded histories, a target per position in training feeds) or, for the same feeds from a
+    column store and a native sampler, ``NextItNetColumnIterator`` (the one ``resident_data=True`` needs)."""
     kind = "nextitnet"
 
 

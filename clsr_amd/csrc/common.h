@@ -138,6 +138,17 @@ __device__ __forceinline__ double block256_sum_d(double v, double* red) {
   return (red[0] + red[1]) + (red[2] + red[3]);
 }
 
+// A share of a REPORTED loss scalar (regulariser, discrepancy term) into its double slot.  Workgroups add their shares in
+// arrival order, and a sum of doubles depends on that order in its last bit.  Every share is therefore rounded to a multiple
+// of 2^-52 first: while the slot (zero at the start of a step, nothing else added to it) stays below 2 in magnitude, every
+// partial sum is k 2^-52 with |k| < 2^53 -- exact in a double -- so the additions commute and two runs of a step report the
+// same bits.  Past 2 the adds round as they always did (a share >= 2 passes through unchanged).  A share moves by at most
+// 1.1e-16.
+__device__ __forceinline__ void loss_add_d(double* slot, double v) {
+  const double q = 4503599627370496.0;   // 2^52
+  atomicAdd(slot, rint(v * q) / q);
+}
+
 // v_rcp_f32 (1 ulp) instead of an IEEE division: the gates of the T-serial recurrences spend most of their
 // VALU time in these two functions
 __device__ __forceinline__ float sigmoidf_(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }

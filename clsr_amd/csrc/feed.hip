@@ -69,29 +69,35 @@ __global__ void __launch_bounds__(1024) feed_check_kernel(FeedArgs d) {
 // W: one 4-byte word or four per access.  A row of T words is contiguous on both sides and consecutive lanes walk
 // consecutive words of it; the four history-level arrays move together (four independent loads in flight per lane).
 template <typename W>
+__device__ __forceinline__ void feed_move_rows(const FeedArgs& d, long nq, int Tq, int big_blocks) {
+  const int G = d.G;
+  const W* __restrict__ c0 = (const W*)d.item_history;
+  const W* __restrict__ c1 = (const W*)d.item_cate_history;
+  const W* __restrict__ c2 = (const W*)d.time_from_first_action;
+  const W* __restrict__ c3 = (const W*)d.time_to_now;
+  W* __restrict__ o0 = (W*)d.out_item_history;
+  W* __restrict__ o1 = (W*)d.out_item_cate_history;
+  W* __restrict__ o2 = (W*)d.out_time_from_first_action;
+  W* __restrict__ o3 = (W*)d.out_time_to_now;
+  for (long q = (long)blockIdx.x * 256 + threadIdx.x; q < nq; q += (long)big_blocks * 256) {
+    const long r = q / Tq;
+    const int c = (int)(q - r * Tq);
+    const long line = d.sel[d.h0 + (d.expanded ? r / G : r)];
+    const long s = line * Tq + c;
+    const W v0 = c0[s], v1 = c1[s], v2 = c2[s], v3 = c3[s];
+    o0[q] = v0;
+    o1[q] = v1;
+    o2[q] = v2;
+    o3[q] = v3;
+  }
+}
+
+template <typename W>
 __global__ void __launch_bounds__(256) feed_build_kernel(FeedArgs d, long nq, int Tq, int big_blocks) {
   if (d.err[FEED_ERR_LAUNCH]) return;
   const int G = d.G;
   if ((int)blockIdx.x < big_blocks) {
-    const W* __restrict__ c0 = (const W*)d.item_history;
-    const W* __restrict__ c1 = (const W*)d.item_cate_history;
-    const W* __restrict__ c2 = (const W*)d.time_from_first_action;
-    const W* __restrict__ c3 = (const W*)d.time_to_now;
-    W* __restrict__ o0 = (W*)d.out_item_history;
-    W* __restrict__ o1 = (W*)d.out_item_cate_history;
-    W* __restrict__ o2 = (W*)d.out_time_from_first_action;
-    W* __restrict__ o3 = (W*)d.out_time_to_now;
-    for (long q = (long)blockIdx.x * 256 + threadIdx.x; q < nq; q += (long)big_blocks * 256) {
-      const long r = q / Tq;
-      const int c = (int)(q - r * Tq);
-      const long line = d.sel[d.h0 + (d.expanded ? r / G : r)];
-      const long s = line * Tq + c;
-      const W v0 = c0[s], v1 = c1[s], v2 = c2[s], v3 = c3[s];
-      o0[q] = v0;
-      o1[q] = v1;
-      o2[q] = v2;
-      o3[q] = v3;
-    }
+    feed_move_rows<W>(d, nq, Tq, big_blocks);
     return;
   }
   const long nrow = d.n * G, row0 = d.h0 * G;
@@ -179,6 +185,223 @@ extern "C" int clsr_feed_build(const void* const* cols_host, long N, const int* 
   return CLSR_OK;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// NextItNet training feeds (NextItNetColumnIterator): a target per position.  The recipe is sel and psrc [n_sel, G - 1, T],
+// the batch line every (line, negative, step) takes its item / category from; the columns are the LEFT-padded ones.
+// The same protocol as above in three launches.  The shard's psrc is n (G - 1) T words (3.3 MB at 4096 x 4 x 50), too many
+// for one workgroup: feed_scan_pos_kernel holds sel and the shard's psrc in slices and leaves the first position that cannot
+// be served per workgroup (plain stores, no atomics on global memory); feed_check_pos_kernel (ONE workgroup) takes their
+// minimum and raises the error words or -- everything passed -- writes denom and the batch's own targets bt[0 .. n_sel) =
+// items[sel], bt[n_sel ..) = cates[sel], which removes one of the two indirections of items[sel[psrc]];
+// feed_build_pos_kernel writes nothing when the status is set.
+enum { FEED_SCAN_PARTS = 1024 };
+
+__global__ void __launch_bounds__(256) feed_scan_pos_kernel(FeedArgs d, int* part) {
+  __shared__ int s_bad;
+  if (threadIdx.x == 0) s_bad = INT_MAX;
+  __syncthreads();
+  const int n_sel = (int)d.n_sel, per = (d.G - 1) * d.T, total = n_sel + (int)(d.n * per);
+  const long p0 = d.h0 * per - n_sel;
+  int bad = INT_MAX;
+  // position of the first index that cannot be served: sel entries first, then the shard's psrc entries (ascending per
+  // thread: the first hit is the thread's lowest)
+  for (long i = blockIdx.x * 256 + threadIdx.x; i < total && bad == INT_MAX; i += gridDim.x * 256) {
+    const bool ok = i < n_sel ? (unsigned)d.sel[i] < (unsigned long)d.N : (unsigned)d.src[p0 + i] < (unsigned)n_sel;
+    if (!ok) bad = (int)i;
+  }
+  if (bad != INT_MAX) atomicMin(&s_bad, bad);
+  __syncthreads();
+  if (threadIdx.x == 0) part[blockIdx.x] = s_bad;
+}
+
+__global__ void __launch_bounds__(1024) feed_check_pos_kernel(FeedArgs d, int* bt, const int* part, int nparts) {
+  __shared__ int s_bad, s_cnt;
+  if (threadIdx.x == 0) {
+    s_bad = INT_MAX;
+    s_cnt = 0;
+  }
+  __syncthreads();
+  const int n_sel = (int)d.n_sel, per = (d.G - 1) * d.T;
+  const long p0 = d.h0 * per;
+  int bad = INT_MAX;
+  for (int b = threadIdx.x; b < nparts; b += 1024) bad = min(bad, part[b]);
+  if (bad != INT_MAX) atomicMin(&s_bad, bad);
+  __syncthreads();
+  bad = s_bad;
+  if (bad != INT_MAX) {
+    if (threadIdx.x == 0) {
+      if (d.err[FEED_ERR_CODE] == 0) {      // sticky: the first failure stays until clsr_feed_clear_error
+        d.err[FEED_ERR_CODE] = bad < n_sel ? 1 : 3;
+        d.err[FEED_ERR_INDEX] = bad < n_sel ? bad : (int)p0 + (bad - n_sel);
+        d.err[FEED_ERR_VALUE] = bad < n_sel ? d.sel[bad] : d.src[p0 + (bad - n_sel)];
+      }
+      d.err[FEED_ERR_LAUNCH] = 1;
+    }
+    return;
+  }
+  for (int i = threadIdx.x; i < n_sel; i += 1024) {
+    const int line = d.sel[i];
+    bt[i] = d.items[line];
+    bt[n_sel + i] = d.cates[line];
+  }
+  int cnt = 0;
+  for (int i = threadIdx.x; i < (int)d.n; i += 1024) cnt += d.lens[d.sel[d.h0 + i]] > d.thr ? 1 : 0;
+  if (cnt) atomicAdd(&s_cnt, cnt);          // integer sum: the value does not depend on the order
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    d.err[FEED_ERR_LAUNCH] = 0;
+    d.out_denom[0] = (float)((long)s_cnt * d.G);
+  }
+}
+
+template <typename W> struct feed_word;
+template <> struct feed_word<unsigned> {
+  static __device__ __forceinline__ unsigned get(unsigned w, int) { return w; }
+  static __device__ __forceinline__ unsigned make(const unsigned* v) { return v[0]; }
+};
+template <> struct feed_word<feed_u32x4> {
+  static __device__ __forceinline__ unsigned get(feed_u32x4 w, int k) { return k == 0 ? w.x : k == 1 ? w.y : k == 2 ? w.z : w.w; }
+  static __device__ __forceinline__ feed_u32x4 make(const unsigned* v) {
+    feed_u32x4 w;
+    w.x = v[0], w.y = v[1], w.z = v[2], w.w = v[3];
+    return w;
+  }
+};
+
+// Blocks [0, big_blocks): the four history arrays (feed_move_rows).  The next tgt_blocks: out_items / out_cates / out_labels
+// [n G, T], a lane per output word W, consecutive lanes on consecutive steps of a row; a negative row reads its psrc row the
+// same way.  The rest: users / seq_len.
+template <typename W>
+__global__ void __launch_bounds__(256) feed_build_pos_kernel(FeedArgs d, const int* __restrict__ bt, long nq, long nqt, int Tq,
+                                                             int big_blocks, int tgt_blocks) {
+  if (d.err[FEED_ERR_LAUNCH]) return;
+  constexpr int WN = (int)(sizeof(W) / 4);
+  const int G = d.G, T = d.T;
+  if ((int)blockIdx.x < big_blocks) {
+    feed_move_rows<W>(d, nq, Tq, big_blocks);
+    return;
+  }
+  if ((int)blockIdx.x < big_blocks + tgt_blocks) {
+    const int* __restrict__ bi = bt;
+    const int* __restrict__ bc = bt + d.n_sel;
+    const W* __restrict__ ps = (const W*)d.src;
+    W* __restrict__ oi = (W*)d.out_items;
+    W* __restrict__ oc = (W*)d.out_cates;
+    W* __restrict__ ol = (W*)d.out_labels;
+    for (long q = (long)(blockIdx.x - big_blocks) * 256 + threadIdx.x; q < nqt; q += (long)tgt_blocks * 256) {
+      const long r = q / Tq;
+      const int t0 = (int)(q - r * Tq) * WN;
+      const long h = r / G;
+      const int g = (int)(r - h * G);
+      unsigned vi[WN], vc[WN], vl[WN];
+      if (g == 0) {
+        // the positive row: the line's history one step on, its target last
+        const long base = (long)d.sel[d.h0 + h] * T;
+#pragma unroll
+        for (int k = 0; k < WN; ++k) {
+          const int t = t0 + k;
+          vi[k] = t == T - 1 ? (unsigned)bi[d.h0 + h] : (unsigned)d.item_history[base + t + 1];
+          vc[k] = t == T - 1 ? (unsigned)bc[d.h0 + h] : (unsigned)d.item_cate_history[base + t + 1];
+          vl[k] = __float_as_uint(1.0f);
+        }
+      } else {
+        const W p = ps[((d.h0 + h) * (G - 1) + (g - 1)) * Tq + (t0 / WN)];
+#pragma unroll
+        for (int k = 0; k < WN; ++k) {
+          const int j = (int)feed_word<W>::get(p, k);
+          vi[k] = (unsigned)bi[j];
+          vc[k] = (unsigned)bc[j];
+          vl[k] = 0u;
+        }
+      }
+      oi[q] = feed_word<W>::make(vi);
+      oc[q] = feed_word<W>::make(vc);
+      ol[q] = feed_word<W>::make(vl);
+    }
+    return;
+  }
+  const long R = d.expanded ? d.n * G : d.n;
+  const long stride = (long)(gridDim.x - big_blocks - tgt_blocks) * 256;
+  for (long b = (long)(blockIdx.x - big_blocks - tgt_blocks) * 256 + threadIdx.x; b < R; b += stride) {
+    const int own = d.sel[d.h0 + (d.expanded ? b / G : b)];
+    d.out_users[b] = d.users[own];
+    d.out_seq_len[b] = d.lens[own];
+  }
+}
+
+extern "C" long clsr_feed_build_pos_scratch_ints(long n_sel) { return n_sel < 0 ? 0 : 2 * n_sel + FEED_SCAN_PARTS; }
+
+extern "C" int clsr_feed_build_pos_supported(long N, long n_sel, int T, int G) {
+  return N >= 1 && N <= INT_MAX && n_sel >= 1 && T >= 1 && T <= clsr_feed_build_max_steps() && G >= 2 &&
+         G <= clsr_feed_build_max_group() && n_sel <= INT_MAX / ((long)G * T) - 1;
+}
+
+extern "C" int clsr_feed_build_pos(const void* const* cols_host, long N, const int* sel, long n_sel, const int* psrc, long h0,
+                                   long n, int T, int G, int expanded, int thr, void* const* outs_host, int* scratch, int* err,
+                                   void* stream) {
+  CLSR_CHECK_ARG(cols_host && outs_host);
+  FeedArgs d;
+  d.item_history = (const int*)cols_host[0];
+  d.item_cate_history = (const int*)cols_host[1];
+  d.time_from_first_action = (const float*)cols_host[2];
+  d.time_to_now = (const float*)cols_host[3];
+  d.lens = (const int*)cols_host[4];
+  d.users = (const int*)cols_host[5];
+  d.items = (const int*)cols_host[6];
+  d.cates = (const int*)cols_host[7];
+  d.sel = sel;
+  d.src = psrc;
+  d.out_users = (int*)outs_host[0];
+  d.out_items = (int*)outs_host[1];
+  d.out_cates = (int*)outs_host[2];
+  d.out_item_history = (int*)outs_host[3];
+  d.out_item_cate_history = (int*)outs_host[4];
+  d.out_time_from_first_action = (float*)outs_host[5];
+  d.out_time_to_now = (float*)outs_host[6];
+  d.out_labels = (float*)outs_host[7];
+  d.out_seq_len = (int*)outs_host[8];
+  d.out_denom = (float*)outs_host[9];
+  d.err = err;
+  d.N = N, d.n_sel = n_sel, d.h0 = h0, d.n = n;
+  d.T = T, d.G = G, d.expanded = expanded, d.thr = thr;
+  CLSR_CHECK_ARG(d.item_history && d.item_cate_history && d.time_from_first_action && d.time_to_now);
+  CLSR_CHECK_ARG(d.lens && d.users && d.items && d.cates && d.sel && d.src && d.err && scratch);
+  CLSR_CHECK_ARG(d.out_users && d.out_items && d.out_cates && d.out_item_history && d.out_item_cate_history);
+  CLSR_CHECK_ARG(d.out_time_from_first_action && d.out_time_to_now && d.out_labels && d.out_seq_len && d.out_denom);
+  CLSR_CHECK_SUPPORTED(clsr_feed_build_pos_supported(d.N, d.n_sel, d.T, d.G));
+  CLSR_CHECK_ARG(d.h0 >= 0 && d.n >= 1 && d.h0 + d.n <= d.n_sel);
+  CLSR_CHECK_ARG(d.expanded == 0 || d.expanded == 1);
+  hipStream_t st = (hipStream_t)stream;
+  int* part = scratch + 2 * d.n_sel;
+  long scan = (d.n_sel + d.n * (d.G - 1) * d.T + 2047) / 2048;      // eight positions a thread
+  if (scan > FEED_SCAN_PARTS) scan = FEED_SCAN_PARTS;
+  hipLaunchKernelGGL(feed_scan_pos_kernel, dim3((int)scan), dim3(256), 0, st, d, part);
+  CLSR_CHECK_LAUNCH();
+  hipLaunchKernelGGL(feed_check_pos_kernel, dim3(1), dim3(1024), 0, st, d, scratch, (const int*)part, (int)scan);
+  CLSR_CHECK_LAUNCH();
+  // 16-byte accesses where every row starts on a 16-byte boundary on every side that is read or written in words of W
+  uintptr_t a = 0;
+  for (const void* p : {(const void*)d.item_history, (const void*)d.item_cate_history, (const void*)d.time_from_first_action,
+                        (const void*)d.time_to_now, (const void*)d.out_item_history, (const void*)d.out_item_cate_history,
+                        (const void*)d.out_time_from_first_action, (const void*)d.out_time_to_now, (const void*)d.src,
+                        (const void*)d.out_items, (const void*)d.out_cates, (const void*)d.out_labels})
+    a |= (uintptr_t)p;
+  const bool wide = d.T % 4 == 0 && a % 16 == 0;
+  const int Tq = wide ? d.T / 4 : d.T;
+  const long nq = d.n * (d.expanded ? d.G : 1) * Tq, nqt = d.n * d.G * Tq;
+  long big = (nq + 255) / 256, tgt = (nqt + 255) / 256, small = (d.n * (d.expanded ? d.G : 1) + 255) / 256;
+  if (big > 16384) big = 16384;
+  if (tgt > 16384) tgt = 16384;
+  if (small > 1024) small = 1024;
+  const dim3 grid((int)(big + tgt + small));
+  if (wide)
+    hipLaunchKernelGGL(feed_build_pos_kernel<feed_u32x4>, grid, dim3(256), 0, st, d, scratch, nq, nqt, Tq, (int)big, (int)tgt);
+  else
+    hipLaunchKernelGGL(feed_build_pos_kernel<unsigned>, grid, dim3(256), 0, st, d, scratch, nq, nqt, Tq, (int)big, (int)tgt);
+  CLSR_CHECK_LAUNCH();
+  return CLSR_OK;
+}
+
 extern "C" int clsr_feed_clear_error(int* err, void* stream) {
   CLSR_CHECK_ARG(err);
   CLSR_HIP(hipMemsetAsync(err, 0, 4 * sizeof(int), (hipStream_t)stream));
@@ -193,8 +416,10 @@ extern "C" int clsr_feed_error(const int* err, void* stream) {
   if (e[FEED_ERR_CODE] == 0) return CLSR_OK;
   if (e[FEED_ERR_CODE] == 1)
     clsr_set_error("clsr_feed_build: sel[%d] = %d is not a line of the resident file", e[FEED_ERR_INDEX], e[FEED_ERR_VALUE]);
-  else
+  else if (e[FEED_ERR_CODE] == 2)
     clsr_set_error("clsr_feed_build: src[%d] = %d is not a line of the batch", e[FEED_ERR_INDEX], e[FEED_ERR_VALUE]);
+  else
+    clsr_set_error("clsr_feed_build_pos: psrc[%d] = %d is not a line of the batch", e[FEED_ERR_INDEX], e[FEED_ERR_VALUE]);
   return CLSR_EINVAL;
 }
 

@@ -230,8 +230,8 @@ __global__ void __launch_bounds__(256) tables_reg_multi_kernel(TablesArgs a) {
   ss = block256_sum_d(ss, red[0]); rl = block256_sum_d(rl, red[1]); dl = block256_sum_d(dl, red[2]);
   if (threadIdx.x == 0) {
     if (ss != 0.0) atomicAdd(d.sumsq_reg, ss);
-    if (a.reg_loss && rl != 0.0) atomicAdd(a.reg_loss, rl);
-    if (d.disc_loss && dl != 0.0) atomicAdd(d.disc_loss, (double)cl * dl);
+    if (a.reg_loss && rl != 0.0) loss_add_d(a.reg_loss, rl);
+    if (d.disc_loss && dl != 0.0) loss_add_d(d.disc_loss, (double)cl * dl);
   }
 }
 
@@ -290,8 +290,8 @@ __global__ void __launch_bounds__(256) tables_reg_multi_v4_kernel(TablesArgs a) 
   ss = wave_sum_d(ss); rl = wave_sum_d(rl); dl = wave_sum_d(dl);
   if ((threadIdx.x & 63) == 0) {
     if (ss != 0.0) atomicAdd(d.sumsq_reg, ss);
-    if (a.reg_loss && rl != 0.0) atomicAdd(a.reg_loss, rl);
-    if (d.disc_loss && dl != 0.0) atomicAdd(d.disc_loss, (double)cl * dl);
+    if (a.reg_loss && rl != 0.0) loss_add_d(a.reg_loss, rl);
+    if (d.disc_loss && dl != 0.0) loss_add_d(d.disc_loss, (double)cl * dl);
   }
 }
 // every table of the launch: rows of 4 k values, 16-byte aligned operands, fewer than 2^31 values

@@ -85,7 +85,7 @@ __global__ void __launch_bounds__(1024) dense_reg_norm_kernel(const float* __res
     double a = 0.0, r = 0.0;
     for (int w = 0; w < BS / 64; ++w) { a += red[0][w]; r += red[1][w]; }
     sumsq[seg] = a;
-    if (reg_loss) atomicAdd(reg_loss, r);
+    if (reg_loss) loss_add_d(reg_loss, r);
   }
 }
 
@@ -219,8 +219,8 @@ __global__ void __launch_bounds__(256) table_reg_kernel(
   ss = block256_sum_d(ss, red[0]); rl = block256_sum_d(rl, red[1]); dl = block256_sum_d(dl, red[2]);
   if (threadIdx.x == 0) {
     if (ss != 0.0) atomicAdd(sumsq, ss);
-    if (reg_loss && rl != 0.0) atomicAdd(reg_loss, rl);
-    if (disc_loss && dl != 0.0) atomicAdd(disc_loss, (double)cl * dl);
+    if (reg_loss && rl != 0.0) loss_add_d(reg_loss, rl);
+    if (disc_loss && dl != 0.0) loss_add_d(disc_loss, (double)cl * dl);
   }
 }
 
@@ -365,8 +365,8 @@ __global__ void __launch_bounds__(256) table_reg_rows_kernel(
   ss = block256_sum_d(ss, red[0]); rl = block256_sum_d(rl, red[1]); dl = block256_sum_d(dl, red[2]);
   if (threadIdx.x == 0) {
     if (ss != 0.0) atomicAdd(sumsq, ss);
-    if (reg_loss && rl != 0.0) atomicAdd(reg_loss, rl);
-    if (disc_loss && dl != 0.0) atomicAdd(disc_loss, (double)cl * dl);
+    if (reg_loss && rl != 0.0) loss_add_d(reg_loss, rl);
+    if (disc_loss && dl != 0.0) loss_add_d(disc_loss, (double)cl * dl);
   }
 }
 

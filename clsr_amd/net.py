@@ -1411,20 +1411,29 @@ class CLSRNet(object):
         :func:`clsr_amd.resident.check_recipe`).  ``h0``, ``n``: the lines of the batch to build (a data-parallel
         rank's shard; default: all).  Only ``sel`` and ``src`` cross PCIe, through a ring of pinned slots like the
         arenas of ``upload``; everything is enqueued on the current stream.  ``into``: an earlier result of the same
-        shape, re-used."""
+        shape, re-used.
+
+        A 3-d ``src`` is the ``psrc`` ``[n_sel, G_train - 1, T]`` of a NextItNet batch
+        (:func:`clsr_amd.resident.check_position_recipe`, ``clsr_feed_build_pos``): ``items`` / ``cates`` ``[n G, T]`` and
+        ``labels`` ``[n G T]`` hold a target per position, and the history-level tensors one row per feed row -- the layout
+        ``upload`` gives the literal feed of ``NextItNetIterator``, which carries no ``hist_group``."""
         G, T = self.G_train, resident.T
         n_sel = int(sel.shape[0])
         n = n_sel - h0 if n is None else int(n)
-        compact = self.dedup
+        pos = src.ndim == 3
+        compact = self.dedup and not pos
         R, B = (n if compact else n * G), n * G
-        if not query("clsr_feed_build_supported", resident.N, n_sel, T, G):
-            raise NotImplementedError("clsr_feed_build: N = %d, batch of %d lines, T = %d, G = %d is not supported"
-                                      % (resident.N, n_sel, T, G))
+        entry = "clsr_feed_build_pos" if pos else "clsr_feed_build"
+        if not query(entry + "_supported", resident.N, n_sel, T, G):
+            raise NotImplementedError("%s: N = %d, batch of %d lines, T = %d, G = %d is not supported"
+                                      % (entry, resident.N, n_sel, T, G))
         if into is None:
             i32, f32 = torch.int32, torch.float32
-            spec = (("users", (R,), i32), ("items", (B,), i32), ("cates", (B,), i32), ("item_history", (R, T), i32),
+            per = (B, T) if pos else (B,)
+            spec = (("users", (R,), i32), ("items", per, i32), ("cates", per, i32), ("item_history", (R, T), i32),
                     ("item_cate_history", (R, T), i32), ("time_from_first_action", (R, T), f32),
-                    ("time_to_now", (R, T), f32), ("labels", (B,), f32), ("seq_len", (R,), i32), ("denom", (1,), f32))
+                    ("time_to_now", (R, T), f32), ("labels", (int(np.prod(per)),), f32), ("seq_len", (R,), i32),
+                    ("denom", (1,), f32))
             lay, off = {}, 0
             for k, shape, _ in spec:           # (the layout of ``upload``: 16-byte aligned pieces of one arena)
                 nb = 4 * int(np.prod(shape))
@@ -1440,13 +1449,14 @@ class CLSRNet(object):
         assert into["B"] == B and into["T"] == T and into["compact"] == compact
         self._last_group = into["G"]
         src_off = (4 * n_sel + 15) // 16 * 16
-        nbytes = src_off + (4 * n_sel * G + 15) // 16 * 16
+        nbytes = src_off + (src.nbytes + 15) // 16 * 16
+        scratch = 4 * query("clsr_feed_build_pos_scratch_ints", n_sel) if pos else 0      # (device only, never staged)
         if nbytes > into["_rcap"]:
             for st in into["_rstage"]:      # (a pinned slot a queued kernel still reads is not let go of)
                 if st is not None and st[1] is not None:
                     st[1].synchronize()
             into["_rcap"], into["_rstage"], into["_desc"] = nbytes, [None] * self._STAGE_SLOTS, None
-            into["_rdev"] = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+            into["_rdev"] = torch.empty(nbytes + scratch, dtype=torch.uint8, device=self.device)
         slot = into["_rslot"]
         into["_rslot"] = (slot + 1) % self._STAGE_SLOTS
         if into["_rstage"][slot] is None:
@@ -1456,7 +1466,7 @@ class CLSRNet(object):
         if ev is not None:
             ev.synchronize()
         np.copyto(pin_np[:4 * n_sel], sel.view(np.uint8))
-        np.copyto(pin_np[src_off:src_off + 4 * n_sel * G], src.reshape(-1).view(np.uint8))
+        np.copyto(pin_np[src_off:src_off + src.nbytes], src.reshape(-1).view(np.uint8))
         rdev = into["_rdev"]
         call("clsr_stage_feed", rdev, pin.data_ptr(), nbytes)
         ev = torch.cuda.Event()
@@ -1466,8 +1476,12 @@ class CLSRNet(object):
         if ent is None or ent[0] is not resident:
             ent = into["_desc"] = (resident, ops.feed_pointers(resident.dev, {k: into[k] for k in ops.FEED_OUTPUTS}))
         thr = int(getattr(self.hp, "contrastive_length_threshold", None) or 0)     # (unset for the sibling models)
-        ops.feed_build(ent[1], resident.N, rdev.data_ptr(), n_sel, rdev.data_ptr() + src_off, int(h0), n, T, G,
-                       not compact, thr, resident.err)
+        if pos:
+            ops.feed_build_pos(ent[1], resident.N, rdev.data_ptr(), n_sel, rdev.data_ptr() + src_off, int(h0), n, T, G,
+                               not compact, thr, rdev.data_ptr() + into["_rcap"], resident.err)
+        else:
+            ops.feed_build(ent[1], resident.N, rdev.data_ptr(), n_sel, rdev.data_ptr() + src_off, int(h0), n, T, G,
+                           not compact, thr, resident.err)
         return into
 
     def build_eval_feed(self, lines, k0, n, g, into=None):

@@ -413,6 +413,15 @@ def feed_build(ptrs, N, sel, n_sel, src, h0, n, T, G, expanded, thr, err):
          ctypes.addressof(ptrs[1]), err)
 
 
+def feed_build_pos(ptrs, N, sel, n_sel, psrc, h0, n, T, G, expanded, thr, scratch, err):
+    """clsr_feed_build_pos: the three launches that build (lines h0 .. h0 + n - 1 of) a NextItNet training feed from
+    resident columns.  ``ptrs``: the result of :func:`feed_pointers`; ``sel`` / ``psrc`` / ``scratch``
+    (``clsr_feed_build_pos_scratch_ints(n_sel)`` ints): int32 tensors or device addresses."""
+    keep_alive(ptrs)
+    call("clsr_feed_build_pos", ctypes.addressof(ptrs[0]), N, sel, n_sel, psrc, h0, n, T, G, int(expanded), thr,
+         ctypes.addressof(ptrs[1]), scratch, err)
+
+
 FEED_EVAL_COLUMNS = FEED_COLUMNS + ("labels",)
 FEED_EVAL_OUTPUTS = ("users", "items", "cates", "item_history", "item_cate_history", "time_from_first_action", "time_to_now",
                      "labels", "users_rows", "seq_len", "denom")

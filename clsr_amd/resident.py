@@ -5,8 +5,10 @@
 ``resident_data=True`` a model keeps the columns the step reads in HBM -- ``item_history``, ``item_cate_history``,
 ``time_from_first_action``, ``time_to_now`` ``[N, T]`` and ``lens``, ``users``, ``items``, ``cates`` ``[N]``, 4-byte words all:
 ``N * (16 T + 16)`` bytes -- and ``clsr_feed_build`` (csrc/feed.hip) gathers the batch there; only ``sel`` and ``src`` cross
-PCIe.  The image is uploaded once per cached file and again when the iterator re-parses the file (its column dict is a new
-object then).  A failed allocation surfaces as torch raises it.
+PCIe.  ``NextItNetColumnIterator`` keeps the same columns left-padded; its recipe is ``(sel, psrc)``
+(:func:`check_position_recipe`) and ``clsr_feed_build_pos`` builds its batches.  The image is uploaded once per cached file
+and again when the iterator re-parses the file (its column dict is a new object then).  A failed allocation surfaces as
+torch raises it.
 
 ``resident_eval=True`` is a separate switch with a store of its own (:class:`ResidentEvalStore`): per evaluated file the
 same columns plus ``labels``, ``N * (16 T + 20)`` bytes, and per ``min_seq_length`` the list ``keep`` of the lines a pass
@@ -17,8 +19,8 @@ builds each chunk's feed from ``(k0, n, g)``.  A file that is trained on and eva
 import numpy as np
 import torch
 
-__all__ = ["ResidentColumns", "ResidentStore", "check_recipe", "COLUMNS", "ResidentEvalColumns", "ResidentEvalStore",
-           "EvalLines", "same_rows", "eval_chunk_plan"]
+__all__ = ["ResidentColumns", "ResidentStore", "check_recipe", "check_position_recipe", "COLUMNS", "ResidentEvalColumns",
+           "ResidentEvalStore", "EvalLines", "same_rows", "eval_chunk_plan"]
 
 _BIG = (("item_history", np.int32), ("item_cate_history", np.int32), ("time_from_first_action", np.float32),
         ("time_to_now", np.float32))
@@ -43,6 +45,26 @@ def check_recipe(sel, src, N, G):
         raise ValueError("recipe src: batch positions must lie in [0, %d) (min %d, max %d)" % (n, src.min(), src.max()))
     if not np.array_equal(src[:, 0], np.arange(n, dtype=np.int32)):
         raise ValueError("recipe src: column 0 must be the line itself")
+    return n
+
+
+def check_position_recipe(sel, psrc, N, G, T):
+    """The recipe of a NextItNet training feed (``NextItNetColumnIterator``): ``sel`` int32 ``[n]`` line numbers in
+    ``[0, N)``, ``psrc`` int32 ``[n, G - 1, T]`` batch positions in ``[0, n)`` -- the line whose (item, cate) negative row
+    ``g + 1`` of line ``i`` carries at step ``t``.  Raises TypeError / ValueError; returns ``n``."""
+    for name, a, nd in (("sel", sel, 1), ("psrc", psrc, 3)):
+        if not isinstance(a, np.ndarray) or a.dtype != np.int32:
+            raise TypeError("recipe %s: an int32 numpy array is required, got %s" % (name, getattr(a, "dtype", type(a))))
+        if a.ndim != nd or not a.flags.c_contiguous:
+            raise ValueError("recipe %s: a contiguous %d-d array is required (shape %r)" % (name, nd, a.shape))
+    n = sel.shape[0]
+    if n < 1 or G < 2 or psrc.shape != (n, G - 1, T):
+        raise ValueError("recipe: sel %r and psrc %r do not describe a batch of groups of %d over %d steps"
+                         % (sel.shape, psrc.shape, G, T))
+    if int(sel.min()) < 0 or int(sel.max()) >= N:
+        raise ValueError("recipe sel: line numbers must lie in [0, %d) (min %d, max %d)" % (N, sel.min(), sel.max()))
+    if int(psrc.min()) < 0 or int(psrc.max()) >= n:
+        raise ValueError("recipe psrc: batch positions must lie in [0, %d) (min %d, max %d)" % (n, psrc.min(), psrc.max()))
     return n
 
 
@@ -197,8 +219,10 @@ class ResidentEvalStore(object):
     iterator's list of lines differs from the cached one (a training pass over the same file shuffled it)."""
 
     def __init__(self, iterator, device):
-        if not hasattr(iterator, "eval_lines") or not getattr(iterator, "lazy_histories", False):
-            raise NotImplementedError("resident_eval: %s keeps no padded column store" % type(iterator).__name__)
+        if (not hasattr(iterator, "eval_lines") or not getattr(iterator, "lazy_histories", False)
+                or getattr(iterator, "per_position_targets", False)):       # (NextItNet: out of this store's scope)
+            raise NotImplementedError("resident_eval: %s keeps no padded column store evaluation feeds are built from"
+                                      % type(iterator).__name__)
         self.iterator, self.device, self.files, self.uploads = iterator, device, {}, 0
 
     def get(self, infile, min_seq_length=1, flags=True):

@@ -22,7 +22,7 @@ import numpy as np
 
 from clsr_amd.deeprec_utils import load_dict
 
-__all__ = ["BaseIterator", "SequentialIterator", "SASequentialIterator", "NextItNetIterator"]
+__all__ = ["BaseIterator", "SequentialIterator", "SASequentialIterator", "NextItNetIterator", "NextItNetColumnIterator"]
 
 _FIELDS = (
     "labels users items cates item_history item_cate_history mask time time_diff "
@@ -115,6 +115,8 @@ class LazyFeed(dict):
     #: ``(file, sel, src)`` of a training feed drawn from a column store: ``sel`` int32 ``[n]``, the file lines of the batch
     #: in batch order; ``src`` int32 ``[n, 1 + ngs]``, the batch line whose (item, cate) every output row carries.  Together
     #: with the file's columns (``_cols``) that is the whole batch: clsr_amd/resident.py rebuilds the feed on the device.
+    #: (``NextItNetColumnIterator``: ``(file, sel, psrc)``, ``psrc`` int32 ``[n, ngs, T]`` -- the batch line whose (item, cate)
+    #: negative row ``g + 1`` of line ``i`` carries at step ``t``.)
     recipe = None
     _cols = None
 
@@ -814,3 +816,107 @@ class NextItNetIterator(SequentialIterator):
         res["users"] = np.repeat(np.asarray(user_list, dtype=np.int32), G)
         res["time"] = np.repeat(np.asarray(time_list, dtype=np.float32), G)
         return res
+
+
+class NextItNetColumnIterator(NextItNetIterator):
+    """The feeds of :class:`NextItNetIterator`, array for array, from a per-file column store: every line is padded once
+    (left padding: the most recent action at step ``T - 1``), an evaluation batch is a row gather, and the per-position
+    negative sampling of a training batch replays the ``random`` module's stream natively
+    (``clsr_host_mt_sample_negatives_pos``: the draws, their order and the state ``random`` is left in are the literal
+    loop's).  A training feed is a :class:`LazyFeed` with every array deferred -- work proportional to ``n * G * T`` is left to
+    whoever reads it -- that carries the recipe ``(file, sel, psrc)`` and its column dict, from which
+    ``clsr_feed_build_pos`` rebuilds the batch on the device (clsr_amd/resident.py).  Without the native library, with a
+    ``random`` state that is not version 3, or for a batch the native sampler refuses, the draws are ``random.randint``
+    calls in the literal order."""
+
+    lazy_histories = True
+    #: ``items`` / ``cates`` / ``labels`` of a training feed hold a target per position and its recipe is
+    #: ``(file, sel, psrc)``: the consumers of ``(file, sel, src)`` recipes and of evaluation column stores ask for this
+    per_position_targets = True
+
+    _BIG = ("item_history", "item_cate_history", "mask", "time_diff", "time_from_first_action", "time_to_now")
+
+    def _load_columns(self, infile):
+        self._columns.pop(infile, None)
+        left = SequentialIterator._load_columns(self, infile)       # left ALIGNED: the history starts at step 0
+        T = self.max_seq_length
+        lens = np.asarray(left["lens"])
+        at = np.arange(T)[None, :] - (T - lens[:, None])            # the left-aligned step every padded step shows
+        cols = dict(left)
+        for k in self._BIG:
+            a = np.take_along_axis(left[k], np.maximum(at, 0), axis=1)
+            a[at < 0] = 0
+            cols[k] = a
+        self._columns[infile] = cols
+        return cols
+
+    def _convert_rows(self, cols, sel, batch_num_ngs):
+        n = len(sel)
+        if batch_num_ngs and n < 5:
+            return None
+        if not batch_num_ngs:
+            res = {k: cols[k][sel] for k in self._BIG}
+            res["labels"] = cols["labels"][sel].reshape(-1, 1)
+            res["users"] = cols["users"][sel].astype(np.float32)
+            res["items"] = cols["items"][sel].reshape(-1, 1)
+            res["cates"] = cols["cates"][sel].reshape(-1, 1)
+            res["time"] = cols["time"][sel]
+            return res
+        G, T = batch_num_ngs + 1, self.max_seq_length
+        items, cates = cols["items"][sel], cols["cates"][sel]
+        # the positive rows: the history one step on, the instance's target last
+        pos = np.concatenate((cols["item_history"][sel][:, 1:], items[:, None]), axis=1)
+        psrc = self._sample_positions(items, pos, batch_num_ngs)
+        rows = np.repeat(sel, G)
+
+        def targets(own, positive):
+            out = np.empty((n, G, T), dtype=np.int32)
+            out[:, 0], out[:, 1:] = positive, own[psrc]
+            return out.reshape(n * G, T)
+
+        def labels():
+            out = np.zeros((n, G, T), dtype=np.float32)
+            out[:, 0] = 1.0
+            return out.reshape(n * G, T)
+
+        thunks = {k: (lambda k=k: cols[k][rows]) for k in self._BIG}
+        thunks["items"] = lambda: targets(items, pos)
+        thunks["cates"] = lambda: targets(cates, np.concatenate((cols["item_cate_history"][sel][:, 1:], cates[:, None]),
+                                                               axis=1))
+        thunks["labels"] = labels
+        thunks["users"] = lambda: cols["users"][rows]
+        thunks["time"] = lambda: cols["time"][rows]
+        out = LazyFeed({}, thunks, None)
+        out.recipe = (np.ascontiguousarray(sel, dtype=np.int32), psrc)
+        return out
+
+    def _sample_positions(self, items, pos, batch_num_ngs):
+        """``psrc`` int32 ``[n, ngs, T]`` with the literal loop's draws (``NextItNetIterator._convert_data``): line ``i``,
+        negative ``g``, step ``t`` in that order, ``j = randint(0, n - 1)`` redrawn while ``items[j] == pos[i, t]``."""
+        n, T = pos.shape
+        psrc = np.empty((n, batch_num_ngs, T), dtype=np.int32)
+        lib, st = _native_lib(), _mt_state()
+        if (lib is not None and hasattr(lib, "clsr_host_mt_sample_negatives_pos") and st is not None
+                and 2 <= n < (1 << 31)):
+            import ctypes
+
+            key, p, gauss = st
+            cpos = ctypes.c_int(p)
+            items = np.ascontiguousarray(items, dtype=np.int32)
+            pos = np.ascontiguousarray(pos, dtype=np.int32)
+            rc = lib.clsr_host_mt_sample_negatives_pos(key.ctypes.data, ctypes.byref(cpos), items.ctypes.data,
+                                                       pos.ctypes.data, n, batch_num_ngs, T, psrc.ctypes.data)
+            if rc == 0:
+                _mt_restore(key, cpos.value, gauss)
+                return psrc
+            # (refused, state untouched: a position no line of the batch can serve -- the literal loop never ends on it)
+        randint, item_list, hi = random.randint, items.tolist(), n - 1
+        for i in range(n):
+            own = pos[i].tolist()
+            for g in range(batch_num_ngs):
+                for t in range(T):
+                    j = randint(0, hi)
+                    while item_list[j] == own[t]:
+                        j = randint(0, hi)
+                    psrc[i, g, t] = j
+        return psrc

@@ -24,7 +24,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from clsr_amd.clsr import (A2SVDModel, CaserModel, CLSRModel, DIENModel, DINModel, GRU4RecModel,  # noqa: E402
                            LGNModel, NCFModel, NextItNetModel, SLI_RECModel, latest_checkpoint)  # noqa: E402
 from clsr_amd.deeprec_utils import prepare_hparams  # noqa: E402
-from clsr_amd.sequential_iterator import NextItNetIterator, SASequentialIterator, SequentialIterator  # noqa: E402
+from clsr_amd.sequential_iterator import (NextItNetColumnIterator, NextItNetIterator, SASequentialIterator,  # noqa: E402
+                                           SequentialIterator)
 
 YAML = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "clsr_amd", "config", "clsr.yaml")
 
@@ -76,7 +77,8 @@ def get_flags():
                    help="data parallel only: the ranks share validation / test (same metrics, to the bit)")
     p.add_argument("--resident_data", type=str2bool, default=False,
                    help="keep the padded columns of the training file in HBM (about N * (16 T + 16) bytes) and gather every "
-                        "training batch there; not for NEXTITNET")
+                        "training batch there (NEXTITNET: with NextItNetColumnIterator, the same feeds from a column "
+                        "store and a native sampler)")
     p.add_argument("--resident_eval", type=str2bool, default=False,
                    help="keep the padded columns of every validation / test file in HBM (about N * (16 T + 20) bytes, an "
                         "image of its own) and build the evaluation feeds there; not for NEXTITNET")
@@ -112,7 +114,9 @@ def get_model(flags_obj, model_path, summary_path, user_vocab, item_vocab, cate_
         if dist is not None and dist.get_rank() != 0:
             hparams.save_model = False
         # (NextItNet's feeds carry a target per position and left-padded histories: an iterator of its own)
-        iterator = NextItNetIterator if flags_obj.model == "NEXTITNET" else SequentialIterator
+        iterator = SequentialIterator
+        if flags_obj.model == "NEXTITNET":
+            iterator = NextItNetColumnIterator if flags_obj.resident_data else NextItNetIterator
         return cls(hparams, iterator, seed=None, device=device, dist=dist, shard_eval=flags_obj.shard_eval,
                    resident_data=flags_obj.resident_data, resident_eval=flags_obj.resident_eval)
     if flags_obj.model != "CLSR":

@@ -1199,6 +1199,15 @@ int clsr_eval_finalize(void* acc, int n, int scale, void* stream);
  *      612-634, bit-identically, and hand the advanced state back (key[624], *pos). */
 int clsr_host_mt_shuffle(unsigned* key, int* pos, long* perm, long n);
 int clsr_host_mt_sample_negatives(unsigned* key, int* pos, const long* items, long n, int ngs, long* src);
+/* NextItNet's per-position form (io/nextitnet_iterator.py): line i, negative g = 1 .. ngs, step t = 0 .. T - 1 in that order,
+ * j = randint(0, n - 1) redrawn while items[j] == pos_rows[i T + t]; psrc [n, ngs, T] (int32) = the accepted batch positions.
+ * items [n] (int32): the targets of the batch; pos_rows [n, T] (int32): the positive row of every line -- its left-padded
+ * history one step on, the target last, padding zeros included (so a target with id 0 is rejected at padded steps).
+ * 2 <= n < 2^31.  A batch with a position that no line can serve (the reference never ends on it) is found BEFORE the
+ * first draw: CLSR_HOST_MT_NO_DRAW is returned and key, *pos and psrc are untouched. */
+#define CLSR_HOST_MT_NO_DRAW 1
+int clsr_host_mt_sample_negatives_pos(unsigned* key, int* pos, const int* items, const int* pos_rows, long n, int ngs, int T,
+                                      int* psrc);
 
 /* ---- training feeds built on the device from a resident column store (csrc/feed.hip, clsr_amd/resident.py): the padded
  *      per-line columns of a file stay in HBM -- item_history, item_cate_history (int32 [N, T]), time_from_first_action,
@@ -1227,6 +1236,30 @@ int clsr_feed_build(const void* const* cols_host, long N, const int* sel, long n
                     int G, int expanded, int thr, void* const* outs_host, int* err, void* stream);
 int clsr_feed_clear_error(int* err, void* stream);
 int clsr_feed_error(const int* err, void* stream);
+
+/* ---- NextItNet training feeds from a resident column store (a target per position; NextItNetColumnIterator): the columns
+ *      are the LEFT-padded ones (the most recent action at step T - 1), the recipe is sel [n_sel] and psrc [n_sel, G - 1, T]
+ *      (int32 positions inside the GLOBAL batch: the line whose item / category row h G + g carries at step t, g >= 1).
+ *      cols_host / outs_host / h0 / n / expanded / thr / err as for clsr_feed_build; the layout is what CLSRNet.upload gives
+ *      the literal feed of NextItNetIterator:
+ *        out_items / out_cates [n G, T]: row h G = the row sel[h0 + h] of item_history / item_cate_history one step on with
+ *          items / cates [sel[h0 + h]] at step T - 1; row h G + g at step t = items / cates [sel[psrc[h0 + h, g - 1, t]]];
+ *        out_labels [n G, T] = 1 on the whole row h G (padding included), else 0;
+ *        the four history arrays, out_users, out_seq_len, out_denom as clsr_feed_build writes them.
+ *      scratch: clsr_feed_build_pos_scratch_ints(n_sel) ints on the device (the batch's own targets, items[sel] then
+ *      cates[sel], written once every index passed, and a word per workgroup of the scan).  A lane per output word,
+ *      consecutive lanes on consecutive steps of a row; 16-byte words when T % 4 == 0 and psrc and the eleven [., T]
+ *      pointers are 16-byte aligned, 4-byte words otherwise.
+ *      Three launches, asynchronous, no atomics on global memory.  The first two (a scan in slices, then one workgroup)
+ *      hold every sel against N and every psrc of the shard (lines h0 .. h0 + n - 1; psrc outside the shard is not read)
+ *      against n_sel: a value that cannot be served raises err as in clsr_feed_build (code 3: psrc, index into the whole
+ *      psrc array; of several the first, sel before psrc) and the call writes NOTHING to the outputs.
+ *      clsr_feed_build_pos_supported: 1 <= N < 2^31, 1 <= T <= clsr_feed_build_max_steps(), 2 <= G <=
+ *      clsr_feed_build_max_group(), (n_sel + 1) G T < 2^31; otherwise -3 from the entry point, nothing launched. */
+int clsr_feed_build_pos_supported(long N, long n_sel, int T, int G);
+long clsr_feed_build_pos_scratch_ints(long n_sel);
+int clsr_feed_build_pos(const void* const* cols_host, long N, const int* sel, long n_sel, const int* psrc, long h0, long n,
+                        int T, int G, int expanded, int thr, void* const* outs_host, int* scratch, int* err, void* stream);
 
 /* ---- evaluation feeds built on the device from a resident column store (csrc/feed.hip, clsr_amd/resident.py): the eight
  *      columns above plus labels (fp32 [N]) stay in HBM; cols_host is the HOST array of the nine device pointers in that

@@ -22,12 +22,17 @@ import torch  # noqa: E402
 
 import clsr_amd.clsr as M  # noqa: E402
 from clsr_amd.deeprec_utils import prepare_hparams  # noqa: E402
-from clsr_amd.sequential_iterator import SASequentialIterator, SequentialIterator  # noqa: E402
+from clsr_amd.sequential_iterator import (NextItNetColumnIterator, NextItNetIterator, SASequentialIterator,  # noqa: E402
+                                           SequentialIterator)
 from clsr_amd.synthetic import make_tsv_dataset  # noqa: E402
 
 MODELS = {"clsr": ("CLSRModel", "clsr.yaml", SASequentialIterator), "a2svd": ("A2SVDModel", "asvd.yaml", SequentialIterator),
           "gru4rec": ("GRU4RecModel", "gru4rec.yaml", SequentialIterator), "ncf": ("NCFModel", "ncf.yaml", SequentialIterator),
-          "lgn": ("LGNModel", "lgn.yaml", SequentialIterator)}
+          "lgn": ("LGNModel", "lgn.yaml", SequentialIterator),
+          # NextItNet: the column iterator (host feeds, or --resident_data) and the literal one (host feeds only; its
+          # per-position sampler is a python loop of 0.4 - 0.8 s per batch: --n_train 16384 --regions 3 --epochs 1)
+          "nextitnet": ("NextItNetModel", "nextitnet.yaml", NextItNetColumnIterator),
+          "nextitnet_literal": ("NextItNetModel", "nextitnet.yaml", NextItNetIterator)}
 
 
 def _stats(xs):
@@ -130,7 +135,7 @@ def main():
                 e1.record()
                 e1.synchronize()
                 build_us.append(1e3 * e0.elapsed_time(e1) / 20)
-        out["build_feed_device_us_per_batch"] = _stats(build_us[1:])     # (recipe copy + check + gather: 3 launches)
+        out["build_feed_device_us_per_batch"] = _stats(build_us[1:])     # (recipe copy + check + gather)
     print(json.dumps(out))
 
 
