@@ -321,14 +321,28 @@ class SequentialBaseModel(BaseModel):
                 return key, st, True
             return key, self.net.upload(feed, training, into=st), False
         side = self.net._side_stream("@dw0")
-        st = self._static.get(("2x",) + key)
+        pair, i = self._next_of_two(key)
+        fresh = pair[i] is None
+        pair[i] = self.net.upload(feed, training, into=pair[i], copy_stream=side)
+        return key, pair[i], fresh
+
+    def _next_of_two(self, key):
+        """The two device feeds of ``key`` that a lookahead loop fills in turn, and which of them is due."""
+        key = ("2x",) + key
+        st = self._static.get(key)
         if st is None:
-            st = self._static[("2x",) + key] = [[None, None], 0]
+            st = self._static[key] = [[None, None], 0]
         i = st[1]
         st[1] ^= 1
-        fresh = st[0][i] is None
-        st[0][i] = self.net.upload(feed, training, into=st[0][i], copy_stream=side)
-        return key, st[0][i], fresh
+        return st[0], i
+
+    def _data_parallel(self):
+        """The :class:`clsr_amd.dp.DataParallel` of a model trained under ``dist``, made on first use."""
+        if self._dp is None:
+            from clsr_amd.dp import DataParallel
+
+            self._dp = DataParallel(self.net, self._dist, sync_bn=self._sync_bn, group=self._group)
+        return self._dp
 
     @staticmethod
     def _mark_free(f):
@@ -362,26 +376,19 @@ class SequentialBaseModel(BaseModel):
             n = check_recipe(sel, src, rc.N, self.net.G_train)
         h0, per = 0, n
         if self._dist is not None:
-            from clsr_amd.dp import DataParallel
-
-            if self._dp is None:
-                self._dp = DataParallel(self.net, self._dist, sync_bn=self._sync_bn, group=self._group)
-            per = n // self._dp.world
+            dp = self._data_parallel()
+            per = n // dp.world
             if per == 0:
-                raise ValueError("global batch of %d positives cannot feed %d ranks" % (n, self._dp.world))
-            h0 = self._dp.rank * per
+                raise ValueError("global batch of %d positives cannot feed %d ranks" % (n, dp.world))
+            h0 = dp.rank * per
         key = ("resident", per, rc.T, True, self.net.G_train)
         if not lookahead:
             f = self._static[key] = self.net.build_feed(rc, sel, src, h0, per, into=self._static.get(key))
             return key, f
         # two arenas filled in turn: batch N + 1 is built (same stream, a few microseconds) before step N is launched
-        st = self._static.get(("2x",) + key)
-        if st is None:
-            st = self._static[("2x",) + key] = [[None, None], 0]
-        i = st[1]
-        st[1] ^= 1
-        st[0][i] = self.net.build_feed(rc, sel, src, h0, per, into=st[0][i])
-        return key, st[0][i]
+        pair, i = self._next_of_two(key)
+        pair[i] = self.net.build_feed(rc, sel, src, h0, per, into=pair[i])
+        return key, pair[i]
 
     def check_resident(self):
         """Raise if ``clsr_feed_build`` refused a batch since the last call (an index outside the file or the batch; the
@@ -397,11 +404,10 @@ class SequentialBaseModel(BaseModel):
             if "_recipe" in feed:
                 return self._stage_resident(feed, lookahead and not self._use_graph)
             if self._dist is not None:
-                from clsr_amd.dp import DataParallel, shard_feed
+                from clsr_amd.dp import shard_feed
 
-                if self._dp is None:
-                    self._dp = DataParallel(self.net, self._dist, sync_bn=self._sync_bn, group=self._group)
-                feed = shard_feed(feed, self._dp.rank, self._dp.world, self.train_num_ngs + 1)
+                dp = self._data_parallel()
+                feed = shard_feed(feed, dp.rank, dp.world, self.train_num_ngs + 1)
             key, f, _ = self._static_feed(feed, True, lookahead=lookahead and not self._use_graph)
             return key, f
 

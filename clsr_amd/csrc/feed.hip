@@ -13,21 +13,102 @@
 
 #include <limits.h>
 
+#include <initializer_list>
+
 typedef unsigned feed_u32x4 __attribute__((ext_vector_type(4)));
 
-// the arguments of one call as the kernels take them (by value)
-struct FeedArgs {
+// the resident columns of a file (labels: evaluation stores only) and the tensors of a feed, as the kernels take them
+struct FeedCols {
   const int* item_history; const int* item_cate_history; const float* time_from_first_action; const float* time_to_now;
-  const int* lens; const int* users; const int* items; const int* cates;
-  const int* sel; const int* src;
+  const int* lens; const int* users; const int* items; const int* cates; const float* labels;
+};
+struct FeedOuts {
   int* out_users; int* out_items; int* out_cates; int* out_item_history; int* out_item_cate_history;
-  float* out_time_from_first_action; float* out_time_to_now; float* out_labels; int* out_seq_len; float* out_denom;
+  float* out_time_from_first_action; float* out_time_to_now; float* out_labels; int* out_users_rows; int* out_seq_len;
+  float* out_denom;
+};
+
+// the arguments of one call as the kernels take them (by value)
+struct FeedArgs : FeedCols, FeedOuts {
+  const int* sel; const int* src;
   int* err;
   long N, n_sel, h0, n;
   int T, G, expanded, thr;
 };
 
+// The first ncols entries of a host column array (include/clsr_hip.h has the order) -> c; false if one is null.
+static bool feed_cols(FeedCols& c, const void* const* p, int ncols) {
+  const void* v[9] = {};
+  bool ok = p != nullptr;
+  for (int i = 0; ok && i < ncols; ++i) ok = (v[i] = p[i]) != nullptr;
+  c = {(const int*)v[0], (const int*)v[1], (const float*)v[2], (const float*)v[3], (const int*)v[4],
+       (const int*)v[5], (const int*)v[6], (const int*)v[7], (const float*)v[8]};
+  return ok;
+}
+
+// A host output array -> o: the ten tensors of a training feed, or (rows) the eleven of an evaluation feed, whose
+// users_rows may be null (a g == 1 feed has no such tensor); false if another one is null.
+static bool feed_outs(FeedOuts& o, void* const* p, bool rows) {
+  if (!p) return false;
+  o = {(int*)p[0], (int*)p[1], (int*)p[2], (int*)p[3], (int*)p[4], (float*)p[5], (float*)p[6], (float*)p[7],
+       rows ? (int*)p[8] : nullptr, (int*)p[rows ? 9 : 8], (float*)p[rows ? 10 : 9]};
+  return o.out_users && o.out_items && o.out_cates && o.out_item_history && o.out_item_cate_history &&
+         o.out_time_from_first_action && o.out_time_to_now && o.out_labels && o.out_seq_len && o.out_denom;
+}
+
+// 16-byte accesses where every row of T words starts on a 16-byte boundary on every side that is read or written in words
+// of W (T = 50 does not)
+static bool feed_wide(int T, std::initializer_list<const void*> sides) {
+  uintptr_t a = 0;
+  for (const void* p : sides) a |= (uintptr_t)p;
+  return T % 4 == 0 && a % 16 == 0;
+}
+static bool feed_wide_rows(int T, const FeedCols& c, const FeedOuts& o) {
+  return feed_wide(T, {c.item_history, c.item_cate_history, c.time_from_first_action, c.time_to_now, o.out_item_history,
+                       o.out_item_cate_history, o.out_time_from_first_action, o.out_time_to_now});
+}
+
+// workgroups of 256 threads for `work` items, a thread each up to `cap` workgroups (grid-stride loops beyond)
+static int feed_blocks(long work, long cap) {
+  const long b = (work + 255) / 256;
+  return (int)(b > cap ? cap : b);
+}
+enum { FEED_BIG_BLOCKS = 16384, FEED_SMALL_BLOCKS = 1024 };
+
+// the 16-byte or the 4-byte instance of a kernel template on `blocks` workgroups of 256 threads
+#define FEED_LAUNCH(kernel, wide, blocks, st, ...)                                                    \
+  do {                                                                                                \
+    if (wide)                                                                                         \
+      hipLaunchKernelGGL(kernel<feed_u32x4>, dim3(blocks), dim3(256), 0, st, __VA_ARGS__);            \
+    else                                                                                              \
+      hipLaunchKernelGGL(kernel<unsigned>, dim3(blocks), dim3(256), 0, st, __VA_ARGS__);              \
+    CLSR_CHECK_LAUNCH();                                                                              \
+  } while (0)
+
 enum { FEED_ERR_CODE = 0, FEED_ERR_INDEX = 1, FEED_ERR_VALUE = 2, FEED_ERR_LAUNCH = 3 };
+
+// The two ends of a checker (ONE workgroup of 1024 threads).  feed_refuse, one thread: raise (code, index, *value) unless
+// an earlier failure is still there, and set the launch status the builder reads first.  feed_accept, every thread, s_cnt
+// zeroed before a barrier: count the shard's histories longer than thr as an integer, clear the status, write denom.
+__device__ __forceinline__ void feed_refuse(int* err, int code, int index, const int* value) {
+  if (err[FEED_ERR_CODE] == 0) {      // sticky: the first failure stays until clsr_feed_clear_error
+    err[FEED_ERR_CODE] = code;
+    err[FEED_ERR_INDEX] = index;
+    err[FEED_ERR_VALUE] = *value;
+  }
+  err[FEED_ERR_LAUNCH] = 1;
+}
+
+__device__ __forceinline__ void feed_accept(const FeedArgs& d, int* s_cnt) {
+  int cnt = 0;
+  for (int i = threadIdx.x; i < (int)d.n; i += 1024) cnt += d.lens[d.sel[d.h0 + i]] > d.thr ? 1 : 0;
+  if (cnt) atomicAdd(s_cnt, cnt);           // integer sum: the value does not depend on the order
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    d.err[FEED_ERR_LAUNCH] = 0;
+    d.out_denom[0] = (float)((long)*s_cnt * d.G);
+  }
+}
 
 __global__ void __launch_bounds__(1024) feed_check_kernel(FeedArgs d) {
   __shared__ int s_bad, s_cnt;
@@ -46,44 +127,43 @@ __global__ void __launch_bounds__(1024) feed_check_kernel(FeedArgs d) {
   __syncthreads();
   const int bad = s_bad;
   if (bad != INT_MAX) {
-    if (threadIdx.x == 0) {
-      if (d.err[FEED_ERR_CODE] == 0) {      // sticky: the first failure stays until clsr_feed_clear_error
-        d.err[FEED_ERR_CODE] = bad < n_sel ? 1 : 2;
-        d.err[FEED_ERR_INDEX] = bad < n_sel ? bad : bad - n_sel;
-        d.err[FEED_ERR_VALUE] = bad < n_sel ? d.sel[bad] : d.src[row0 + (bad - n_sel)];
-      }
-      d.err[FEED_ERR_LAUNCH] = 1;
-    }
+    if (threadIdx.x == 0)
+      feed_refuse(d.err, bad < n_sel ? 1 : 2, bad < n_sel ? bad : bad - n_sel,
+                  bad < n_sel ? d.sel + bad : d.src + row0 + (bad - n_sel));
     return;
   }
-  int cnt = 0;
-  for (int i = threadIdx.x; i < (int)d.n; i += 1024) cnt += d.lens[d.sel[d.h0 + i]] > d.thr ? 1 : 0;
-  if (cnt) atomicAdd(&s_cnt, cnt);          // integer sum: the value does not depend on the order
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    d.err[FEED_ERR_LAUNCH] = 0;
-    d.out_denom[0] = (float)((long)s_cnt * d.G);
-  }
+  feed_accept(d, &s_cnt);
 }
+
+// The file line an output row of the four history-level arrays is copied from: a training feed (lines sel[h0 ..), every
+// line G times when expanded) and an evaluation chunk (every g-th line of keep[k0 ..)).
+struct FeedTrainLine {
+  const FeedArgs& d;
+  __device__ __forceinline__ long operator()(long r) const { return d.sel[d.h0 + (d.expanded ? r / d.G : r)]; }
+};
+struct FeedEvalLine {
+  const int* __restrict__ keep;
+  int g;
+  __device__ __forceinline__ long operator()(long h) const { return keep[h * g]; }
+};
 
 // W: one 4-byte word or four per access.  A row of T words is contiguous on both sides and consecutive lanes walk
 // consecutive words of it; the four history-level arrays move together (four independent loads in flight per lane).
-template <typename W>
-__device__ __forceinline__ void feed_move_rows(const FeedArgs& d, long nq, int Tq, int big_blocks) {
-  const int G = d.G;
-  const W* __restrict__ c0 = (const W*)d.item_history;
-  const W* __restrict__ c1 = (const W*)d.item_cate_history;
-  const W* __restrict__ c2 = (const W*)d.time_from_first_action;
-  const W* __restrict__ c3 = (const W*)d.time_to_now;
-  W* __restrict__ o0 = (W*)d.out_item_history;
-  W* __restrict__ o1 = (W*)d.out_item_cate_history;
-  W* __restrict__ o2 = (W*)d.out_time_from_first_action;
-  W* __restrict__ o3 = (W*)d.out_time_to_now;
+template <typename W, typename Line>
+__device__ __forceinline__ void feed_move_rows(const FeedCols& cols, const FeedOuts& outs, const Line line_of, long nq,
+                                               int Tq, int big_blocks) {
+  const W* __restrict__ c0 = (const W*)cols.item_history;
+  const W* __restrict__ c1 = (const W*)cols.item_cate_history;
+  const W* __restrict__ c2 = (const W*)cols.time_from_first_action;
+  const W* __restrict__ c3 = (const W*)cols.time_to_now;
+  W* __restrict__ o0 = (W*)outs.out_item_history;
+  W* __restrict__ o1 = (W*)outs.out_item_cate_history;
+  W* __restrict__ o2 = (W*)outs.out_time_from_first_action;
+  W* __restrict__ o3 = (W*)outs.out_time_to_now;
   for (long q = (long)blockIdx.x * 256 + threadIdx.x; q < nq; q += (long)big_blocks * 256) {
     const long r = q / Tq;
     const int c = (int)(q - r * Tq);
-    const long line = d.sel[d.h0 + (d.expanded ? r / G : r)];
-    const long s = line * Tq + c;
+    const long s = line_of(r) * Tq + c;
     const W v0 = c0[s], v1 = c1[s], v2 = c2[s], v3 = c3[s];
     o0[q] = v0;
     o1[q] = v1;
@@ -97,7 +177,7 @@ __global__ void __launch_bounds__(256) feed_build_kernel(FeedArgs d, long nq, in
   if (d.err[FEED_ERR_LAUNCH]) return;
   const int G = d.G;
   if ((int)blockIdx.x < big_blocks) {
-    feed_move_rows<W>(d, nq, Tq, big_blocks);
+    feed_move_rows<W>(d, d, FeedTrainLine{d}, nq, Tq, big_blocks);
     return;
   }
   const long nrow = d.n * G, row0 = d.h0 * G;
@@ -128,60 +208,36 @@ extern "C" int clsr_feed_build_supported(long N, long n_sel, int T, int G) {
          G <= clsr_feed_build_max_group() && n_sel * ((long)G + 1) < INT_MAX;
 }
 
-extern "C" int clsr_feed_build(const void* const* cols_host, long N, const int* sel, long n_sel, const int* src, long h0,
-                               long n, int T, int G, int expanded, int thr, void* const* outs_host, int* err, void* stream) {
-  CLSR_CHECK_ARG(cols_host && outs_host);
-  FeedArgs d;
-  d.item_history = (const int*)cols_host[0];
-  d.item_cate_history = (const int*)cols_host[1];
-  d.time_from_first_action = (const float*)cols_host[2];
-  d.time_to_now = (const float*)cols_host[3];
-  d.lens = (const int*)cols_host[4];
-  d.users = (const int*)cols_host[5];
-  d.items = (const int*)cols_host[6];
-  d.cates = (const int*)cols_host[7];
-  d.sel = sel;
-  d.src = src;
-  d.out_users = (int*)outs_host[0];
-  d.out_items = (int*)outs_host[1];
-  d.out_cates = (int*)outs_host[2];
-  d.out_item_history = (int*)outs_host[3];
-  d.out_item_cate_history = (int*)outs_host[4];
-  d.out_time_from_first_action = (float*)outs_host[5];
-  d.out_time_to_now = (float*)outs_host[6];
-  d.out_labels = (float*)outs_host[7];
-  d.out_seq_len = (int*)outs_host[8];
-  d.out_denom = (float*)outs_host[9];
-  d.err = err;
+// The arguments of clsr_feed_build / clsr_feed_build_pos -> d, checked; `supported`: the entry point's own shape rule.
+static int feed_train_args(FeedArgs& d, const void* const* cols_host, long N, const int* sel, long n_sel, const int* src,
+                           long h0, long n, int T, int G, int expanded, int thr, void* const* outs_host, int* err,
+                           int supported) {
+  CLSR_CHECK_ARG(feed_cols(d, cols_host, 8));
+  CLSR_CHECK_ARG(feed_outs(d, outs_host, false));
+  CLSR_CHECK_ARG(sel && src && err);
+  d.sel = sel, d.src = src, d.err = err;
   d.N = N, d.n_sel = n_sel, d.h0 = h0, d.n = n;
   d.T = T, d.G = G, d.expanded = expanded, d.thr = thr;
-  CLSR_CHECK_ARG(d.item_history && d.item_cate_history && d.time_from_first_action && d.time_to_now);
-  CLSR_CHECK_ARG(d.lens && d.users && d.items && d.cates && d.sel && d.src && d.err);
-  CLSR_CHECK_ARG(d.out_users && d.out_items && d.out_cates && d.out_item_history && d.out_item_cate_history);
-  CLSR_CHECK_ARG(d.out_time_from_first_action && d.out_time_to_now && d.out_labels && d.out_seq_len && d.out_denom);
-  CLSR_CHECK_SUPPORTED(clsr_feed_build_supported(d.N, d.n_sel, d.T, d.G));
+  CLSR_CHECK_SUPPORTED(supported);
   CLSR_CHECK_ARG(d.h0 >= 0 && d.n >= 1 && d.h0 + d.n <= d.n_sel);
   CLSR_CHECK_ARG(d.expanded == 0 || d.expanded == 1);
+  return CLSR_OK;
+}
+
+extern "C" int clsr_feed_build(const void* const* cols_host, long N, const int* sel, long n_sel, const int* src, long h0,
+                               long n, int T, int G, int expanded, int thr, void* const* outs_host, int* err, void* stream) {
+  FeedArgs d;
+  const int rc = feed_train_args(d, cols_host, N, sel, n_sel, src, h0, n, T, G, expanded, thr, outs_host, err,
+                                 clsr_feed_build_supported(N, n_sel, T, G));
+  if (rc != CLSR_OK) return rc;
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(feed_check_kernel, dim3(1), dim3(1024), 0, st, d);
   CLSR_CHECK_LAUNCH();
-  // 16-byte accesses where every row starts on a 16-byte boundary on both sides (T = 50 does not)
-  uintptr_t a = 0;
-  for (const void* p : {(const void*)d.item_history, (const void*)d.item_cate_history, (const void*)d.time_from_first_action,
-                        (const void*)d.time_to_now, (const void*)d.out_item_history, (const void*)d.out_item_cate_history,
-                        (const void*)d.out_time_from_first_action, (const void*)d.out_time_to_now})
-    a |= (uintptr_t)p;
-  const bool wide = d.T % 4 == 0 && a % 16 == 0;
+  const bool wide = feed_wide_rows(d.T, d, d);
   const int Tq = wide ? d.T / 4 : d.T;
   const long nq = d.n * (d.expanded ? d.G : 1) * Tq;
-  long big = (nq + 255) / 256, small = (d.n * d.G + 255) / 256;
-  if (big > 16384) big = 16384;
-  if (small > 1024) small = 1024;
-  if (wide)
-    hipLaunchKernelGGL(feed_build_kernel<feed_u32x4>, dim3((int)(big + small)), dim3(256), 0, st, d, nq, Tq, (int)big);
-  else
-    hipLaunchKernelGGL(feed_build_kernel<unsigned>, dim3((int)(big + small)), dim3(256), 0, st, d, nq, Tq, (int)big);
-  CLSR_CHECK_LAUNCH();
+  const int big = feed_blocks(nq, FEED_BIG_BLOCKS), small = feed_blocks(d.n * d.G, FEED_SMALL_BLOCKS);
+  FEED_LAUNCH(feed_build_kernel, wide, big + small, st, d, nq, Tq, big);
   return CLSR_OK;
 }
 
@@ -229,14 +285,9 @@ __global__ void __launch_bounds__(1024) feed_check_pos_kernel(FeedArgs d, int* b
   __syncthreads();
   bad = s_bad;
   if (bad != INT_MAX) {
-    if (threadIdx.x == 0) {
-      if (d.err[FEED_ERR_CODE] == 0) {      // sticky: the first failure stays until clsr_feed_clear_error
-        d.err[FEED_ERR_CODE] = bad < n_sel ? 1 : 3;
-        d.err[FEED_ERR_INDEX] = bad < n_sel ? bad : (int)p0 + (bad - n_sel);
-        d.err[FEED_ERR_VALUE] = bad < n_sel ? d.sel[bad] : d.src[p0 + (bad - n_sel)];
-      }
-      d.err[FEED_ERR_LAUNCH] = 1;
-    }
+    if (threadIdx.x == 0)
+      feed_refuse(d.err, bad < n_sel ? 1 : 3, bad < n_sel ? bad : (int)p0 + (bad - n_sel),
+                  bad < n_sel ? d.sel + bad : d.src + p0 + (bad - n_sel));
     return;
   }
   for (int i = threadIdx.x; i < n_sel; i += 1024) {
@@ -244,14 +295,7 @@ __global__ void __launch_bounds__(1024) feed_check_pos_kernel(FeedArgs d, int* b
     bt[i] = d.items[line];
     bt[n_sel + i] = d.cates[line];
   }
-  int cnt = 0;
-  for (int i = threadIdx.x; i < (int)d.n; i += 1024) cnt += d.lens[d.sel[d.h0 + i]] > d.thr ? 1 : 0;
-  if (cnt) atomicAdd(&s_cnt, cnt);          // integer sum: the value does not depend on the order
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    d.err[FEED_ERR_LAUNCH] = 0;
-    d.out_denom[0] = (float)((long)s_cnt * d.G);
-  }
+  feed_accept(d, &s_cnt);
 }
 
 template <typename W> struct feed_word;
@@ -278,7 +322,7 @@ __global__ void __launch_bounds__(256) feed_build_pos_kernel(FeedArgs d, const i
   constexpr int WN = (int)(sizeof(W) / 4);
   const int G = d.G, T = d.T;
   if ((int)blockIdx.x < big_blocks) {
-    feed_move_rows<W>(d, nq, Tq, big_blocks);
+    feed_move_rows<W>(d, d, FeedTrainLine{d}, nq, Tq, big_blocks);
     return;
   }
   if ((int)blockIdx.x < big_blocks + tgt_blocks) {
@@ -339,38 +383,11 @@ extern "C" int clsr_feed_build_pos_supported(long N, long n_sel, int T, int G) {
 extern "C" int clsr_feed_build_pos(const void* const* cols_host, long N, const int* sel, long n_sel, const int* psrc, long h0,
                                    long n, int T, int G, int expanded, int thr, void* const* outs_host, int* scratch, int* err,
                                    void* stream) {
-  CLSR_CHECK_ARG(cols_host && outs_host);
+  CLSR_CHECK_ARG(scratch);
   FeedArgs d;
-  d.item_history = (const int*)cols_host[0];
-  d.item_cate_history = (const int*)cols_host[1];
-  d.time_from_first_action = (const float*)cols_host[2];
-  d.time_to_now = (const float*)cols_host[3];
-  d.lens = (const int*)cols_host[4];
-  d.users = (const int*)cols_host[5];
-  d.items = (const int*)cols_host[6];
-  d.cates = (const int*)cols_host[7];
-  d.sel = sel;
-  d.src = psrc;
-  d.out_users = (int*)outs_host[0];
-  d.out_items = (int*)outs_host[1];
-  d.out_cates = (int*)outs_host[2];
-  d.out_item_history = (int*)outs_host[3];
-  d.out_item_cate_history = (int*)outs_host[4];
-  d.out_time_from_first_action = (float*)outs_host[5];
-  d.out_time_to_now = (float*)outs_host[6];
-  d.out_labels = (float*)outs_host[7];
-  d.out_seq_len = (int*)outs_host[8];
-  d.out_denom = (float*)outs_host[9];
-  d.err = err;
-  d.N = N, d.n_sel = n_sel, d.h0 = h0, d.n = n;
-  d.T = T, d.G = G, d.expanded = expanded, d.thr = thr;
-  CLSR_CHECK_ARG(d.item_history && d.item_cate_history && d.time_from_first_action && d.time_to_now);
-  CLSR_CHECK_ARG(d.lens && d.users && d.items && d.cates && d.sel && d.src && d.err && scratch);
-  CLSR_CHECK_ARG(d.out_users && d.out_items && d.out_cates && d.out_item_history && d.out_item_cate_history);
-  CLSR_CHECK_ARG(d.out_time_from_first_action && d.out_time_to_now && d.out_labels && d.out_seq_len && d.out_denom);
-  CLSR_CHECK_SUPPORTED(clsr_feed_build_pos_supported(d.N, d.n_sel, d.T, d.G));
-  CLSR_CHECK_ARG(d.h0 >= 0 && d.n >= 1 && d.h0 + d.n <= d.n_sel);
-  CLSR_CHECK_ARG(d.expanded == 0 || d.expanded == 1);
+  const int rc = feed_train_args(d, cols_host, N, sel, n_sel, psrc, h0, n, T, G, expanded, thr, outs_host, err,
+                                 clsr_feed_build_pos_supported(N, n_sel, T, G));
+  if (rc != CLSR_OK) return rc;
   hipStream_t st = (hipStream_t)stream;
   int* part = scratch + 2 * d.n_sel;
   long scan = (d.n_sel + d.n * (d.G - 1) * d.T + 2047) / 2048;      // eight positions a thread
@@ -379,26 +396,12 @@ extern "C" int clsr_feed_build_pos(const void* const* cols_host, long N, const i
   CLSR_CHECK_LAUNCH();
   hipLaunchKernelGGL(feed_check_pos_kernel, dim3(1), dim3(1024), 0, st, d, scratch, (const int*)part, (int)scan);
   CLSR_CHECK_LAUNCH();
-  // 16-byte accesses where every row starts on a 16-byte boundary on every side that is read or written in words of W
-  uintptr_t a = 0;
-  for (const void* p : {(const void*)d.item_history, (const void*)d.item_cate_history, (const void*)d.time_from_first_action,
-                        (const void*)d.time_to_now, (const void*)d.out_item_history, (const void*)d.out_item_cate_history,
-                        (const void*)d.out_time_from_first_action, (const void*)d.out_time_to_now, (const void*)d.src,
-                        (const void*)d.out_items, (const void*)d.out_cates, (const void*)d.out_labels})
-    a |= (uintptr_t)p;
-  const bool wide = d.T % 4 == 0 && a % 16 == 0;
+  const bool wide = feed_wide_rows(d.T, d, d) && feed_wide(d.T, {d.src, d.out_items, d.out_cates, d.out_labels});
   const int Tq = wide ? d.T / 4 : d.T;
-  const long nq = d.n * (d.expanded ? d.G : 1) * Tq, nqt = d.n * d.G * Tq;
-  long big = (nq + 255) / 256, tgt = (nqt + 255) / 256, small = (d.n * (d.expanded ? d.G : 1) + 255) / 256;
-  if (big > 16384) big = 16384;
-  if (tgt > 16384) tgt = 16384;
-  if (small > 1024) small = 1024;
-  const dim3 grid((int)(big + tgt + small));
-  if (wide)
-    hipLaunchKernelGGL(feed_build_pos_kernel<feed_u32x4>, grid, dim3(256), 0, st, d, scratch, nq, nqt, Tq, (int)big, (int)tgt);
-  else
-    hipLaunchKernelGGL(feed_build_pos_kernel<unsigned>, grid, dim3(256), 0, st, d, scratch, nq, nqt, Tq, (int)big, (int)tgt);
-  CLSR_CHECK_LAUNCH();
+  const long R = d.n * (d.expanded ? d.G : 1), nq = R * Tq, nqt = d.n * d.G * Tq;
+  const int big = feed_blocks(nq, FEED_BIG_BLOCKS), tgt = feed_blocks(nqt, FEED_BIG_BLOCKS),
+            small = feed_blocks(R, FEED_SMALL_BLOCKS);
+  FEED_LAUNCH(feed_build_pos_kernel, wide, big + tgt + small, st, d, (const int*)scratch, nq, nqt, Tq, big, tgt);
   return CLSR_OK;
 }
 
@@ -431,28 +434,11 @@ extern "C" int clsr_feed_error(const int* err, void* stream) {
 // once per (file, keep), every line whose history-level columns equal those of the line before it; the host turns the
 // marks into chunks (k0, n, g) and clsr_feed_build_eval writes the arena CLSRNet.upload(feed, False) would have filled for
 // a chunk: history-level tensors from every g-th line, line-level tensors from every line.  One launch each.
-struct FeedEvalArgs {
-  const int* item_history; const int* item_cate_history; const float* time_from_first_action; const float* time_to_now;
-  const int* lens; const int* users; const int* items; const int* cates; const float* labels;
+struct FeedEvalArgs : FeedCols, FeedOuts {
   const int* keep;
-  int* out_users; int* out_items; int* out_cates; int* out_item_history; int* out_item_cate_history;
-  float* out_time_from_first_action; float* out_time_to_now; float* out_labels; int* out_users_rows; int* out_seq_len;
-  float* out_denom;
   long k0, n;
   int g, T, thr;
 };
-
-static void feed_eval_cols(FeedEvalArgs& d, const void* const* cols_host, int with_labels) {
-  d.item_history = (const int*)cols_host[0];
-  d.item_cate_history = (const int*)cols_host[1];
-  d.time_from_first_action = (const float*)cols_host[2];
-  d.time_to_now = (const float*)cols_host[3];
-  d.lens = (const int*)cols_host[4];
-  d.users = (const int*)cols_host[5];
-  d.items = (const int*)cols_host[6];
-  d.cates = (const int*)cols_host[7];
-  d.labels = with_labels ? (const float*)cols_host[8] : nullptr;
-}
 
 // the user id as the host path carries it: through the float32 placeholder of the reference and back
 __device__ __forceinline__ int feed_user_id(int id) { return (int)(float)id; }
@@ -503,24 +489,7 @@ __global__ void __launch_bounds__(256) feed_build_eval_kernel(FeedEvalArgs d, lo
   const int g = d.g;
   const int* __restrict__ keep = d.keep + d.k0;
   if ((int)blockIdx.x < big_blocks) {
-    const W* __restrict__ c0 = (const W*)d.item_history;
-    const W* __restrict__ c1 = (const W*)d.item_cate_history;
-    const W* __restrict__ c2 = (const W*)d.time_from_first_action;
-    const W* __restrict__ c3 = (const W*)d.time_to_now;
-    W* __restrict__ o0 = (W*)d.out_item_history;
-    W* __restrict__ o1 = (W*)d.out_item_cate_history;
-    W* __restrict__ o2 = (W*)d.out_time_from_first_action;
-    W* __restrict__ o3 = (W*)d.out_time_to_now;
-    for (long q = (long)blockIdx.x * 256 + threadIdx.x; q < nq; q += (long)big_blocks * 256) {
-      const long h = q / Tq;
-      const int c = (int)(q - h * Tq);
-      const long s = (long)keep[h * g] * Tq + c;
-      const W v0 = c0[s], v1 = c1[s], v2 = c2[s], v3 = c3[s];
-      o0[q] = v0;
-      o1[q] = v1;
-      o2[q] = v2;
-      o3[q] = v3;
-    }
+    feed_move_rows<W>(d, d, FeedEvalLine{keep, g}, nq, Tq, big_blocks);
     return;
   }
   const int small_blocks = (int)gridDim.x - big_blocks - 1;
@@ -557,70 +526,34 @@ extern "C" int clsr_feed_build_eval_supported(long N, long n_keep, long k0, long
 
 extern "C" int clsr_feed_same_rows(const void* const* cols_host, long N, const int* keep, long n_keep, int T,
                                    unsigned char* flags, void* stream) {
-  CLSR_CHECK_ARG(cols_host && keep && flags);
+  CLSR_CHECK_ARG(keep && flags);
   FeedEvalArgs d = {};
-  feed_eval_cols(d, cols_host, 0);
+  CLSR_CHECK_ARG(feed_cols(d, cols_host, 6));
   d.keep = keep;
   d.T = T;
-  CLSR_CHECK_ARG(d.item_history && d.item_cate_history && d.time_from_first_action && d.time_to_now && d.lens && d.users);
   CLSR_CHECK_ARG(N >= 1 && N <= INT_MAX && n_keep >= 1 && n_keep <= INT_MAX && T >= 1 && T <= clsr_feed_build_max_steps());
-  uintptr_t a = 0;
-  for (const void* p : {(const void*)d.item_history, (const void*)d.item_cate_history, (const void*)d.time_from_first_action,
-                        (const void*)d.time_to_now})
-    a |= (uintptr_t)p;
-  const bool wide = T % 4 == 0 && a % 16 == 0;
+  const bool wide = feed_wide(T, {d.item_history, d.item_cate_history, d.time_from_first_action, d.time_to_now});
   const int Tq = wide ? T / 4 : T;
   long blocks = (n_keep + 3) / 4;            // four waves, four pairs a workgroup
   if (blocks > 8192) blocks = 8192;
-  hipStream_t st = (hipStream_t)stream;
-  if (wide)
-    hipLaunchKernelGGL(feed_same_rows_kernel<feed_u32x4>, dim3((int)blocks), dim3(256), 0, st, d, n_keep, Tq, flags);
-  else
-    hipLaunchKernelGGL(feed_same_rows_kernel<unsigned>, dim3((int)blocks), dim3(256), 0, st, d, n_keep, Tq, flags);
-  CLSR_CHECK_LAUNCH();
+  FEED_LAUNCH(feed_same_rows_kernel, wide, (int)blocks, (hipStream_t)stream, d, n_keep, Tq, flags);
   return CLSR_OK;
 }
 
 extern "C" int clsr_feed_build_eval(const void* const* cols_host, long N, const int* keep, long n_keep, long k0, long n,
                                     int g, int T, int thr, void* const* outs_host, void* stream) {
-  CLSR_CHECK_ARG(cols_host && outs_host && keep);
+  CLSR_CHECK_ARG(keep);
   FeedEvalArgs d = {};
-  feed_eval_cols(d, cols_host, 1);
+  CLSR_CHECK_ARG(feed_cols(d, cols_host, 9));
+  CLSR_CHECK_ARG(feed_outs(d, outs_host, true));
   d.keep = keep;
-  d.out_users = (int*)outs_host[0];
-  d.out_items = (int*)outs_host[1];
-  d.out_cates = (int*)outs_host[2];
-  d.out_item_history = (int*)outs_host[3];
-  d.out_item_cate_history = (int*)outs_host[4];
-  d.out_time_from_first_action = (float*)outs_host[5];
-  d.out_time_to_now = (float*)outs_host[6];
-  d.out_labels = (float*)outs_host[7];
-  d.out_users_rows = (int*)outs_host[8];     // may be null: a g == 1 feed has no such tensor
-  d.out_seq_len = (int*)outs_host[9];
-  d.out_denom = (float*)outs_host[10];
   d.k0 = k0, d.n = n, d.g = g, d.T = T, d.thr = thr;
-  CLSR_CHECK_ARG(d.item_history && d.item_cate_history && d.time_from_first_action && d.time_to_now);
-  CLSR_CHECK_ARG(d.lens && d.users && d.items && d.cates && d.labels);
-  CLSR_CHECK_ARG(d.out_users && d.out_items && d.out_cates && d.out_item_history && d.out_item_cate_history);
-  CLSR_CHECK_ARG(d.out_time_from_first_action && d.out_time_to_now && d.out_labels && d.out_seq_len && d.out_denom);
   CLSR_CHECK_ARG(d.out_users_rows || g == 1);
   CLSR_CHECK_ARG(clsr_feed_build_eval_supported(N, n_keep, k0, n, g, T));
-  uintptr_t a = 0;
-  for (const void* p : {(const void*)d.item_history, (const void*)d.item_cate_history, (const void*)d.time_from_first_action,
-                        (const void*)d.time_to_now, (const void*)d.out_item_history, (const void*)d.out_item_cate_history,
-                        (const void*)d.out_time_from_first_action, (const void*)d.out_time_to_now})
-    a |= (uintptr_t)p;
-  const bool wide = T % 4 == 0 && a % 16 == 0;
+  const bool wide = feed_wide_rows(T, d, d);
   const int Tq = wide ? T / 4 : T;
   const long nq = (n / g) * Tq;
-  long big = (nq + 255) / 256, small = (n + 255) / 256;
-  if (big > 16384) big = 16384;
-  if (small > 1024) small = 1024;
-  hipStream_t st = (hipStream_t)stream;
-  if (wide)
-    hipLaunchKernelGGL(feed_build_eval_kernel<feed_u32x4>, dim3((int)(big + small + 1)), dim3(256), 0, st, d, nq, Tq, (int)big);
-  else
-    hipLaunchKernelGGL(feed_build_eval_kernel<unsigned>, dim3((int)(big + small + 1)), dim3(256), 0, st, d, nq, Tq, (int)big);
-  CLSR_CHECK_LAUNCH();
+  const int big = feed_blocks(nq, FEED_BIG_BLOCKS), small = feed_blocks(n, FEED_SMALL_BLOCKS);
+  FEED_LAUNCH(feed_build_eval_kernel, wide, big + small + 1, (hipStream_t)stream, d, nq, Tq, big);
   return CLSR_OK;
 }

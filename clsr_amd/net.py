@@ -25,7 +25,7 @@ from collections import OrderedDict
 import numpy as np
 import torch
 
-from clsr_amd import ops
+from clsr_amd import feeds, ops
 from clsr_amd.ops import call, query
 from clsr_amd.params import CL, TABLES, UNUSED_TABLE, init_tensor, param_specs
 
@@ -1316,7 +1316,7 @@ class CLSRNet(object):
     # ------------------------------------------------------------------ feed upload
     def host_arrays(self, feed, training=True):
         """numpy feed (iterator layout) -> dict of contiguous numpy arrays with the device dtypes
-        (+ the per-batch scalars the kernels read from device memory).
+        (+ the per-batch scalars the kernels read from device memory), then ``B, T, compact, G`` of the device feed.
 
         A COMPACT training feed (``hist_group`` = 1 + train_num_ngs present: users / histories / mask /
         time arrays hold one row per positive line, see sequential_iterator.LazyFeed) is uploaded as is
@@ -1341,12 +1341,8 @@ class CLSRNet(object):
             h["users_rows"] = np.ascontiguousarray(np.asarray(feed["users_rows"]).reshape(-1), dtype=np.int32)
         h["seq_len"] = seq_len
         rep = hg if compact else 1
-        thr = getattr(self.hp, "contrastive_length_threshold", None) or 0     # (unset for the sibling models)
-        h["denom"] = np.asarray([float((seq_len > thr).sum() * rep)], dtype=np.float32)
-        self._last_group = hg if compact else 0
-        return h, int(mask.shape[0]) * rep, int(mask.shape[1]), compact
-
-    _STAGE_SLOTS = 3
+        h["denom"] = np.asarray([float((seq_len > feeds.length_threshold(self.hp)).sum() * rep)], dtype=np.float32)
+        return h, int(mask.shape[0]) * rep, int(mask.shape[1]), compact, hg if compact else 0
 
     def upload(self, feed, training, into=None, copy_stream=None):
         """numpy feed -> device tensors (views into ONE device arena).  The arrays are packed into a
@@ -1361,47 +1357,15 @@ class CLSRNet(object):
         launches step N (``SequentialBaseModel.batch_train``), the batch crosses PCIe while the previous step
         computes.  The caller records ``into["_free"]`` (an event on the compute stream) after the last launch that
         reads this arena; the copy waits for it."""
-        h, B, T, compact = self.host_arrays(feed, training)
+        h, B, T, compact, G = self.host_arrays(feed, training)
         if into is None:
-            lay, off = {}, 0
-            for k, arr in h.items():
-                lay[k] = (off, arr.nbytes)
-                off += (arr.nbytes + 15) // 16 * 16
-            dev = torch.empty(off, dtype=torch.uint8, device=self.device)
-            into = {"B": B, "T": T, "compact": compact, "G": self._last_group, "_lay": lay, "_nbytes": off,
-                    "_dev": dev, "_slot": 0,
-                    "_stage": [None] * self._STAGE_SLOTS}
-            for k, arr in h.items():
-                o, n = lay[k]
-                into[k] = dev[o:o + n].view(torch.from_numpy(arr).dtype).view(arr.shape)
-        assert into["B"] == B and into["T"] == T and into["compact"] == compact and into["G"] == self._last_group
-        slot = into["_slot"]
-        into["_slot"] = (slot + 1) % self._STAGE_SLOTS
-        if into["_stage"][slot] is None:
-            pin = torch.empty(into["_nbytes"], dtype=torch.uint8, pin_memory=True)
-            into["_stage"][slot] = [pin, None, pin.numpy()]
-        pin, ev, pin_np = into["_stage"][slot]
-        if ev is not None:
-            ev.synchronize()
-        for k, arr in h.items():
-            o, n = into["_lay"][k]
-            assert arr.nbytes == n
-            # plain single-threaded memcpy on purpose: a torch CPU copy_ wakes the whole OpenMP pool,
-            # whose spinning workers were measured to stall this thread's kernel launches for ~7 ms/step
-            np.copyto(pin_np[o:o + n], arr.reshape(-1).view(np.uint8))
-        if copy_stream is None:
-            call("clsr_stage_feed", into["_dev"], pin.data_ptr(), into["_nbytes"])
-            ev = torch.cuda.Event()
-            ev.record()
-        else:
-            if into.get("_free") is not None:
-                copy_stream.wait_event(into["_free"])
-            with torch.cuda.stream(copy_stream):
-                into["_dev"].copy_(pin, non_blocking=True)
-                ev = torch.cuda.Event()
-                ev.record(copy_stream)
+            spec = [(k, a.shape, torch.from_numpy(a).dtype) for k, a in h.items()]
+            into = feeds.device_feed(spec, self.device, B, T, compact, G)
+        assert into["B"] == B and into["T"] == T and into["compact"] == compact and into["G"] == G
+        # (``into`` keeps its arena; on ``copy_stream`` the copy waits for ``_free`` and ``_ready`` is published)
+        ev = into["_arena"].send(h, copy_stream, into.get("_free"))
+        if copy_stream is not None:
             into["_ready"] = ev      # the caller makes the compute stream wait for it right before the step
-        into["_stage"][slot][1] = ev
         return into
 
     def build_feed(self, resident, sel, src, h0=0, n=None, into=None):
@@ -1428,60 +1392,21 @@ class CLSRNet(object):
             raise NotImplementedError("%s: N = %d, batch of %d lines, T = %d, G = %d is not supported"
                                       % (entry, resident.N, n_sel, T, G))
         if into is None:
-            i32, f32 = torch.int32, torch.float32
-            per = (B, T) if pos else (B,)
-            spec = (("users", (R,), i32), ("items", per, i32), ("cates", per, i32), ("item_history", (R, T), i32),
-                    ("item_cate_history", (R, T), i32), ("time_from_first_action", (R, T), f32),
-                    ("time_to_now", (R, T), f32), ("labels", (int(np.prod(per)),), f32), ("seq_len", (R,), i32),
-                    ("denom", (1,), f32))
-            lay, off = {}, 0
-            for k, shape, _ in spec:           # (the layout of ``upload``: 16-byte aligned pieces of one arena)
-                nb = 4 * int(np.prod(shape))
-                lay[k] = (off, nb)
-                off += (nb + 15) // 16 * 16
-            dev = torch.empty(off, dtype=torch.uint8, device=self.device)
-            into = {"B": B, "T": T, "compact": compact, "G": G if compact else 0, "_lay": lay, "_nbytes": off,
-                    "_dev": dev, "_slot": 0, "_stage": [None] * self._STAGE_SLOTS, "_rcap": 0, "_rdev": None,
-                    "_rslot": 0, "_rstage": [None] * self._STAGE_SLOTS, "_desc": None}
-            for k, shape, dt in spec:
-                o, nb = lay[k]
-                into[k] = dev[o:o + nb].view(dt).view(shape)
+            into = feeds.device_feed(feeds.train_spec(R, B, T, pos), self.device, B, T, compact, G if compact else 0)
+            into["_rbuf"] = feeds.RecipeBuffer(self.device)
         assert into["B"] == B and into["T"] == T and into["compact"] == compact
-        self._last_group = into["G"]
-        src_off = (4 * n_sel + 15) // 16 * 16
-        nbytes = src_off + (src.nbytes + 15) // 16 * 16
         scratch = 4 * query("clsr_feed_build_pos_scratch_ints", n_sel) if pos else 0      # (device only, never staged)
-        if nbytes > into["_rcap"]:
-            for st in into["_rstage"]:      # (a pinned slot a queued kernel still reads is not let go of)
-                if st is not None and st[1] is not None:
-                    st[1].synchronize()
-            into["_rcap"], into["_rstage"], into["_desc"] = nbytes, [None] * self._STAGE_SLOTS, None
-            into["_rdev"] = torch.empty(nbytes + scratch, dtype=torch.uint8, device=self.device)
-        slot = into["_rslot"]
-        into["_rslot"] = (slot + 1) % self._STAGE_SLOTS
-        if into["_rstage"][slot] is None:
-            pin = torch.empty(into["_rcap"], dtype=torch.uint8, pin_memory=True)
-            into["_rstage"][slot] = [pin, None, pin.numpy()]
-        pin, ev, pin_np = into["_rstage"][slot]
-        if ev is not None:
-            ev.synchronize()
-        np.copyto(pin_np[:4 * n_sel], sel.view(np.uint8))
-        np.copyto(pin_np[src_off:src_off + src.nbytes], src.reshape(-1).view(np.uint8))
-        rdev = into["_rdev"]
-        call("clsr_stage_feed", rdev, pin.data_ptr(), nbytes)
-        ev = torch.cuda.Event()
-        ev.record()
-        into["_rstage"][slot][1] = ev
-        ent = into["_desc"]
-        if ent is None or ent[0] is not resident:
-            ent = into["_desc"] = (resident, ops.feed_pointers(resident.dev, {k: into[k] for k in ops.FEED_OUTPUTS}))
-        thr = int(getattr(self.hp, "contrastive_length_threshold", None) or 0)     # (unset for the sibling models)
+        # (``into`` keeps its arena; the recipe buffer alone may grow, after every queued read of its pinned slots)
+        sel_dev, src_dev, scratch_dev = into["_rbuf"].send(sel, src, scratch)
+        arena = into["_arena"]
+        if arena.cols is not resident:
+            arena.cols, arena.ptrs = resident, ops.feed_pointers(resident.dev, {k: into[k] for k in ops.FEED_OUTPUTS})
+        thr = int(feeds.length_threshold(self.hp))
         if pos:
-            ops.feed_build_pos(ent[1], resident.N, rdev.data_ptr(), n_sel, rdev.data_ptr() + src_off, int(h0), n, T, G,
-                               not compact, thr, rdev.data_ptr() + into["_rcap"], resident.err)
+            ops.feed_build_pos(arena.ptrs, resident.N, sel_dev, n_sel, src_dev, int(h0), n, T, G, not compact, thr,
+                               scratch_dev, resident.err)
         else:
-            ops.feed_build(ent[1], resident.N, rdev.data_ptr(), n_sel, rdev.data_ptr() + src_off, int(h0), n, T, G,
-                           not compact, thr, resident.err)
+            ops.feed_build(arena.ptrs, resident.N, sel_dev, n_sel, src_dev, int(h0), n, T, G, not compact, thr, resident.err)
         return into
 
     def build_eval_feed(self, lines, k0, n, g, into=None):
@@ -1497,33 +1422,17 @@ class CLSRNet(object):
         if not query("clsr_feed_build_eval_supported", rc.N, lines.n_keep, k0, n, g, T):
             raise ValueError("clsr_feed_build_eval: lines %d .. %d + %d of %d in groups of %d (N = %d, T = %d) cannot be "
                              "built" % (k0, k0, n, lines.n_keep, g, rc.N, T))
-        H, compact = n // g, g > 1
+        compact = g > 1
         if into is None:
-            i32, f32 = torch.int32, torch.float32
-            spec = [("users", (H,), i32), ("items", (n,), i32), ("cates", (n,), i32), ("item_history", (H, T), i32),
-                    ("item_cate_history", (H, T), i32), ("time_from_first_action", (H, T), f32),
-                    ("time_to_now", (H, T), f32), ("labels", (n,), f32)]
-            if compact:
-                spec.append(("users_rows", (n,), i32))
-            spec += [("seq_len", (H,), i32), ("denom", (1,), f32)]
-            lay, off = {}, 0
-            for k, shape, _ in spec:           # (the layout of ``upload``: 16-byte aligned pieces of one arena)
-                nb = 4 * int(np.prod(shape))
-                lay[k] = (off, nb)
-                off += (nb + 15) // 16 * 16
-            dev = torch.empty(off, dtype=torch.uint8, device=self.device)
-            into = {"B": n, "T": T, "compact": compact, "G": g if compact else 0, "_lay": lay, "_nbytes": off, "_dev": dev,
-                    "_desc": None}
-            for k, shape, dt in spec:
-                o, nb = lay[k]
-                into[k] = dev[o:o + nb].view(dt).view(shape)
+            into = feeds.device_feed(feeds.eval_spec(n // g, n, T, compact), self.device, n, T, compact,
+                                     g if compact else 0)
         assert into["B"] == n and into["T"] == T and into["G"] == (g if compact else 0)
-        self._last_group = into["G"]
-        ent = into["_desc"]
-        if ent is None or ent[0] is not rc:
-            ent = into["_desc"] = (rc, ops.feed_eval_pointers(rc.dev, {k: into[k] for k in ops.FEED_EVAL_OUTPUTS if k in into}))
-        thr = int(getattr(self.hp, "contrastive_length_threshold", None) or 0)     # (unset for the sibling models)
-        ops.feed_build_eval(ent[1], rc.N, lines.keep_dev, lines.n_keep, k0, n, g, T, thr)
+        arena = into["_arena"]
+        if arena.cols is not rc:
+            outs = {k: into[k] for k in ops.FEED_EVAL_OUTPUTS if k in into}
+            arena.cols, arena.ptrs = rc, ops.feed_eval_pointers(rc.dev, outs)
+        thr = int(feeds.length_threshold(self.hp))
+        ops.feed_build_eval(arena.ptrs, rc.N, lines.keep_dev, lines.n_keep, k0, n, g, T, thr)
         return into
 
     # ------------------------------------------------------------------ attention block

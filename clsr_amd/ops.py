@@ -392,17 +392,24 @@ FEED_OUTPUTS = ("users", "items", "cates", "item_history", "item_cate_history", 
                 "labels", "seq_len", "denom")
 
 
+def _feed_pointer_array(entry, names, tensors):
+    """The host pointer array of feed entry point ``entry`` from a dict of tensors, in the order of ``names``, with the
+    dtypes the entry point reads them as checked here (it sees addresses only).  ``users_rows`` alone may be missing: a
+    null pointer."""
+    for k, t in tensors.items():
+        want = torch.float32 if k in ("time_from_first_action", "time_to_now", "labels", "denom") else torch.int32
+        if not (t.is_cuda and t.is_contiguous() and t.dtype == want):
+            raise TypeError("%s %s: a contiguous %s GPU tensor is required, got %s" % (entry, k, want, t.dtype))
+    missing = [k for k in names if k not in tensors and k != "users_rows"]
+    if missing:
+        raise KeyError("%s: no tensor %s" % (entry, ", ".join(missing)))
+    return (ctypes.c_void_p * len(names))(*[tensors[k].data_ptr() if k in tensors else None for k in names])
+
+
 def feed_pointers(cols, outs):
-    """The two host pointer arrays of clsr_feed_build from dicts of tensors (``FEED_COLUMNS`` / ``FEED_OUTPUTS``), with the
-    dtypes the entry point reads them as checked here (it sees addresses only)."""
-    f32 = ("time_from_first_action", "time_to_now", "labels", "denom")
-    for d in (cols, outs):
-        for k, t in d.items():
-            want = torch.float32 if k in f32 else torch.int32
-            if not (t.is_cuda and t.is_contiguous() and t.dtype == want):
-                raise TypeError("clsr_feed_build %s: a contiguous %s GPU tensor is required, got %s" % (k, want, t.dtype))
-    return ((ctypes.c_void_p * len(FEED_COLUMNS))(*[cols[k].data_ptr() for k in FEED_COLUMNS]),
-            (ctypes.c_void_p * len(FEED_OUTPUTS))(*[outs[k].data_ptr() for k in FEED_OUTPUTS]))
+    """The two host pointer arrays of clsr_feed_build from dicts of tensors (``FEED_COLUMNS`` / ``FEED_OUTPUTS``)."""
+    return (_feed_pointer_array("clsr_feed_build", FEED_COLUMNS, cols),
+            _feed_pointer_array("clsr_feed_build", FEED_OUTPUTS, outs))
 
 
 def feed_build(ptrs, N, sel, n_sel, src, h0, n, T, G, expanded, thr, err):
@@ -431,20 +438,8 @@ def feed_eval_pointers(cols, outs=None):
     """The host pointer arrays of clsr_feed_same_rows / clsr_feed_build_eval from dicts of tensors (``FEED_EVAL_COLUMNS``;
     ``FEED_EVAL_OUTPUTS``, where ``users_rows`` may be missing: a null pointer), dtypes checked as in
     :func:`feed_pointers`.  ``outs=None``: the column array alone."""
-    f32 = ("time_from_first_action", "time_to_now", "labels", "denom")
-    for d in (cols, outs or {}):
-        for k, t in d.items():
-            want = torch.float32 if k in f32 else torch.int32
-            if not (t.is_cuda and t.is_contiguous() and t.dtype == want):
-                raise TypeError("clsr_feed_build_eval %s: a contiguous %s GPU tensor is required, got %s" % (k, want, t.dtype))
-    cp = (ctypes.c_void_p * len(FEED_EVAL_COLUMNS))(*[cols[k].data_ptr() for k in FEED_EVAL_COLUMNS])
-    if outs is None:
-        return cp
-    missing = [k for k in FEED_EVAL_OUTPUTS if k not in outs and k != "users_rows"]
-    if missing:
-        raise KeyError("clsr_feed_build_eval: no output tensor %s" % ", ".join(missing))
-    return cp, (ctypes.c_void_p * len(FEED_EVAL_OUTPUTS))(*[outs[k].data_ptr() if k in outs else None
-                                                            for k in FEED_EVAL_OUTPUTS])
+    cp = _feed_pointer_array("clsr_feed_build_eval", FEED_EVAL_COLUMNS, cols)
+    return cp if outs is None else (cp, _feed_pointer_array("clsr_feed_build_eval", FEED_EVAL_OUTPUTS, outs))
 
 
 def feed_same_rows(cols_ptrs, N, keep, n_keep, T, flags):

@@ -28,21 +28,31 @@ _SMALL = ("lens", "users", "items", "cates")
 COLUMNS = tuple(k for k, _ in _BIG) + _SMALL
 
 
-def check_recipe(sel, src, N, G):
-    """``sel`` int32 ``[n]`` line numbers in ``[0, N)``, ``src`` int32 ``[n, G]`` batch positions in ``[0, n)`` with
-    ``src[:, 0]`` the line itself (the positive row).  Raises TypeError / ValueError; returns ``n``."""
-    for name, a, nd in (("sel", sel, 1), ("src", src, 2)):
+def _check(sel, name, src, N, rank, tail, G, T=None):
+    """The body the two recipe checks share: ``sel`` int32 ``[n]`` in ``[0, N)`` and the ``rank``-d second array ``name``,
+    int32 ``[n] + tail`` in ``[0, n)`` (``tail`` None: no batch has this shape; ``G``, ``T``: the groups as the message
+    names them), both contiguous."""
+    for nm, a, nd in (("sel", sel, 1), (name, src, rank)):
         if not isinstance(a, np.ndarray) or a.dtype != np.int32:
-            raise TypeError("recipe %s: an int32 numpy array is required, got %s" % (name, getattr(a, "dtype", type(a))))
+            raise TypeError("recipe %s: an int32 numpy array is required, got %s" % (nm, getattr(a, "dtype", type(a))))
         if a.ndim != nd or not a.flags.c_contiguous:
-            raise ValueError("recipe %s: a contiguous %d-d array is required (shape %r)" % (name, nd, a.shape))
+            raise ValueError("recipe %s: a contiguous %d-d array is required (shape %r)" % (nm, nd, a.shape))
     n = sel.shape[0]
-    if n < 1 or src.shape != (n, G):
-        raise ValueError("recipe: sel %r and src %r do not describe a batch of groups of %d" % (sel.shape, src.shape, G))
+    if n < 1 or tail is None or src.shape != (n,) + tail:
+        raise ValueError("recipe: sel %r and %s %r do not describe a batch of groups of %s"
+                         % (sel.shape, name, src.shape, "%d" % G if T is None else "%d over %d steps" % (G, T)))
     if int(sel.min()) < 0 or int(sel.max()) >= N:
         raise ValueError("recipe sel: line numbers must lie in [0, %d) (min %d, max %d)" % (N, sel.min(), sel.max()))
     if int(src.min()) < 0 or int(src.max()) >= n:
-        raise ValueError("recipe src: batch positions must lie in [0, %d) (min %d, max %d)" % (n, src.min(), src.max()))
+        raise ValueError("recipe %s: batch positions must lie in [0, %d) (min %d, max %d)"
+                         % (name, n, src.min(), src.max()))
+    return n
+
+
+def check_recipe(sel, src, N, G):
+    """``sel`` int32 ``[n]`` line numbers in ``[0, N)``, ``src`` int32 ``[n, G]`` batch positions in ``[0, n)`` with
+    ``src[:, 0]`` the line itself (the positive row).  Raises TypeError / ValueError; returns ``n``."""
+    n = _check(sel, "src", src, N, 2, (G,), G)
     if not np.array_equal(src[:, 0], np.arange(n, dtype=np.int32)):
         raise ValueError("recipe src: column 0 must be the line itself")
     return n
@@ -52,20 +62,7 @@ def check_position_recipe(sel, psrc, N, G, T):
     """The recipe of a NextItNet training feed (``NextItNetColumnIterator``): ``sel`` int32 ``[n]`` line numbers in
     ``[0, N)``, ``psrc`` int32 ``[n, G - 1, T]`` batch positions in ``[0, n)`` -- the line whose (item, cate) negative row
     ``g + 1`` of line ``i`` carries at step ``t``.  Raises TypeError / ValueError; returns ``n``."""
-    for name, a, nd in (("sel", sel, 1), ("psrc", psrc, 3)):
-        if not isinstance(a, np.ndarray) or a.dtype != np.int32:
-            raise TypeError("recipe %s: an int32 numpy array is required, got %s" % (name, getattr(a, "dtype", type(a))))
-        if a.ndim != nd or not a.flags.c_contiguous:
-            raise ValueError("recipe %s: a contiguous %d-d array is required (shape %r)" % (name, nd, a.shape))
-    n = sel.shape[0]
-    if n < 1 or G < 2 or psrc.shape != (n, G - 1, T):
-        raise ValueError("recipe: sel %r and psrc %r do not describe a batch of groups of %d over %d steps"
-                         % (sel.shape, psrc.shape, G, T))
-    if int(sel.min()) < 0 or int(sel.max()) >= N:
-        raise ValueError("recipe sel: line numbers must lie in [0, %d) (min %d, max %d)" % (N, sel.min(), sel.max()))
-    if int(psrc.min()) < 0 or int(psrc.max()) >= n:
-        raise ValueError("recipe psrc: batch positions must lie in [0, %d) (min %d, max %d)" % (n, psrc.min(), psrc.max()))
-    return n
+    return _check(sel, "psrc", psrc, N, 3, (G - 1, T) if G >= 2 else None, G, T)
 
 
 class ResidentColumns(object):

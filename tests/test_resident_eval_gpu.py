@@ -95,7 +95,7 @@ def _same_feed(got, want, what):
     for k in sorted(public(want)):
         if isinstance(want[k], torch.Tensor):
             assert got[k].dtype == want[k].dtype and got[k].shape == want[k].shape, (what, k)
-            assert got[k].data_ptr() % 16 == 0 and got["_lay"][k] == want["_lay"][k], (what, k)
+            assert got[k].data_ptr() % 16 == 0 and got["_arena"].lay[k] == want["_arena"].lay[k], (what, k)
             assert torch.equal(got[k].view(torch.int32), want[k].view(torch.int32)), (what, k)
         else:
             assert got[k] == want[k], (what, k, got[k], want[k])
