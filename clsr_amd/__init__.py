@@ -16,3 +16,12 @@ if "GPU_MAX_HW_QUEUES" not in os.environ:
                        "take effect (set it in the environment, or import clsr_amd before the first device call); "
                        "the training step runs ~4 % slower with the default of 4 hardware queues")
     os.environ["GPU_MAX_HW_QUEUES"] = "8"
+
+
+def __getattr__(name):
+    # ``from clsr_amd import SASRecModel``: resolved on first use, so that importing the package stays free of torch
+    if name == "SASRecModel":
+        from clsr_amd.clsr import SASRecModel
+
+        return SASRecModel
+    raise AttributeError("module %r has no attribute %r" % (__name__, name))

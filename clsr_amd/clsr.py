@@ -815,6 +815,12 @@ class NextItNetModel(_SiblingModel):
     kind = "nextitnet"
 
 
+class SASRecModel(_SiblingModel):
+    """SASRec, the self-attention baseline of the paper's comparison table (the reference ships none): hparams
+    ``num_blocks``, ``num_heads`` (config/sasrec.yaml); built with ``SequentialIterator``, like GRU4Rec."""
+    kind = "sasrec"
+
+
 class SLI_RECModel(_SiblingModel):
     """Reference ``SLI_RECModel`` (models/sequential/sli_rec.py)."""
     kind = "sli_rec"

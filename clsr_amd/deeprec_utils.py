@@ -193,6 +193,8 @@ _DEFAULTS = [
     ("embed_size", None), ("n_layers", None), ("decay", None), ("eval_epoch", None),
     ("top_k", None), ("counterfactual_recent_k", 5), ("use_complex_attention", False),
     ("sequential_model", "time4lstm"), ("time_unit", "s"), ("ncf_layer_sizes", [80, 40]),
+    # not reference keys (the reference ships no SASRec): blocks and attention heads of SASRecModel (sasrec.yaml)
+    ("num_blocks", None), ("num_heads", None),
 ]
 
 

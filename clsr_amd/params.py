@@ -149,7 +149,7 @@ def init_tensor(kind, shape, hp, gen):
 # (examples/00_quick_start/sequential.py:94-205): they share the embedding layer and the logit MLP of
 # SequentialBaseModel (sequential_base_model.py:55-74,354-452) and differ in _build_seq_graph.
 SIB_TABLES = OrderedDict([("item", EMB + "item_embedding"), ("cate", EMB + "cate_embedding")])
-SIBLINGS = ("gru4rec", "din", "sli_rec", "a2svd", "dien", "caser", "ncf", "nextitnet", "lgn")
+SIBLINGS = ("gru4rec", "din", "sli_rec", "a2svd", "dien", "caser", "ncf", "nextitnet", "lgn", "sasrec")
 # NCF (ncf.py:15-42): four tables of its own beside the trunk's, all [V, user_embedding_dim] -- the item tables too.  The
 # trunk's item / cate tables stay trained tables: the involved-row regulariser reaches them, the data gradient does not.
 NCF_TABLES = OrderedDict([("item", EMB + "item_embedding"), ("cate", EMB + "cate_embedding"),
@@ -201,6 +201,8 @@ def sibling_scopes(kind):
         return dict(gc="sequential/")
     if kind == "nextitnet":    # nextitnet.py:41,127-131: variable_scope("nextitnet") / one scope per residual block
         return dict(nx="sequential/nextitnet/")
+    if kind == "sasrec":       # not a model of the reference: one scope of this project's choosing, outside sequential/embedding
+        return dict(sa="sequential/sasrec/")
     raise ValueError("unknown sibling model %r" % (kind,))
 
 
@@ -256,8 +258,28 @@ def nextitnet_specs(scope, C, hp):
     return specs
 
 
+def sasrec_specs(scope, C, hp):
+    """Variables of the SASRec encoder in creation order (the layout csrc/sasrec.hip addresses by offset): the positional
+    table [max_seq_length, C] like an embedding table (init_method, init_value); per block the two layer norms (gain one,
+    bias zero; not named gamma / beta, which the trunk reads as a batch-norm layer), the four attention matrices and the two
+    feed-forward matrices, all [C, C] = [in, out] (truncated normal, stddev 0.02, as NextItNet's) with zero biases; the final
+    layer norm."""
+    C = int(C)
+    specs = [(scope + "position_embedding", (int(hp.max_seq_length), C), "w")]
+    for l in range(int(hp.num_blocks)):
+        b = scope + "block_%d/" % l
+        specs += [(b + "layer_norm1/gain", (C,), "one"), (b + "layer_norm1/bias", (C,), "zero")]
+        for n in ("query", "key", "value", "output"):
+            specs += [(b + "attention/%s/kernel" % n, (C, C), "tnormal_0.02"), (b + "attention/%s/bias" % n, (C,), "zero")]
+        specs += [(b + "layer_norm2/gain", (C,), "one"), (b + "layer_norm2/bias", (C,), "zero")]
+        for n in ("ffn_1", "ffn_2"):
+            specs += [(b + n + "/kernel", (C, C), "tnormal_0.02"), (b + n + "/bias", (C,), "zero")]
+    return specs + [(scope + "layer_norm_final/gain", (C,), "one"), (scope + "layer_norm_final/bias", (C,), "zero")]
+
+
 def sibling_specs(dims, hp, kind):
-    """Ordered (name, shape, init kind) of every variable of GRU4Rec / DIN / SLi-Rec / A2SVD / DIEN / Caser / NCF / NextItNet."""
+    """Ordered (name, shape, init kind) of every variable of GRU4Rec / DIN / SLi-Rec / A2SVD / DIEN / Caser / NCF / NextItNet /
+    SASRec."""
     Vu, Vi, Vc = dims["Vu"], dims["Vi"], dims["Vc"]
     Di, Dc, Du, H = hp.item_embedding_dim, hp.cate_embedding_dim, hp.user_embedding_dim, hp.hidden_size
     D = Di + Dc
@@ -280,6 +302,9 @@ def sibling_specs(dims, hp, kind):
         out_dim = 2 * (int(hp.n_v) + int(hp.L) * int(hp.n_h)) + D
     elif kind == "nextitnet":
         specs += nextitnet_specs(sc["nx"], D, hp)
+        out_dim = 2 * D
+    elif kind == "sasrec":
+        specs += sasrec_specs(sc["sa"], D, hp)
         out_dim = 2 * D
     elif kind == "dien":
         att = list(hp.att_fcn_layer_sizes)

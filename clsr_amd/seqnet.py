@@ -21,6 +21,11 @@ clip + Adam) and differ in ``_build_seq_graph``:
                                                          conv, 1x1 conv) over the history; trained on EVERY position: the
                                                          logit MLP sees Hn T G rows -- no mask anywhere
 
+  SASRecModel    (no reference file: the paper's baseline)  a learnt position row, then blocks of causal self-attention and a
+                                                         ReLU feed-forward (pre-norm, residual), a final layer norm on the
+                                                         last valid step, ++ target; padding masked everywhere
+                                                         (csrc/sasrec.hip)
+
 ``SeqNet`` re-uses CLSRNet wholesale -- parameter store, packed weights, the position-tiled GEMMs, the fused recurrence
 launch, the attention block (forward and backward), the MLP heads, sorted segmented embedding gradients, regularisers,
 clip, Adam, the stream structure, data parallelism -- and only re-states the three graphs and their backward passes.
@@ -55,7 +60,7 @@ class SeqNet(CLSRNet):
     def __init__(self, hp, dims, kind=None, **kw):
         self.kind = sibling_kind(kind if kind is not None else hp.model_type)
         if self.kind is None:
-            raise ValueError("SeqNet builds gru4rec / din / dien / sli_rec / a2svd / caser / ncf / nextitnet / lgn, got %r"
+            raise ValueError("SeqNet builds gru4rec / din / dien / sli_rec / a2svd / caser / ncf / nextitnet / lgn / sasrec, got %r"
                              % (kind or hp.model_type,))
         self.sc = sibling_scopes(self.kind)
         if self.kind == "caser" and hp.hidden_size is None:
@@ -85,7 +90,13 @@ class SeqNet(CLSRNet):
             # sees values it can unpack
             hp = copy.copy(hp)
             hp.hidden_size, hp.att_fcn_layer_sizes = 0, None       # (attention_size: the trunk never reads it for this kind)
+        if self.kind == "sasrec":
+            # settings the encoder never reads: whatever they hold, the trunk sees values it can unpack
+            hp = copy.copy(hp)
+            hp.hidden_size, hp.att_fcn_layer_sizes = 0, None       # (attention_size: the trunk never reads it for this kind)
         super(SeqNet, self).__init__(hp, dims, **kw)
+        if self.kind == "sasrec":
+            self._sasrec_setup()
         if self.kind == "caser":
             self._caser_setup()
         if self.kind == "nextitnet":
@@ -115,13 +126,16 @@ class SeqNet(CLSRNet):
             bad.append("enable_BN must be True")
         if list(hp.activation) != ["relu"] * len(hp.activation):
             bad.append("activation must be relu")
-        self._check_dropout(hp, bad, mlp_only=self.kind in ("a2svd", "gru4rec", "caser", "nextitnet"))
-        if self.kind in ("caser", "nextitnet") and self.dropout_in_effect(hp):
+        self._check_dropout(hp, bad, mlp_only=self.kind in ("a2svd", "gru4rec", "caser", "nextitnet", "sasrec"))
+        if self.kind in ("caser", "nextitnet", "sasrec") and self.dropout_in_effect(hp):
             # (its one _fcn_net is the logit MLP too: the tail of A2SVD / GRU4Rec would serve; not wired up or tested yet)
             bad.append("user_dropout with dropout %r: dropout in %s's logit MLP is not implemented yet"
-                       % ([float(d) for d in hp.dropout], "Caser" if self.kind == "caser" else "NextItNet"))
+                       % ([float(d) for d in hp.dropout],
+                          {"caser": "Caser", "nextitnet": "NextItNet", "sasrec": "SASRec"}[self.kind]))
         if self.kind == "nextitnet" and self.precision != "fp32":
             bad.append("precision must be 'fp32', got %r (NextItNet's kernels are fp32 FMA chains)" % (self.precision,))
+        if self.kind == "sasrec" and self.precision != "fp32":
+            bad.append("precision must be 'fp32', got %r (SASRec's kernels are fp32 FMA chains)" % (self.precision,))
         if any(float(getattr(hp, k)) != 0.0 for k in ("embed_l1", "layer_l1", "cross_l1", "cross_l2")):
             bad.append("l1 / cross regularisers must be 0")
         if hp.loss != "softmax" or hp.method != "classification":
@@ -143,6 +157,8 @@ class SeqNet(CLSRNet):
             bad += self._caser_limits(hp, bool(bad))
         if self.kind == "nextitnet":
             bad += self._nextitnet_limits(hp)
+        if self.kind == "sasrec":
+            bad += self._sasrec_limits(hp)
         if self.kind in ("a2svd", "sli_rec") and int(hp.attention_size) % 4:
             bad.append("attention_size must be a multiple of 4")
         if bad:
@@ -219,6 +235,53 @@ class SeqNet(CLSRNet):
         self.nx_W, self.nx_dW, self.nx_P = first, self.dense_grad[g0:g0 + o], o
         # (a rate of T or more only ever reads the padding: every such rate computes what T does)
         self.nx_dil = torch.tensor([min(int(d), 1 << 20) for d in hp.dilations], dtype=torch.int32, device=self.device)
+
+    @staticmethod
+    def _sasrec_limits(hp):
+        """SASRec's own keys, by name; the kernels' say on the whole shape (csrc/sasrec.hip) once each key is in range.
+        hidden_size, attention_size, att_fcn_layer_sizes and attention_dropout are never read: any value passes."""
+        bad = []
+        nb, nh = getattr(hp, "num_blocks", None), getattr(hp, "num_heads", None)
+        if nb is None or nh is None:
+            return ["num_blocks and num_heads must be set (sasrec.yaml: num_blocks 2, num_heads 1)"]
+        cmax, nbmax, tmax = (query("clsr_sasrec_max_" + n) for n in ("channels", "blocks", "steps"))
+        is_int = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, bool)
+        if not is_int(nb) or not 1 <= nb <= nbmax:
+            bad.append("num_blocks must lie in 1..%d, got %r" % (nbmax, nb))
+        Di, Dc, T = int(hp.item_embedding_dim), int(hp.cate_embedding_dim), int(hp.max_seq_length)
+        C = Di + Dc
+        if Di <= 0 or Dc <= 0 or C % 8 or C > cmax:
+            bad.append("item_embedding_dim + cate_embedding_dim must be a multiple of 8, at most %d, got %d + %d"
+                       % (cmax, Di, Dc))
+        elif not is_int(nh) or nh < 1 or C % nh or (C // nh) % 4:
+            bad.append("num_heads must divide item_embedding_dim + cate_embedding_dim = %d into heads of a multiple of 4 "
+                       "channels, got %r" % (C, nh))
+        if not bad and 1 <= T <= tmax and not query("clsr_sasrec_supported", T, T, C, int(nb), int(nh)):
+            bad.append("max_seq_length %d with item_embedding_dim + cate_embedding_dim = %d: a history's backward state needs "
+                       "%d bytes of LDS, the budget is %d (160 KB)"
+                       % (T, C, query("clsr_sasrec_lds_bytes", T, C, 1), query("clsr_sasrec_lds_budget_bytes")))
+        return bad
+
+    def _sasrec_setup(self):
+        """SASRec's shape constants and the parameter block the kernels address by offset: the positional table, the
+        variables of all blocks and the final layer norm are consecutive in the dense buffer, in the layout csrc/sasrec.hip
+        states (checked here, once)."""
+        hp = self.hp
+        self.sa_T, self.sa_nb, self.sa_nh = int(hp.max_seq_length), int(hp.num_blocks), int(hp.num_heads)
+        names = [n for n, _, _ in self.specs if n.startswith(self.sc["sa"])]
+        first, o = self.P[names[0]], 0
+        for n in names:
+            if self.P[n].data_ptr() != first.data_ptr() + 4 * o:
+                raise AssertionError("SASRec parameter block is not contiguous at %s" % n)
+            o += self.P[n].numel()
+        if o != query("clsr_sasrec_param_floats", self.sa_T, self.D, self.sa_nb):
+            raise AssertionError("SASRec parameter block: %d floats" % o)
+        if first.data_ptr() % 16:
+            raise AssertionError("SASRec parameter block is not 16-byte aligned")
+        if names[0] != self.sc["sa"] + "position_embedding" or names[-1] != self.sc["sa"] + "layer_norm_final/bias":
+            raise AssertionError("SASRec parameter block runs from %s to %s" % (names[0], names[-1]))
+        g0 = (self.Gd[names[0]].data_ptr() - self.dense_grad.data_ptr()) // 4
+        self.sa_W, self.sa_dW, self.sa_P = first, self.dense_grad[g0:g0 + o], o
 
     @staticmethod
     def _ncf_widths(hp):
@@ -429,7 +492,7 @@ class SeqNet(CLSRNet):
             return 2 * (int(self.hp.n_v) + int(self.hp.L) * int(self.hp.n_h)) + self.D
         if self.kind == "ncf":
             return self.nc_Du + int(self.hp.ncf_layer_sizes[-1])
-        if self.kind == "nextitnet":
+        if self.kind in ("nextitnet", "sasrec"):
             return 2 * self.D
         return {"gru4rec": self.H + self.D, "din": 3 * self.D, "sli_rec": 2 * self.D, "a2svd": 2 * self.D,
                 "dien": 3 * self.D + self.H}[self.kind]
@@ -582,6 +645,18 @@ class SeqNet(CLSRNet):
             call("clsr_copy_cols", pooled, PW2, 0, G, B, PW2, mo, W, 0, 0)
             call("clsr_copy_cols", target, D, 0, 1, B, D, mo, W, PW2, 0)
             out.update(pooled=pooled, argmax_item=am[0], argmax_cate=am[1], ties_item=ti[0], ties_cate=ti[1])
+        elif kind == "sasrec":
+            if T > self.sa_T:
+                raise ValueError("SASRec's positional table holds max_seq_length = %d rows: the feed holds %d steps"
+                                 % (self.sa_T, T))
+            aux()
+            # ONE launch for the whole stack; training saves every block's input and the last valid row, scoring nothing.
+            # s lands in columns 0 .. D of all G rows of its history group
+            saved = self._buf("sa.saved", query("clsr_sasrec_saved_floats", Hn, T, D, self.sa_nb)) if training else None
+            call("clsr_sasrec_fwd", hist, seq_len, ls, Hn, T, self.sa_T, D, self.sa_W, self.sa_nb, self.sa_nh, saved, mo,
+                 W, G)
+            call("clsr_copy_cols", target, D, 0, 1, B, D, mo, W, D, 0)
+            out.update(saved=saved)
         else:
             NX = self.NX
             t = sc["t4"]
@@ -754,6 +829,17 @@ class SeqNet(CLSRNet):
             call("clsr_caser_hconv_bwd", dpool, PW2, out["pooled"], PW2, out["argmax_item"], out["argmax_cate"],
                  out["ties_item"], out["ties_cate"], hist, D, Hn, T, Di, Dc, self.cz_W["item"], self.cz_W["cate"],
                  self.cz_L, self.cz_nv, self.cz_nh, dhist, self.cz_dW["item"], self.cz_dW["cate"], ws)
+            self._dw_flush()
+        elif kind == "sasrec":
+            call("clsr_group_sum_cols", dmo, W, 0, G, Hn, D, dL, D, 0, 1)
+            call("clsr_copy_cols", dmo, W, D, 1, B, D, dtarget, D, 0, 1)
+            shape = (Hn, T, self.sa_T, D, self.sa_nb)
+            parts = query("clsr_sasrec_parts", *shape)
+            ws = self._buf("sa.ws", query("clsr_sasrec_workspace_floats", *shape))
+            # ONE launch: d hist is written (padded steps: 0.0), every dense gradient leaves as a row of sums per workgroup
+            call("clsr_sasrec_bwd", dL, out["saved"], seq_len, ls, Hn, T, self.sa_T, D, self.sa_W, self.sa_nb, self.sa_nh,
+                 dhist, ws)
+            self._rp(ws, parts, self.sa_P, self.sa_P, self.sa_dW)
             self._dw_flush()
         else:
             NX = self.NX

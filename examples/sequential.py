@@ -12,6 +12,7 @@ user of the reference makes is the import root (clsr_amd instead of reco_utils..
     python examples/sequential.py --model CASER ...                        # caser.yaml: L 3, n_v 128, n_h 128
     python examples/sequential.py --model NCF ...                          # ncf.yaml: tower [80, 40] over 40-wide tables
     python examples/sequential.py --model NEXTITNET ...                    # nextitnet.yaml: dilations [1, 2, 4, 1, 2, 4], width 3
+    python examples/sequential.py --model SASREC ...                       # sasrec.yaml: num_blocks 2, num_heads 1
     python examples/sequential.py --model LGN ...                          # lgn.yaml: the graph is built from train_data
 """
 import argparse
@@ -22,7 +23,7 @@ import time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from clsr_amd.clsr import (A2SVDModel, CaserModel, CLSRModel, DIENModel, DINModel, GRU4RecModel,  # noqa: E402
-                           LGNModel, NCFModel, NextItNetModel, SLI_RECModel, latest_checkpoint)  # noqa: E402
+                           LGNModel, NCFModel, NextItNetModel, SASRecModel, SLI_RECModel, latest_checkpoint)  # noqa: E402
 from clsr_amd.deeprec_utils import prepare_hparams  # noqa: E402
 from clsr_amd.sequential_iterator import (NextItNetColumnIterator, NextItNetIterator, SASequentialIterator,  # noqa: E402
                                            SequentialIterator)
@@ -95,7 +96,8 @@ def get_model(flags_obj, model_path, summary_path, user_vocab, item_vocab, cate_
     siblings = {"SLIREC": ("sli_rec.yaml", SLI_RECModel), "GRU4REC": ("gru4rec.yaml", GRU4RecModel),
                 "DIN": ("din.yaml", DINModel), "A2SVD": ("asvd.yaml", A2SVDModel), "DIEN": ("dien.yaml", DIENModel),
                 "CASER": ("caser.yaml", CaserModel), "NCF": ("ncf.yaml", NCFModel),
-                "NEXTITNET": ("nextitnet.yaml", NextItNetModel), "LGN": ("lgn.yaml", LGNModel)}
+                "NEXTITNET": ("nextitnet.yaml", NextItNetModel), "LGN": ("lgn.yaml", LGNModel),
+                "SASREC": ("sasrec.yaml", SASRecModel)}
     if flags_obj.model in siblings:     # reference :94-119, :157-205: same flags, the model's own yaml
         yaml_name, cls = siblings[flags_obj.model]
         extra = dict(manual_alpha=flags_obj.manual_alpha, manual_alpha_value=flags_obj.manual_alpha_value) \
@@ -120,7 +122,7 @@ def get_model(flags_obj, model_path, summary_path, user_vocab, item_vocab, cate_
         return cls(hparams, iterator, seed=None, device=device, dist=dist, shard_eval=flags_obj.shard_eval,
                    resident_data=flags_obj.resident_data, resident_eval=flags_obj.resident_eval)
     if flags_obj.model != "CLSR":
-        raise SystemExit("--model must be CLSR, SLIREC, GRU4REC, DIN, DIEN, A2SVD, CASER, NCF, NEXTITNET or LGN")
+        raise SystemExit("--model must be CLSR, SLIREC, GRU4REC, DIN, DIEN, A2SVD, CASER, NCF, NEXTITNET, LGN or SASREC")
     hparams = prepare_hparams(
         YAML, embed_l2=flags_obj.embed_l2, layer_l2=flags_obj.layer_l2,
         contrastive_loss=flags_obj.contrastive_loss, triplet_margin=flags_obj.triplet_margin,

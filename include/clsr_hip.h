@@ -852,6 +852,41 @@ int clsr_nextitnet_fwd(const float* hist, long Hn, int T, int C, const float* pa
 int clsr_nextitnet_bwd(const float* dout, const float* saved, long Hn, int T, int C, const float* params, int k,
                        int nblocks, const int* dilations, float* dhist, float* partial, void* stream);
 
+/* SASRec (csrc/sasrec.hip): nblocks pre-norm blocks of causal self-attention (nheads heads of dh = C / nheads channels)
+ * and a C -> C -> C ReLU feed-forward over hist [Hn, T, C] (contiguous, left aligned, C = Di + Dc a multiple of 8), a learnt
+ * position row pos[len - 1 - t] added first, a final layer norm on the last valid step; history h has
+ * len = clamp(seq_len[h len_stride], 0, T) valid steps, the others are padding (never a key, zero gradient; len = 0: s = 0).
+ * LN over channels with biased variance and eps 1e-8 inside the root.
+ * params: pos [Tmax][C] | per block  gamma1 | beta1 [C] | Wq [C][C] | bq [C] | Wk | bk | Wv | bv | Wo | bo | gamma2 | beta2 |
+ * W1 [C][C] | b1 | W2 [C][C] | b2 | then gammaf | betaf [C]; matrices are [in][out] (clsr_sasrec_param_floats, no padding).
+ * clsr_sasrec_supported: T <= Tmax <= clsr_sasrec_max_steps() (256), C a multiple of 8 up to clsr_sasrec_max_channels() (64),
+ * nheads divides C with dh a multiple of 4, 1 .. clsr_sasrec_max_blocks() (4) blocks, and the backward's one-history slice
+ * clsr_sasrec_lds_bytes(T, C, 1) = 4 (9 T (C + 1) + T (C / 2 + 1) + 2) within clsr_sasrec_lds_budget_bytes() (160 KB;
+ * scoring: 4 (5 T (C + 1) + 2)).  An unsupported shape: an error from the entry points, nothing written.
+ * clsr_sasrec_fwd: ONE launch for all blocks; a history's activations stay in LDS.  saved (training; NULL: scoring)
+ * [clsr_sasrec_saved_floats] receives every block's input [nblocks][Hn][T][C] (padding rows zero), then x_L[len - 1]
+ * [Hn][C].  out receives s = LNf(x_L[len - 1]): rows h rep + g, g < rep, ldo floats apart, columns 0 .. C.
+ * clsr_sasrec_bwd: ONE launch.  dout [Hn, C] = d s; dhist [Hn, T, C] is WRITTEN (padding rows 0.0); partial
+ * [clsr_sasrec_parts][param floats] receives one row of gradient sums per workgroup in the layout of params (rows of pos
+ * past the longest history: 0.0) -- the caller reduces the rows in ascending order (clsr_reduce_parts_multi).  No atomics:
+ * two runs are bit-identical. */
+int clsr_sasrec_supported(int T, int Tmax, int C, int nblocks, int nheads);
+int clsr_sasrec_max_channels(void);
+int clsr_sasrec_max_blocks(void);
+int clsr_sasrec_max_steps(void);
+int clsr_sasrec_max_parts(void);
+long clsr_sasrec_lds_budget_bytes(void);
+long clsr_sasrec_lds_bytes(int T, int C, int training);
+long clsr_sasrec_param_floats(int Tmax, int C, int nblocks);
+long clsr_sasrec_saved_floats(long Hn, int T, int C, int nblocks);
+int clsr_sasrec_slice(int T, int C, int training);
+int clsr_sasrec_parts(long Hn, int T, int Tmax, int C, int nblocks);
+long clsr_sasrec_workspace_floats(long Hn, int T, int Tmax, int C, int nblocks);
+int clsr_sasrec_fwd(const float* hist, const int* seq_len, int len_stride, long Hn, int T, int Tmax, int C,
+                    const float* params, int nblocks, int nheads, float* saved, float* out, int ldo, int rep, void* stream);
+int clsr_sasrec_bwd(const float* dout, const float* saved, const int* seq_len, int len_stride, long Hn, int T, int Tmax,
+                    int C, const float* params, int nblocks, int nheads, float* dhist, float* partial, void* stream);
+
 /* LGN (models/sequential/lgn.py, csrc/lgn.hip): all N node rows [N, C] (fp32, contiguous, C a multiple of 4 up to
  * clsr_lgn_max_width() = 128) propagated through a CSR matrix (indptr [N + 1], indices, values: int32 / fp32 on the DEVICE,
  * N and the entry count within int32: clsr_lgn_supported), a dense layer fused behind the product.  W [C][C] (in x out) and

@@ -28,7 +28,7 @@ from clsr_amd.synthetic import make_tsv_dataset  # noqa: E402
 
 MODELS = {"clsr": ("CLSRModel", "clsr.yaml", SASequentialIterator), "a2svd": ("A2SVDModel", "asvd.yaml", SequentialIterator),
           "gru4rec": ("GRU4RecModel", "gru4rec.yaml", SequentialIterator), "ncf": ("NCFModel", "ncf.yaml", SequentialIterator),
-          "lgn": ("LGNModel", "lgn.yaml", SequentialIterator),
+          "lgn": ("LGNModel", "lgn.yaml", SequentialIterator), "sasrec": ("SASRecModel", "sasrec.yaml", SequentialIterator),
           # NextItNet: the column iterator (host feeds, or --resident_data) and the literal one (host feeds only; its
           # per-position sampler is a python loop of 0.4 - 0.8 s per batch: --n_train 16384 --regions 3 --epochs 1)
           "nextitnet": ("NextItNetModel", "nextitnet.yaml", NextItNetColumnIterator),
