@@ -745,7 +745,12 @@ class _SiblingModel(SequentialBaseModel):
             raise NotImplementedError("%s: table_dtype=%r is available for CLSRModel only" % (type(self).__name__, self._table_dtype))
         if self._table_master:
             raise NotImplementedError("%s: table_master=True is available for CLSRModel only" % type(self).__name__)
-        return SeqNet(hp, dims, kind=self.kind, device=self._device, seed=self.seed, dedup_histories=self._dedup)
+        return SeqNet(hp, dims, kind=self.kind, device=self._device, seed=self.seed, dedup_histories=self._dedup,
+                      **self._net_keywords())
+
+    def _net_keywords(self):
+        """Keywords of the model's own that its net takes (none but SASRec's)."""
+        return {}
 
     def train(self, sess, feed_dict):
         self._train_step(self._to_arrays(feed_dict, True))
@@ -817,8 +822,19 @@ class NextItNetModel(_SiblingModel):
 
 class SASRecModel(_SiblingModel):
     """SASRec, the self-attention baseline of the paper's comparison table (the reference ships none): hparams
-    ``num_blocks``, ``num_heads`` (config/sasrec.yaml); built with ``SequentialIterator``, like GRU4Rec."""
+    ``num_blocks``, ``num_heads`` (config/sasrec.yaml); built with ``SequentialIterator``, like GRU4Rec.
+
+    ``long_histories=True`` lifts the limit LDS sets on ``max_seq_length`` (105 steps at the yaml's width of 40): shapes the
+    resident kernels refuse run the tiled pair, up to 256 steps; every other shape runs what it runs without the keyword, to
+    the bit.  Variables and checkpoints are the same either way."""
     kind = "sasrec"
+
+    def __init__(self, hparams, iterator_creator, *args, **kw):
+        self._long_histories = bool(kw.pop("long_histories", False))
+        super(SASRecModel, self).__init__(hparams, iterator_creator, *args, **kw)
+
+    def _net_keywords(self):
+        return dict(long_histories=self._long_histories)
 
 
 class SLI_RECModel(_SiblingModel):

@@ -641,3 +641,506 @@ extern "C" int clsr_sasrec_bwd(const float* dout, const float* saved, const int*
   CLSR_CHECK_LAUNCH();
   return CLSR_OK;
 }
+
+// ================================================================================================ tiled kernels
+// The same encoder for histories whose backward state LDS does not hold (and for any it does): a workgroup owns ONE history
+// at a time and walks its steps in tiles of TE = min(tile, T) rows; thread r of the first TE owns row t0 + r of the tile.
+// k and v of the WHOLE history stay in LDS (two rows per step), every other row exists for one tile only:
+//   forward   LDS: 2 T (C + 1) + 3 TE (C + 1) words (k, v | x, q, o).  One sweep per block, tiles ascending: a tile's keys
+//             0 .. t are in place when its queries attend (causal).  A block's output rows go to the next block's rows of
+//             ``saved`` (training) or to the workgroup's T C floats of the workspace (scoring) and come back tile by tile.
+//   backward  LDS: 2 T (C + 1) + 7 TE (C + 1) + TE (C / 2 + 1) words (k, v | x, xhat2, q, o, the gradient, two scratch rows,
+//             log-sum-exp and sum a da per head).  The gradient w.r.t. a block's output lives in the history's rows of
+//             dhist between tiles.  Two sweeps per block:
+//             the QUERY sweep recomputes a tile (k, v into the resident rows), walks it back to d q, adds d W2 .. d Wq,
+//             and parks per row q | d o | d q Wq^T | log-sum-exp, sum a da in the workgroup's rows of the workspace
+//             (3 C + C / 2 floats a row);
+//             the KEY sweep takes a tile of keys, streams the parked rows of the query tiles i >= j back through the
+//             staging rows (tiles ascending, rows ascending), sums d k and d v into the key tile's own rows, finishes d u,
+//             the first layer norm's backward and d Wk, d Wv, d gamma1, d beta1.
+// Dense gradients: the workgroup zeroes its row of partial sums once, then one owner thread per element adds a tile's rows
+// (ascending) to it, tiles ascending, histories ascending.  No atomics: two runs are bit-identical.
+#define SA_TILE_MAX 64
+
+static inline int sa_tile_rows(int T, int tile) { return tile < T ? tile : T; }
+static inline long sa_tiled_lds_floats(int T, int C, int tile, int training) {
+  return 2L * T * (C + 1) + (long)sa_tile_rows(T, tile) * (training ? 7L * (C + 1) + C / 2 + 1 : 3L * (C + 1));
+}
+// floats of a parked row: q [C] | d o [C] | d q Wq^T [C] | log-sum-exp [nh] | sum a da [nh] (2 nh <= C / 2)
+__host__ __device__ static inline int sa_park_floats(int C) { return 3 * C + C / 2; }
+
+extern "C" long clsr_sasrec_tiled_lds_bytes(int T, int C, int tile, int training) {
+  if (T <= 0 || C <= 0 || tile <= 0) return 0;
+  return 4L * sa_tiled_lds_floats(T, C, tile, training);
+}
+
+extern "C" int clsr_sasrec_tiled_supported(int T, int Tmax, int C, int nblocks, int nheads, int tile) {
+  if (!sa_dims_ok(T, C) || Tmax < T || Tmax > SA_MAX_T) return 0;
+  if (nblocks < 1 || nblocks > SA_MAX_BLOCKS || nheads < 1 || C % nheads || (C / nheads) % 4) return 0;
+  if (tile < 1 || tile > SA_TILE_MAX) return 0;
+  return clsr_sasrec_tiled_lds_bytes(T, C, tile, 1) <= clsr_sasrec_lds_budget_bytes();
+}
+
+// the tile the host passes: the largest the budget holds, at most SA_TILE_MAX (0: none fits)
+extern "C" int clsr_sasrec_tiled_default_tile(int T, int C) {
+  if (!sa_dims_ok(T, C)) return 0;
+  for (int tile = SA_TILE_MAX; tile >= 1; --tile)
+    if (clsr_sasrec_tiled_lds_bytes(T, C, tile, 1) <= clsr_sasrec_lds_budget_bytes()) return tile;
+  return 0;
+}
+
+// workgroups of both launches = rows of partial sums = sets of parked rows
+extern "C" int clsr_sasrec_tiled_parts(long Hn, int T, int Tmax, int C, int nblocks) {
+  if (Hn <= 0 || !clsr_sasrec_tiled_supported(T, Tmax, C, nblocks, 1, 1)) return 0;
+  long parts = Hn < SA_MAX_PARTS ? Hn : SA_MAX_PARTS;
+  const long cap = SA_WS_FLOATS / (clsr_sasrec_param_floats(Tmax, C, nblocks) + (long)T * sa_park_floats(C));
+  if (parts > cap) parts = cap;
+  return parts < 1 ? 1 : (int)parts;
+}
+
+// training: [parts][param floats] partial sums, then [parts][T][3 C + C / 2] parked rows; scoring: [parts][T][C] rows of x
+extern "C" long clsr_sasrec_tiled_workspace_floats(long Hn, int T, int Tmax, int C, int nblocks, int tile, int training) {
+  if (!clsr_sasrec_tiled_supported(T, Tmax, C, nblocks, 1, tile)) return 0;
+  const long parts = clsr_sasrec_tiled_parts(Hn, T, Tmax, C, nblocks);
+  return parts * (training ? clsr_sasrec_param_floats(Tmax, C, nblocks) + (long)T * sa_park_floats(C) : (long)T * C);
+}
+
+__device__ __forceinline__ int sa_len(const int* __restrict__ seq_len, int len_stride, long h, int T) {
+  const int n = seq_len[h * len_stride];
+  return n < 0 ? 0 : (n > T ? T : n);
+}
+
+// ------------------------------------------------------------------------------------------------ tiled forward
+// xs: the workgroup's [T][C] rows of x between blocks (scoring; training keeps them in saved)
+__global__ void __launch_bounds__(SA_THREADS) sa_tiled_fwd_kernel(const float* __restrict__ hist,
+                                                                  const int* __restrict__ seq_len, int len_stride, long Hn,
+                                                                  int T, int C, const float* __restrict__ params, int Tmax,
+                                                                  int nb, int nh, float* saved, float* __restrict__ out,
+                                                                  int ldo, int rep, int TE, float* ws) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const int tid = threadIdx.x, LX = C + 1, dh = C / nh;
+  float* K = lds;
+  float* V = K + T * LX;
+  float* X = V + T * LX;
+  float* Q = X + TE * LX;
+  float* O = Q + TE * LX;
+  const SaOff of = sa_offsets(C);
+  const long PB = sa_block_floats(C), TC = (long)T * C;
+  const float* __restrict__ pos = params;
+  const float* __restrict__ blocks = params + (long)Tmax * C;
+  const float* __restrict__ fin = blocks + nb * PB;
+  const float scale = 1.0f / sqrtf((float)dh);
+  float* xs = saved ? nullptr : ws + (long)blockIdx.x * TC;
+  for (long h = blockIdx.x; h < Hn; h += gridDim.x) {
+    const int len = sa_len(seq_len, len_stride, h, T);
+    const float* __restrict__ src = hist + h * TC;
+    if (saved)      // the rows of padding of every block's input
+      for (int l = 0; l < nb; ++l)
+        for (long e = (long)len * C + tid; e < TC; e += SA_THREADS) saved[((long)l * Hn + h) * TC + e] = 0.f;
+    if (len == 0) {
+      for (int c = tid; c < C; c += SA_THREADS) {
+        if (saved) saved[(long)nb * Hn * TC + h * C + c] = 0.f;
+        for (int g = 0; g < rep; ++g) out[(h * rep + g) * ldo + c] = 0.f;
+      }
+      continue;
+    }
+    const int ntv = (len + TE - 1) / TE;
+    for (int l = 0; l < nb; ++l) {
+      const float* __restrict__ p = blocks + l * PB;
+      const float* xin = saved ? saved + ((long)l * Hn + h) * TC : xs;
+      float* xout = l + 1 < nb ? (saved ? saved + ((long)(l + 1) * Hn + h) * TC : xs) : nullptr;
+      for (int j = 0; j < ntv; ++j) {
+        const int t0 = j * TE, nr = min(TE, len - t0);
+        __syncthreads();
+        for (int e = tid; e < nr * C; e += SA_THREADS) {
+          const int r = e / C, c = e - r * C, tt = t0 + r;
+          float v;
+          if (l == 0) {
+            v = src[tt * C + c] + pos[(len - 1 - tt) * C + c];
+            if (saved) saved[h * TC + tt * C + c] = v;
+          } else {
+            v = xin[tt * C + c];
+          }
+          X[r * LX + c] = v;
+        }
+        __syncthreads();
+        const bool active = tid < nr;
+        const int row = active ? tid : 0, t = t0 + row;
+        float* xr = X + row * LX;
+        float* qr = Q + row * LX;
+        float* orow = O + row * LX;
+        if (active) {
+          float mean, rstd;
+          sa_stats(xr, C, mean, rstd);
+          sa_qkv(xr, mean, rstd, orow, p, of, C, qr, K + t * LX, V + t * LX);
+        }
+        __syncthreads();
+        if (active) {
+          sa_attend(qr, K, V, LX, t, nh, dh, scale, orow, nullptr);
+          for (int o = 0; o < C; o += 4) {
+            f32x4 acc = ld4(p + of.bo + o);
+            sa_axpy4(orow, p + of.Wo + o, C, C, acc);
+            xr[o] += acc.x, xr[o + 1] += acc.y, xr[o + 2] += acc.z, xr[o + 3] += acc.w;
+          }
+          float mean, rstd;
+          sa_stats(xr, C, mean, rstd);
+          for (int c = 0; c < C; ++c) orow[c] = (xr[c] - mean) * rstd;
+          for (int o = 0; o < C; o += 4) {
+            f32x4 acc = ld4(p + of.b1 + o);
+            sa_axpy4_ln(orow, p + of.g2, p + of.be2, p + of.W1 + o, C, C, acc);
+            qr[o] = sa_relu(acc.x), qr[o + 1] = sa_relu(acc.y), qr[o + 2] = sa_relu(acc.z), qr[o + 3] = sa_relu(acc.w);
+          }
+          for (int o = 0; o < C; o += 4) {
+            f32x4 acc = ld4(p + of.b2 + o);
+            sa_axpy4(qr, p + of.W2 + o, C, C, acc);
+            xr[o] += acc.x, xr[o + 1] += acc.y, xr[o + 2] += acc.z, xr[o + 3] += acc.w;
+          }
+          // ---- s = LNf(x_L[len - 1]), once per row of the history group
+          if (l == nb - 1 && t == len - 1) {
+            float mf, rf;
+            sa_stats(xr, C, mf, rf);
+            if (saved)
+              for (int c = 0; c < C; ++c) saved[(long)nb * Hn * TC + h * C + c] = xr[c];
+            for (int c = 0; c < C; ++c) {
+              const float v = fmaf(fin[c], (xr[c] - mf) * rf, fin[C + c]);
+              for (int g = 0; g < rep; ++g) out[(h * rep + g) * ldo + c] = v;
+            }
+          }
+        }
+        if (xout) {
+          __syncthreads();
+          for (int e = tid; e < nr * C; e += SA_THREADS) {
+            const int r = e / C, c = e - r * C;
+            xout[(t0 + r) * C + c] = X[r * LX + c];
+          }
+        }
+      }
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------------ tiled backward
+// gp[e] += sum over the tile's rows r < nr of A(r, e / C) * Bm[r][e % C] (one owner thread per element, rows ascending; LN as
+// in sa_dw); then the column sums of Bm are added to gb (NULL: none)
+template <bool LN>
+__device__ __forceinline__ void sa_dw_add(const float* Am, const float* Bm, const float* __restrict__ g,
+                                          const float* __restrict__ b, int LX, int C, int nr, float* gp, float* gb) {
+  for (int e = threadIdx.x; e < C * C; e += SA_THREADS) {
+    const int i = e / C, o = e - i * C;
+    const float gi = LN ? g[i] : 1.f, bi = LN ? b[i] : 0.f;
+    float s = 0.f;
+    for (int r = 0; r < nr; ++r) s = fmaf(LN ? fmaf(gi, Am[r * LX + i], bi) : Am[r * LX + i], Bm[r * LX + o], s);
+    gp[e] += s;
+  }
+  if (gb)
+    for (int o = threadIdx.x; o < C; o += SA_THREADS) {
+      float s = 0.f;
+      for (int r = 0; r < nr; ++r) s += Bm[r * LX + o];
+      gb[o] += s;
+    }
+}
+
+// d gamma[c] += sum_r Dm[r][c] * Xh[r][c], d beta[c] += sum_r Dm[r][c] over the tile's rows
+__device__ __forceinline__ void sa_dln_add(const float* Dm, const float* Xh, int LX, int C, int nr, float* gg, float* gb) {
+  for (int c = threadIdx.x; c < C; c += SA_THREADS) {
+    float sg = 0.f, sb = 0.f;
+    for (int r = 0; r < nr; ++r) {
+      const float d = Dm[r * LX + c];
+      sg = fmaf(d, Xh[r * LX + c], sg);
+      sb += d;
+    }
+    gg[c] += sg;
+    gb[c] += sb;
+  }
+}
+
+__global__ void __launch_bounds__(SA_THREADS) sa_tiled_bwd_kernel(const float* __restrict__ dout,
+                                                                  const float* __restrict__ saved,
+                                                                  const int* __restrict__ seq_len, int len_stride, long Hn,
+                                                                  int T, int C, const float* __restrict__ params, int Tmax,
+                                                                  int nb, int nh, float* dhist, float* partial, int TE,
+                                                                  float* parked) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const int tid = threadIdx.x, LX = C + 1, LS = C / 2 + 1, dh = C / nh, WR = sa_park_floats(C);
+  const int BUF = TE * LX;
+  float* K = lds;             // the whole history
+  float* V = K + T * LX;
+  float* X = V + T * LX;      // the tile: the block's input x_l
+  float* Y = X + BUF;         // xhat2; key sweep: d v
+  float* Q = Y + BUF;         // q; key sweep: the staged q, then d u
+  float* O = Q + BUF;         // o, then d q
+  float* G = O + BUF;         // gradient w.r.t. the block's output, then its input
+  float* T1 = G + BUF;        // d h1, then d o, then xhat1; key sweep: the staged d o, then xhat1
+  float* H1 = T1 + BUF;       // h1, then d w, then d q Wq^T; key sweep: d k
+  float* ST = H1 + BUF;       // per row: log-sum-exp [nh] | sum a da [nh]
+  const SaOff of = sa_offsets(C);
+  const long PB = sa_block_floats(C), TC = (long)T * C;
+  const long P = (long)Tmax * C + nb * PB + 2 * C;
+  const float* __restrict__ blocks = params + (long)Tmax * C;
+  const float* __restrict__ fin = blocks + nb * PB;
+  const float scale = 1.0f / sqrtf((float)dh);
+  float* part = partial + (long)blockIdx.x * P;
+  float* part_blocks = part + (long)Tmax * C;
+  float* part_fin = part_blocks + nb * PB;
+  float* park = parked + (long)blockIdx.x * T * WR;
+  const float* __restrict__ xlast = saved + (long)nb * Hn * TC;
+  for (long e = tid; e < P; e += SA_THREADS) part[e] = 0.f;
+  for (long h = blockIdx.x; h < Hn; h += gridDim.x) {
+    const int len = sa_len(seq_len, len_stride, h, T);
+    float* dx = dhist + h * TC;     // the history's gradient rows between tiles; d hist at the end
+    __syncthreads();
+    for (long e = tid; e < TC; e += SA_THREADS) dx[e] = 0.f;
+    if (len == 0) continue;
+    // ---- the final layer norm (row len - 1 only): xhatf -> T1, d s -> H1, its backward -> G, in row 0 of the tile
+    if (tid == 0) {
+      const float* __restrict__ xl = xlast + h * C;
+      const float* __restrict__ ds = dout + h * C;
+      for (int c = 0; c < C; ++c) T1[c] = xl[c];
+      float mean, rstd;
+      sa_stats(T1, C, mean, rstd);
+      for (int c = 0; c < C; ++c) T1[c] = (T1[c] - mean) * rstd, H1[c] = ds[c], G[c] = 0.f;
+      sa_ln_bwd(H1, T1, fin, rstd, C, G);
+    }
+    __syncthreads();
+    for (int c = tid; c < C; c += SA_THREADS) {
+      part_fin[c] += H1[c] * T1[c];
+      part_fin[C + c] += H1[c];
+      dx[(long)(len - 1) * C + c] = G[c];
+    }
+    const int ntv = (len + TE - 1) / TE;
+    for (int l = nb - 1; l >= 0; --l) {
+      const float* __restrict__ p = blocks + l * PB;
+      float* gp = part_blocks + l * PB;
+      const float* __restrict__ xsrc = saved + ((long)l * Hn + h) * TC;
+      // ================================================================ the query sweep
+      for (int j = 0; j < ntv; ++j) {
+        const int t0 = j * TE, nr = min(TE, len - t0);
+        __syncthreads();
+        for (int e = tid; e < nr * C; e += SA_THREADS) {
+          const int r = e / C, c = e - r * C;
+          X[r * LX + c] = xsrc[(t0 + r) * C + c];
+          G[r * LX + c] = dx[(t0 + r) * C + c];
+        }
+        __syncthreads();
+        const bool active = tid < nr;
+        const int row = active ? tid : 0, t = t0 + row;
+        float* xr = X + row * LX;
+        float* yr = Y + row * LX;
+        float* qr = Q + row * LX;
+        float* kr = K + t * LX;
+        float* vr = V + t * LX;
+        float* orow = O + row * LX;
+        float* gr = G + row * LX;
+        float* t1 = T1 + row * LX;
+        float* h1 = H1 + row * LX;
+        float* st = ST + row * LS;
+        // ---- the block again: q, k, v
+        float mean1 = 0.f, rstd1 = 0.f, rstd2 = 0.f;
+        if (active) {
+          sa_stats(xr, C, mean1, rstd1);
+          sa_qkv(xr, mean1, rstd1, orow, p, of, C, qr, kr, vr);
+        }
+        __syncthreads();
+        // ---- o and the log-sum-exp, xhat2 -> Y, h1 -> H1, then d h1 = gate (G . W2^T) -> T1
+        if (active) {
+          sa_attend(qr, K, V, LX, t, nh, dh, scale, orow, st);
+          for (int o = 0; o < C; o += 4) {
+            f32x4 acc = ld4(p + of.bo + o);
+            sa_axpy4(orow, p + of.Wo + o, C, C, acc);
+            yr[o] = xr[o] + acc.x, yr[o + 1] = xr[o + 1] + acc.y, yr[o + 2] = xr[o + 2] + acc.z, yr[o + 3] = xr[o + 3] + acc.w;
+          }
+          float mean2;
+          sa_stats(yr, C, mean2, rstd2);
+          for (int c = 0; c < C; ++c) yr[c] = (yr[c] - mean2) * rstd2;
+          for (int o = 0; o < C; o += 4) {
+            f32x4 acc = ld4(p + of.b1 + o);
+            sa_axpy4_ln(yr, p + of.g2, p + of.be2, p + of.W1 + o, C, C, acc);
+            h1[o] = sa_relu(acc.x), h1[o + 1] = sa_relu(acc.y), h1[o + 2] = sa_relu(acc.z), h1[o + 3] = sa_relu(acc.w);
+          }
+          for (int jj = 0; jj < C; jj += 4) {
+            f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+            sa_dot4(gr, p + of.W2 + jj * C, C, C, acc);
+            t1[jj] = h1[jj] > 0.f ? acc.x : 0.f, t1[jj + 1] = h1[jj + 1] > 0.f ? acc.y : 0.f;
+            t1[jj + 2] = h1[jj + 2] > 0.f ? acc.z : 0.f, t1[jj + 3] = h1[jj + 3] > 0.f ? acc.w : 0.f;
+          }
+        }
+        __syncthreads();
+        // ---- d W2, d b2, d W1, d b1
+        sa_dw_add<false>(H1, G, nullptr, nullptr, LX, C, nr, gp + of.W2, gp + of.b2);
+        sa_dw_add<true>(Y, T1, p + of.g2, p + of.be2, LX, C, nr, gp + of.W1, gp + of.b1);
+        __syncthreads();
+        // ---- d w = d h1 . W1^T -> H1; G += LN2 backward: G is d y; d o = d y . Wo^T -> T1; sum a da per head = d o . o
+        if (active) {
+          for (int c = 0; c < C; c += 4) {
+            f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+            sa_dot4(t1, p + of.W1 + c * C, C, C, acc);
+            h1[c] = acc.x, h1[c + 1] = acc.y, h1[c + 2] = acc.z, h1[c + 3] = acc.w;
+          }
+          sa_ln_bwd(h1, yr, p + of.g2, rstd2, C, gr);
+          for (int c = 0; c < C; c += 4) {
+            f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+            sa_dot4(gr, p + of.Wo + c * C, C, C, acc);
+            t1[c] = acc.x, t1[c + 1] = acc.y, t1[c + 2] = acc.z, t1[c + 3] = acc.w;
+          }
+          for (int hd = 0; hd < nh; ++hd) st[nh + hd] = sa_dot(t1 + hd * dh, orow + hd * dh, dh);
+        }
+        __syncthreads();
+        // ---- d gamma2, d beta2, d Wo, d bo
+        sa_dln_add(H1, Y, LX, C, nr, gp + of.g2, gp + of.be2);
+        sa_dw_add<false>(O, G, nullptr, nullptr, LX, C, nr, gp + of.Wo, gp + of.bo);
+        __syncthreads();
+        // ---- d q -> O by the query's thread over its keys; the row is parked for the key sweep; d q Wq^T -> H1 and parked;
+        // xhat1 -> T1
+        if (active) {
+          float* pk = park + (long)t * WR;
+          for (int hd = 0; hd < nh; ++hd) {
+            const int c0 = hd * dh;
+            const float lse = st[hd], dl = st[nh + hd];
+            for (int d = 0; d < dh; ++d) orow[c0 + d] = 0.f;
+            for (int s = 0; s <= t; ++s) {
+              const float* ks = K + s * LX + c0;
+              const float a = expf(sa_dot(qr + c0, ks, dh) * scale - lse);
+              const float dz = a * (sa_dot(t1 + c0, V + s * LX + c0, dh) - dl) * scale;
+              for (int d = 0; d < dh; ++d) orow[c0 + d] = fmaf(dz, ks[d], orow[c0 + d]);
+            }
+            pk[3 * C + hd] = lse, pk[3 * C + nh + hd] = dl;
+          }
+          for (int c = 0; c < C; ++c) pk[c] = qr[c], pk[C + c] = t1[c];
+          for (int c = 0; c < C; c += 4) {
+            f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+            sa_dot4(orow, p + of.Wq + c * C, C, C, acc);
+            pk[2 * C + c] = acc.x, pk[2 * C + c + 1] = acc.y, pk[2 * C + c + 2] = acc.z, pk[2 * C + c + 3] = acc.w;
+          }
+          for (int c = 0; c < C; ++c) t1[c] = (xr[c] - mean1) * rstd1;
+        }
+        __syncthreads();
+        // ---- d Wq, d bq; the gradient rows (d y) go back
+        sa_dw_add<true>(T1, O, p + of.g1, p + of.be1, LX, C, nr, gp + of.Wq, gp + of.bq);
+        for (int e = tid; e < nr * C; e += SA_THREADS) {
+          const int r = e / C, c = e - r * C;
+          dx[(t0 + r) * C + c] = G[r * LX + c];
+        }
+      }
+      // ================================================================ the key sweep
+      for (int j = 0; j < ntv; ++j) {
+        const int t0 = j * TE, nr = min(TE, len - t0);
+        __syncthreads();
+        for (int e = tid; e < nr * C; e += SA_THREADS) {
+          const int r = e / C, c = e - r * C;
+          X[r * LX + c] = xsrc[(t0 + r) * C + c];
+          G[r * LX + c] = dx[(t0 + r) * C + c];
+        }
+        const bool active = tid < nr;
+        const int row = active ? tid : 0, t = t0 + row;
+        float* xr = X + row * LX;
+        float* yr = Y + row * LX;
+        float* qr = Q + row * LX;
+        const float* kr = K + t * LX;
+        const float* vr = V + t * LX;
+        float* gr = G + row * LX;
+        float* t1 = T1 + row * LX;
+        float* h1 = H1 + row * LX;
+        if (active)
+          for (int c = 0; c < C; ++c) h1[c] = 0.f, yr[c] = 0.f;
+        // ---- d k -> H1 and d v -> Y by the key's thread over the queries t' >= t, a staged tile of parked rows at a time
+        for (int i = j; i < ntv; ++i) {
+          const int q0 = i * TE, nq = min(TE, len - q0);
+          __syncthreads();
+          for (int e = tid; e < nq * C; e += SA_THREADS) {
+            const int r = e / C, c = e - r * C;
+            const float* pk = park + (long)(q0 + r) * WR;
+            Q[r * LX + c] = pk[c];
+            T1[r * LX + c] = pk[C + c];
+          }
+          for (int e = tid; e < nq * 2 * nh; e += SA_THREADS) {
+            const int r = e / (2 * nh), k2 = e - r * 2 * nh;
+            ST[r * LS + k2] = park[(long)(q0 + r) * WR + 3 * C + k2];
+          }
+          __syncthreads();
+          if (active)
+            for (int hd = 0; hd < nh; ++hd) {
+              const int c0 = hd * dh;
+              for (int tq = max(t, q0); tq < q0 + nq; ++tq) {
+                const int r = tq - q0;
+                const float* qt = Q + r * LX + c0;
+                const float* dot_ = T1 + r * LX + c0;
+                const float a = expf(sa_dot(qt, kr + c0, dh) * scale - ST[r * LS + hd]);
+                const float dz = a * (sa_dot(dot_, vr + c0, dh) - ST[r * LS + nh + hd]) * scale;
+                for (int d = 0; d < dh; ++d) {
+                  h1[c0 + d] = fmaf(dz, qt[d], h1[c0 + d]);
+                  yr[c0 + d] = fmaf(a, dot_[d], yr[c0 + d]);
+                }
+              }
+            }
+        }
+        __syncthreads();
+        // ---- d u = d q . Wq^T (parked) + d k . Wk^T + d v . Wv^T -> Q; xhat1 -> T1; G += LN1 backward: G is d x_l
+        if (active) {
+          float mean1, rstd1;
+          sa_stats(xr, C, mean1, rstd1);
+          const float* pk = park + (long)t * WR + 2 * C;
+          for (int c = 0; c < C; c += 4) {
+            f32x4 acc = {pk[c], pk[c + 1], pk[c + 2], pk[c + 3]};
+            sa_dot4(h1, p + of.Wk + c * C, C, C, acc);
+            sa_dot4(yr, p + of.Wv + c * C, C, C, acc);
+            qr[c] = acc.x, qr[c + 1] = acc.y, qr[c + 2] = acc.z, qr[c + 3] = acc.w;
+          }
+          for (int c = 0; c < C; ++c) t1[c] = (xr[c] - mean1) * rstd1;
+          sa_ln_bwd(qr, t1, p + of.g1, rstd1, C, gr);
+        }
+        __syncthreads();
+        // ---- d Wk, d bk, d Wv, d bv, d gamma1, d beta1; the gradient rows (d x_l) go back
+        sa_dw_add<true>(T1, H1, p + of.g1, p + of.be1, LX, C, nr, gp + of.Wk, gp + of.bk);
+        sa_dw_add<true>(T1, Y, p + of.g1, p + of.be1, LX, C, nr, gp + of.Wv, gp + of.bv);
+        sa_dln_add(Q, T1, LX, C, nr, gp + of.g1, gp + of.be1);
+        for (int e = tid; e < nr * C; e += SA_THREADS) {
+          const int r = e / C, c = e - r * C;
+          dx[(t0 + r) * C + c] = G[r * LX + c];
+        }
+      }
+    }
+    __syncthreads();
+    // ---- dx is d hist (padding rows zero); d pos[p] += d x_0[len - 1 - p]
+    for (int e = tid; e < len * C; e += SA_THREADS) {
+      const int pp = e / C, c = e - pp * C;
+      part[e] += dx[(long)(len - 1 - pp) * C + c];
+    }
+  }
+}
+
+extern "C" int clsr_sasrec_tiled_fwd(const float* hist, const int* seq_len, int len_stride, long Hn, int T, int Tmax, int C,
+                                     const float* params, int nblocks, int nheads, float* saved, float* out, int ldo,
+                                     int rep, int tile, float* workspace, void* stream) {
+  CLSR_CHECK_ARG(hist && seq_len && params && out && (saved || workspace));
+  CLSR_CHECK_ARG(Hn > 0 && rep >= 1 && ldo >= C && len_stride >= 1);
+  CLSR_CHECK_SUPPORTED(clsr_sasrec_tiled_supported(T, Tmax, C, nblocks, nheads, tile));
+  CLSR_CHECK_SUPPORTED(Hn * T * (long)(rep > nblocks ? rep : nblocks) < (1L << 31) / SA_MAX_C);
+  const size_t shmem = (size_t)sa_tiled_lds_floats(T, C, tile, 0) * sizeof(float);
+  if (shmem > 64 * 1024)
+    CLSR_HIP(hipFuncSetAttribute((const void*)sa_tiled_fwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
+  const int parts = clsr_sasrec_tiled_parts(Hn, T, Tmax, C, nblocks);
+  hipLaunchKernelGGL(sa_tiled_fwd_kernel, dim3((unsigned)parts), dim3(SA_THREADS), shmem, (hipStream_t)stream, hist, seq_len,
+                     len_stride, Hn, T, C, params, Tmax, nblocks, nheads, saved, out, ldo, rep, sa_tile_rows(T, tile),
+                     workspace);
+  CLSR_CHECK_LAUNCH();
+  return CLSR_OK;
+}
+
+extern "C" int clsr_sasrec_tiled_bwd(const float* dout, const float* saved, const int* seq_len, int len_stride, long Hn,
+                                     int T, int Tmax, int C, const float* params, int nblocks, int nheads, float* dhist,
+                                     int tile, float* workspace, void* stream) {
+  CLSR_CHECK_ARG(dout && saved && seq_len && params && dhist && workspace);
+  CLSR_CHECK_ARG(Hn > 0 && len_stride >= 1);
+  CLSR_CHECK_SUPPORTED(clsr_sasrec_tiled_supported(T, Tmax, C, nblocks, nheads, tile));
+  CLSR_CHECK_SUPPORTED(Hn * T * (long)nblocks < (1L << 31) / SA_MAX_C);
+  const size_t shmem = (size_t)sa_tiled_lds_floats(T, C, tile, 1) * sizeof(float);
+  if (shmem > 64 * 1024)
+    CLSR_HIP(hipFuncSetAttribute((const void*)sa_tiled_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
+  const int parts = clsr_sasrec_tiled_parts(Hn, T, Tmax, C, nblocks);
+  float* parked = workspace + (long)parts * clsr_sasrec_param_floats(Tmax, C, nblocks);
+  hipLaunchKernelGGL(sa_tiled_bwd_kernel, dim3((unsigned)parts), dim3(SA_THREADS), shmem, (hipStream_t)stream, dout, saved,
+                     seq_len, len_stride, Hn, T, C, params, Tmax, nblocks, nheads, dhist, workspace, sa_tile_rows(T, tile),
+                     parked);
+  CLSR_CHECK_LAUNCH();
+  return CLSR_OK;
+}

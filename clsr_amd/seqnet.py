@@ -24,7 +24,8 @@ clip + Adam) and differ in ``_build_seq_graph``:
   SASRecModel    (no reference file: the paper's baseline)  a learnt position row, then blocks of causal self-attention and a
                                                          ReLU feed-forward (pre-norm, residual), a final layer norm on the
                                                          last valid step, ++ target; padding masked everywhere
-                                                         (csrc/sasrec.hip)
+                                                         (csrc/sasrec.hip); ``long_histories=True``:
+                                                         histories past what LDS holds run the tiled kernels, up to 256
 
 ``SeqNet`` re-uses CLSRNet wholesale -- parameter store, packed weights, the position-tiled GEMMs, the fused recurrence
 launch, the attention block (forward and backward), the MLP heads, sorted segmented embedding gradients, regularisers,
@@ -76,6 +77,11 @@ class SeqNet(CLSRNet):
             if len(hp.att_fcn_layer_sizes or ()) != 2:
                 hp.att_fcn_layer_sizes = None
         self._lg_graph = kw.pop("graph", None)
+        # SASRec only: histories past what LDS holds run the tiled kernels (csrc/sasrec.hip)
+        self.long_histories = bool(kw.pop("long_histories", False))
+        if self.long_histories and self.kind != "sasrec":
+            raise NotImplementedError("long_histories=True is SASRec's keyword (kind 'sasrec'): %s takes its histories of up "
+                                      "to 256 steps as it is" % self.kind)
         if self.kind == "lgn":
             # settings without effect in LGN's graph (lgn.py never reads them): whatever they hold, the trunk sees values it
             # can unpack and no dropout in an MLP that does not exist (embedding_dropout stays as it is: refused when set)
@@ -158,7 +164,7 @@ class SeqNet(CLSRNet):
         if self.kind == "nextitnet":
             bad += self._nextitnet_limits(hp)
         if self.kind == "sasrec":
-            bad += self._sasrec_limits(hp)
+            bad += self._sasrec_limits(hp, self.long_histories)
         if self.kind in ("a2svd", "sli_rec") and int(hp.attention_size) % 4:
             bad.append("attention_size must be a multiple of 4")
         if bad:
@@ -237,9 +243,10 @@ class SeqNet(CLSRNet):
         self.nx_dil = torch.tensor([min(int(d), 1 << 20) for d in hp.dilations], dtype=torch.int32, device=self.device)
 
     @staticmethod
-    def _sasrec_limits(hp):
+    def _sasrec_limits(hp, long_histories=False):
         """SASRec's own keys, by name; the kernels' say on the whole shape (csrc/sasrec.hip) once each key is in range.
-        hidden_size, attention_size, att_fcn_layer_sizes and attention_dropout are never read: any value passes."""
+        hidden_size, attention_size, att_fcn_layer_sizes and attention_dropout are never read: any value passes.
+        ``long_histories``: a shape the resident kernels refuse passes if the tiled ones hold it under their default tile."""
         bad = []
         nb, nh = getattr(hp, "num_blocks", None), getattr(hp, "num_heads", None)
         if nb is None or nh is None:
@@ -257,9 +264,15 @@ class SeqNet(CLSRNet):
             bad.append("num_heads must divide item_embedding_dim + cate_embedding_dim = %d into heads of a multiple of 4 "
                        "channels, got %r" % (C, nh))
         if not bad and 1 <= T <= tmax and not query("clsr_sasrec_supported", T, T, C, int(nb), int(nh)):
-            bad.append("max_seq_length %d with item_embedding_dim + cate_embedding_dim = %d: a history's backward state needs "
-                       "%d bytes of LDS, the budget is %d (160 KB)"
-                       % (T, C, query("clsr_sasrec_lds_bytes", T, C, 1), query("clsr_sasrec_lds_budget_bytes")))
+            if not long_histories:
+                bad.append("max_seq_length %d with item_embedding_dim + cate_embedding_dim = %d: a history's backward state "
+                           "needs %d bytes of LDS, the budget is %d (160 KB); long_histories=True lifts this limit (tiled "
+                           "kernels, up to %d steps)"
+                           % (T, C, query("clsr_sasrec_lds_bytes", T, C, 1), query("clsr_sasrec_lds_budget_bytes"), tmax))
+            elif query("clsr_sasrec_tiled_default_tile", T, C) <= 0:
+                bad.append("max_seq_length %d with item_embedding_dim + cate_embedding_dim = %d: k and v of a history and one "
+                           "row of the tiled backward's state need %d bytes of LDS, the budget is %d (160 KB)"
+                           % (T, C, query("clsr_sasrec_tiled_lds_bytes", T, C, 1, 1), query("clsr_sasrec_lds_budget_bytes")))
         return bad
 
     def _sasrec_setup(self):
@@ -282,6 +295,13 @@ class SeqNet(CLSRNet):
             raise AssertionError("SASRec parameter block runs from %s to %s" % (names[0], names[-1]))
         g0 = (self.Gd[names[0]].data_ptr() - self.dense_grad.data_ptr()) // 4
         self.sa_W, self.sa_dW, self.sa_P = first, self.dense_grad[g0:g0 + o], o
+
+    def _sasrec_tile(self, T):
+        """The pair of kernels a feed of T steps runs, forward and backward alike: 0, the resident pair, for every shape it
+        admits (a net built with ``long_histories`` is bit-identical to one without there), else the tiled pair's tile."""
+        if not self.long_histories or query("clsr_sasrec_supported", T, self.sa_T, self.D, self.sa_nb, self.sa_nh):
+            return 0
+        return query("clsr_sasrec_tiled_default_tile", T, self.D)
 
     @staticmethod
     def _ncf_widths(hp):
@@ -653,8 +673,17 @@ class SeqNet(CLSRNet):
             # ONE launch for the whole stack; training saves every block's input and the last valid row, scoring nothing.
             # s lands in columns 0 .. D of all G rows of its history group
             saved = self._buf("sa.saved", query("clsr_sasrec_saved_floats", Hn, T, D, self.sa_nb)) if training else None
-            call("clsr_sasrec_fwd", hist, seq_len, ls, Hn, T, self.sa_T, D, self.sa_W, self.sa_nb, self.sa_nh, saved, mo,
-                 W, G)
+            tile = self._sasrec_tile(T)
+            if tile:
+                # a shape the resident kernels refuse: the tiled pair, its workspace sized for this launch (training: the
+                # backward's partial sums and parked rows, which the backward of this step fetches under the same name)
+                ws = self._buf("sa.tws.train" if training else "sa.tws.score",
+                               query("clsr_sasrec_tiled_workspace_floats", Hn, T, self.sa_T, D, self.sa_nb, tile, int(training)))
+                call("clsr_sasrec_tiled_fwd", hist, seq_len, ls, Hn, T, self.sa_T, D, self.sa_W, self.sa_nb, self.sa_nh, saved,
+                     mo, W, G, tile, ws)
+            else:
+                call("clsr_sasrec_fwd", hist, seq_len, ls, Hn, T, self.sa_T, D, self.sa_W, self.sa_nb, self.sa_nh, saved, mo,
+                     W, G)
             call("clsr_copy_cols", target, D, 0, 1, B, D, mo, W, D, 0)
             out.update(saved=saved)
         else:
@@ -834,11 +863,18 @@ class SeqNet(CLSRNet):
             call("clsr_group_sum_cols", dmo, W, 0, G, Hn, D, dL, D, 0, 1)
             call("clsr_copy_cols", dmo, W, D, 1, B, D, dtarget, D, 0, 1)
             shape = (Hn, T, self.sa_T, D, self.sa_nb)
-            parts = query("clsr_sasrec_parts", *shape)
-            ws = self._buf("sa.ws", query("clsr_sasrec_workspace_floats", *shape))
+            tile = self._sasrec_tile(T)
             # ONE launch: d hist is written (padded steps: 0.0), every dense gradient leaves as a row of sums per workgroup
-            call("clsr_sasrec_bwd", dL, out["saved"], seq_len, ls, Hn, T, self.sa_T, D, self.sa_W, self.sa_nb, self.sa_nh,
-                 dhist, ws)
+            if tile:
+                parts = query("clsr_sasrec_tiled_parts", *shape)
+                ws = self._buf("sa.tws.train", query("clsr_sasrec_tiled_workspace_floats", *(shape + (tile, 1))))
+                call("clsr_sasrec_tiled_bwd", dL, out["saved"], seq_len, ls, Hn, T, self.sa_T, D, self.sa_W, self.sa_nb,
+                     self.sa_nh, dhist, tile, ws)
+            else:
+                parts = query("clsr_sasrec_parts", *shape)
+                ws = self._buf("sa.ws", query("clsr_sasrec_workspace_floats", *shape))
+                call("clsr_sasrec_bwd", dL, out["saved"], seq_len, ls, Hn, T, self.sa_T, D, self.sa_W, self.sa_nb, self.sa_nh,
+                     dhist, ws)
             self._rp(ws, parts, self.sa_P, self.sa_P, self.sa_dW)
             self._dw_flush()
         else:

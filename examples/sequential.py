@@ -13,6 +13,7 @@ user of the reference makes is the import root (clsr_amd instead of reco_utils..
     python examples/sequential.py --model NCF ...                          # ncf.yaml: tower [80, 40] over 40-wide tables
     python examples/sequential.py --model NEXTITNET ...                    # nextitnet.yaml: dilations [1, 2, 4, 1, 2, 4], width 3
     python examples/sequential.py --model SASREC ...                       # sasrec.yaml: num_blocks 2, num_heads 1
+    python examples/sequential.py --dataset kuaishou --model SASREC --long_histories true ...   # 250 steps: the tiled kernels
     python examples/sequential.py --model LGN ...                          # lgn.yaml: the graph is built from train_data
 """
 import argparse
@@ -83,6 +84,9 @@ def get_flags():
     p.add_argument("--resident_eval", type=str2bool, default=False,
                    help="keep the padded columns of every validation / test file in HBM (about N * (16 T + 20) bytes, an "
                         "image of its own) and build the evaluation feeds there; not for NEXTITNET")
+    p.add_argument("--long_histories", type=str2bool, default=False,
+                   help="SASREC only: run histories past what LDS holds (105 steps at the yaml's width of 40; --dataset "
+                        "kuaishou has 250) on the tiled kernels, up to 256 steps")
     return p.parse_args()
 
 
@@ -119,8 +123,11 @@ def get_model(flags_obj, model_path, summary_path, user_vocab, item_vocab, cate_
         iterator = SequentialIterator
         if flags_obj.model == "NEXTITNET":
             iterator = NextItNetColumnIterator if flags_obj.resident_data else NextItNetIterator
+        if flags_obj.long_histories and flags_obj.model != "SASREC":
+            raise SystemExit("--long_histories is SASREC's flag: the other models take histories of up to 256 steps as they are")
+        own = dict(long_histories=True) if flags_obj.long_histories else {}
         return cls(hparams, iterator, seed=None, device=device, dist=dist, shard_eval=flags_obj.shard_eval,
-                   resident_data=flags_obj.resident_data, resident_eval=flags_obj.resident_eval)
+                   resident_data=flags_obj.resident_data, resident_eval=flags_obj.resident_eval, **own)
     if flags_obj.model != "CLSR":
         raise SystemExit("--model must be CLSR, SLIREC, GRU4REC, DIN, DIEN, A2SVD, CASER, NCF, NEXTITNET, LGN or SASREC")
     hparams = prepare_hparams(

@@ -887,6 +887,33 @@ int clsr_sasrec_fwd(const float* hist, const int* seq_len, int len_stride, long 
 int clsr_sasrec_bwd(const float* dout, const float* saved, const int* seq_len, int len_stride, long Hn, int T, int Tmax,
                     int C, const float* params, int nblocks, int nheads, float* dhist, float* partial, void* stream);
 
+/* SASRec, tiled (csrc/sasrec.hip): the same encoder, parameter block, saved layout and conventions of dout / dhist / out /
+ * ldo / rep for histories whose backward state LDS does not hold (and for any it does).  A workgroup owns ONE history at a
+ * time and walks its steps in tiles of t = min(tile, T) rows: k and v of the whole history stay in LDS, every other row
+ * exists for one tile.  clsr_sasrec_tiled_lds_bytes(T, C, tile, 1) = 4 (2 T (C + 1) + t (7 (C + 1) + C / 2 + 1)), scoring
+ * 4 (2 T (C + 1) + 3 t (C + 1)).  clsr_sasrec_tiled_supported: the limits of clsr_sasrec_supported on T, Tmax, C, nblocks and
+ * nheads, tile in 1 .. 64, and the training figure within clsr_sasrec_lds_budget_bytes(); every T <= 256 is admitted at
+ * C <= 40 with clsr_sasrec_tiled_default_tile(T, C): the largest tile the budget holds, at most 64 (0: none fits).
+ * clsr_sasrec_tiled_parts: workgroups of both launches, at most clsr_sasrec_max_parts().  workspace
+ * [clsr_sasrec_tiled_workspace_floats]: training  [parts][param floats] partial sums (reduced by the caller in ascending
+ * order, as for clsr_sasrec_bwd), then [parts][T][3 C + C / 2] rows parked between the backward's two sweeps (q | d o |
+ * d q Wq^T | log-sum-exp and sum a da per head); scoring (saved = NULL)  [parts][T][C] rows of x between blocks.  The training
+ * forward keeps those rows in saved and does not touch the workspace.
+ * clsr_sasrec_tiled_fwd / clsr_sasrec_tiled_bwd: ONE launch each; between tiles the gradient rows of a history live in its
+ * rows of dhist.  No atomics, a fixed order (histories, tiles and rows ascending): two runs are bit-identical.  An
+ * unsupported shape or tile: an error, nothing written. */
+int clsr_sasrec_tiled_supported(int T, int Tmax, int C, int nblocks, int nheads, int tile);
+int clsr_sasrec_tiled_default_tile(int T, int C);
+long clsr_sasrec_tiled_lds_bytes(int T, int C, int tile, int training);
+int clsr_sasrec_tiled_parts(long Hn, int T, int Tmax, int C, int nblocks);
+long clsr_sasrec_tiled_workspace_floats(long Hn, int T, int Tmax, int C, int nblocks, int tile, int training);
+int clsr_sasrec_tiled_fwd(const float* hist, const int* seq_len, int len_stride, long Hn, int T, int Tmax, int C,
+                          const float* params, int nblocks, int nheads, float* saved, float* out, int ldo, int rep, int tile,
+                          float* workspace, void* stream);
+int clsr_sasrec_tiled_bwd(const float* dout, const float* saved, const int* seq_len, int len_stride, long Hn, int T,
+                          int Tmax, int C, const float* params, int nblocks, int nheads, float* dhist, int tile,
+                          float* workspace, void* stream);
+
 /* LGN (models/sequential/lgn.py, csrc/lgn.hip): all N node rows [N, C] (fp32, contiguous, C a multiple of 4 up to
  * clsr_lgn_max_width() = 128) propagated through a CSR matrix (indptr [N + 1], indices, values: int32 / fp32 on the DEVICE,
  * N and the entry count within int32: clsr_lgn_supported), a dense layer fused behind the product.  W [C][C] (in x out) and
