@@ -723,6 +723,32 @@ class SequentialBaseModel(BaseModel):
                     wt.write("\n")
         return self
 
+    def recommend_k_items(self, infile, catalogue, top_k=10, remove_seen=True, outfile=None, chunk=None):
+        """The ``top_k`` best items of ``catalogue`` (:class:`clsr_amd.catalogue.Catalogue`) for every request of
+        ``infile``, selected on the device (clsr_amd/recommend.py, csrc/reco.hip); the name and arguments of the upstream
+        toolkit's ``recommend_k_items(test, top_k, remove_seen)``.
+
+        Every line of ``infile`` that ``predict`` scores is one request, in file order: the line's user, history and
+        timestamp (its label, target item and category are ignored).  Returns ``Recommendations(users [N] int32,
+        items [N, K] int32, scores [N, K] float32)`` (CPU tensors).  ``scores`` are the logits of the scoring pass --
+        ``torch.sigmoid(scores)`` is what ``predict`` writes; ranking on logits keeps the order where the sigmoid
+        saturates.  Row ``n`` holds the K best candidates of request ``n`` in the strict total order "``a`` before ``b``
+        iff ``score_a > score_b``, or the scores compare equal (-0.0 ties with +0.0) and ``item_a < item_b``".  With
+        ``remove_seen`` a candidate whose id occurs in the request's ``item_history`` row as the model is fed it (its last
+        ``max_seq_length`` steps) is skipped.  Slots past the last candidate hold item -1 and score -inf.  Logits are
+        assumed finite; a logit of -0.0 is returned as +0.0.
+
+        ``top_k``: 1 .. 256.  ``outfile``: a TSV of ``user \\t item \\t rank \\t score`` per filled slot, raw strings
+        through the inverse vocabularies, ranks from 1.  ``chunk``: candidates per request and launch (default: planned,
+        ``clsr_amd.recommend.plan``); the result does not depend on it.  Under ``dist`` every rank computes the full
+        result; ``use_graph`` does not capture this path."""
+        from clsr_amd import recommend as R
+
+        reco = R.recommend(self, infile, catalogue, top_k=top_k, remove_seen=remove_seen, chunk=chunk)
+        if outfile is not None:
+            R.write_tsv(outfile, reco, self.iterator.userdict, self.iterator.itemdict)
+        return reco
+
 
 class CLSRModel(SequentialBaseModel):
     """Reference ``CLSRModel`` (clsr.py).  All graph pieces live in :class:`clsr_amd.net.CLSRNet`."""
@@ -818,6 +844,10 @@ class NextItNetModel(_SiblingModel):
     ``NextItNetIterator`` (left-padded histories, a target per position in training feeds) or, for the same feeds from a
     column store and a native sampler, ``NextItNetColumnIterator`` (the one ``resident_data=True`` needs)."""
     kind = "nextitnet"
+
+    def recommend_k_items(self, *args, **kw):
+        raise NotImplementedError("NextItNetModel.recommend_k_items: NextItNet's feeds carry a target per position (left-padded "
+                                  "histories); the compact scoring feed the candidates are filled into has no such layout")
 
 
 class SASRecModel(_SiblingModel):

@@ -87,6 +87,10 @@ def get_flags():
     p.add_argument("--long_histories", type=str2bool, default=False,
                    help="SASREC only: run histories past what LDS holds (105 steps at the yaml's width of 40; --dataset "
                         "kuaishou has 250) on the tiled kernels, up to 256 steps")
+    p.add_argument("--recommend", type=int, default=0, metavar="K",
+                   help="after the test evaluation: the K best items of the catalogue (every item the train, valid and test "
+                        "files name) for every line of the test file, seen items removed, selected on the device and "
+                        "written to recommend.tsv beside the data (user, item, rank, score); not for NEXTITNET")
     return p.parse_args()
 
 
@@ -151,6 +155,15 @@ def get_model(flags_obj, model_path, summary_path, user_vocab, item_vocab, cate_
                      resident_eval=flags_obj.resident_eval)
 
 
+def recommend(model, top_k, files, outfile):
+    """--recommend K: the catalogue from ``files`` (train, valid, test), recommendations for the test file, as a TSV."""
+    from clsr_amd.catalogue import Catalogue
+
+    catalogue = Catalogue.from_files(model, files)
+    reco = model.recommend_k_items(files[-1], catalogue, top_k=top_k, remove_seen=True, outfile=outfile)
+    print("recommend: %d requests x %d candidates, top %d -> %s" % (reco.items.shape[0], len(catalogue), top_k, outfile))
+
+
 def init_data_parallel(flags_obj):
     """One process per GPU (``python -m torch.distributed.run --nproc-per-node N examples/sequential.py ...``):
     RCCL process group, this rank's GPU, and the SAME ``random`` stream on every rank (all ranks iterate the same
@@ -212,6 +225,8 @@ def main():
     if flags_obj.only_test:
         model.load_model(latest_checkpoint(model_path))
         print(model.run_weighted_eval(test_file, num_ngs=flags_obj.test_num_ngs))
+        if flags_obj.recommend:
+            recommend(model, flags_obj.recommend, (train_file, valid_file, test_file), os.path.join(data_path, "recommend.tsv"))
         return
     start_time = time.time()
     model = model.fit(train_file, valid_file, valid_num_ngs=flags_obj.val_num_ngs, eval_metric="wauc")
@@ -224,6 +239,8 @@ def main():
     print(res)
     if flags_obj.write_prediction_to_file:
         model.predict(test_file, output_file)
+    if flags_obj.recommend:
+        recommend(model, flags_obj.recommend, (train_file, valid_file, test_file), os.path.join(data_path, "recommend.tsv"))
 
 
 if __name__ == "__main__":

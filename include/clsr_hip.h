@@ -1349,6 +1349,28 @@ int clsr_feed_same_rows(const void* const* cols_host, long N, const int* keep, l
 int clsr_feed_build_eval(const void* const* cols_host, long N, const int* keep, long n_keep, long k0, long n, int g, int T,
                          int thr, void* const* outs_host, void* stream);
 
+/* ---- recommend_k_items (csrc/reco.hip, clsr_amd/recommend.py): the launches around the scoring pass of a catalogue chunk.
+ *      clsr_reco_fill_candidates: for h < Hn, j < g:  items[h g + j] = c0 + j < M ? cand_items[c0 + j] : 0, cates alike --
+ *        the items / cates tensors of a compact scoring feed (hist_group = g); 1 <= M < 2^31, 0 <= c0 < M, Hn g < 2^31.
+ *      clsr_reco_topk_merge: per history h the first n_valid (1 .. g) candidates of the chunk -- logit / items [Hn g] -- are
+ *        merged into the running list best_score / best_item [Hn, K], kept sorted in the strict total order
+ *          a before b  iff  score_a > score_b, or score_a == score_b (IEEE: -0.0 ties with +0.0) and item_a < item_b.
+ *        first != 0: the list starts as K empty slots (-inf, -1) and best_* are not read.  remove_seen != 0: a candidate
+ *        whose id is one of the T ids at hist_items[h hist_row_stride ..] never enters (padding is id 0, never a candidate).
+ *        Columns j >= n_valid are not read.  Scores are assumed finite; a stored -0.0 score is returned as +0.0.  The
+ *        result is the K best of all (score, item) pairs merged so far: it does not depend on the chunk size, on the order
+ *        of the chunks or on the launch geometry.  One workgroup per history, 33 KB of LDS, no atomics; asynchronous.
+ *      clsr_reco_topk_supported: 1 <= Hn, Hn g < 2^31, 1 <= g <= clsr_reco_max_chunk() (3840: the list and a chunk's
+ *        survivors share 4096 key slots), 1 <= T <= 256, 1 <= K <= clsr_reco_max_k() (256); otherwise -3 from the entry. */
+int clsr_reco_max_chunk(void);
+int clsr_reco_max_k(void);
+int clsr_reco_topk_supported(long Hn, int g, int T, int K);
+int clsr_reco_fill_candidates(const int* cand_items, const int* cand_cates, long M, long c0, int g, long Hn, int* items,
+                              int* cates, void* stream);
+int clsr_reco_topk_merge(const float* logit, const int* items, long Hn, int g, int n_valid, const int* hist_items,
+                         long hist_row_stride, int T, int remove_seen, int K, float* best_score, int* best_item, int first,
+                         void* stream);
+
 #ifdef __cplusplus
 }
 #endif
