@@ -749,6 +749,39 @@ class SequentialBaseModel(BaseModel):
             R.write_tsv(outfile, reco, self.iterator.userdict, self.iterator.itemdict)
         return reco
 
+    def run_catalogue_eval(self, infile, catalogue, ks=(1, 5, 10), remove_seen=True, chunk=None, return_ranks=False):
+        """Unsampled evaluation: the rank of every positive of ``infile`` among ALL items of ``catalogue``
+        (:class:`clsr_amd.catalogue.Catalogue`), counted on the device (clsr_amd/recommend.py, csrc/reco.hip).
+
+        A request is a line of ``infile`` that ``predict`` scores and whose label is 1, in file order; the label-0 lines of
+        its group are ignored.  Its target is the line's own (item, category) pair, scored as ``predict`` scores the line.
+        The candidates are the catalogue's items except the one with the target's id and, with ``remove_seen``, except
+        those whose id occurs in the request's ``item_history`` row as fed (the rule of ``recommend_k_items``); the target
+        itself is never dropped.  ``rank = 1 +`` the number of candidates left that come before the target in the order of
+        ``recommend_k_items`` (higher logit first, equal logits by ascending id, -0.0 ties with +0.0; logits are assumed
+        finite).  It does not depend on ``chunk``.
+
+        Returns a dict: ``hit@k`` (mean of ``rank <= k``) and ``ndcg@k`` (mean of ``1 / log2(1 + rank)`` where ``rank <= k``,
+        else 0) for every ``k`` of ``ks``, ``mean_mrr`` (mean of ``1 / rank``), ``mean_rank``, ``requests`` and
+        ``candidates`` (the catalogue's size) -- float64 on the host from the integer ranks, unrounded.  ``ks``: positive
+        integers, no upper limit (a rank is exact at any depth).  With ``return_ranks``: ``(dict, CatalogueRanks(users [N]
+        int32, items [N] int32, scores [N] float32, ranks [N] int32))``, CPU tensors; ``scores`` are the targets' logits.
+
+        ``chunk``: candidates per request and launch, ``1 .. clsr_reco_max_chunk() - 1`` (default: planned,
+        ``clsr_amd.recommend.plan_ranked``).  A file without a kept positive line is refused.  Under ``dist`` every rank
+        computes the full result; ``use_graph`` does not capture this path."""
+        from clsr_amd import recommend as R
+
+        try:
+            ks = tuple(ks)
+        except TypeError:
+            raise ValueError("ks must be a sequence of positive integers, got %r" % (ks,))
+        if not ks or not all(isinstance(k, (int, np.integer)) and not isinstance(k, bool) and int(k) >= 1 for k in ks):
+            raise ValueError("ks must be a non-empty sequence of positive integers, got %r" % (ks,))
+        ranks = R.rank_targets(self, infile, catalogue, remove_seen=remove_seen, chunk=chunk)
+        res = R.rank_metrics(ranks.ranks.numpy(), [int(k) for k in ks], len(catalogue))
+        return (res, ranks) if return_ranks else res
+
 
 class CLSRModel(SequentialBaseModel):
     """Reference ``CLSRModel`` (clsr.py).  All graph pieces live in :class:`clsr_amd.net.CLSRNet`."""
@@ -848,6 +881,11 @@ class NextItNetModel(_SiblingModel):
     def recommend_k_items(self, *args, **kw):
         raise NotImplementedError("NextItNetModel.recommend_k_items: NextItNet's feeds carry a target per position (left-padded "
                                   "histories); the compact scoring feed the candidates are filled into has no such layout")
+
+    def run_catalogue_eval(self, *args, **kw):
+        raise NotImplementedError("NextItNetModel.run_catalogue_eval: NextItNet's feeds carry a target per position (left-padded "
+                                  "histories); the compact scoring feed the target and the candidates are filled into has no "
+                                  "such layout")
 
 
 class SASRecModel(_SiblingModel):

@@ -121,6 +121,69 @@ __global__ void __launch_bounds__(256) reco_topk_kernel(const float* __restrict_
   }
 }
 
+// ---- rank of one target against the catalogue (clsr_amd/recommend.py: rank_targets).  The rank of an item is a count, not a
+// sort: column 0 of every group holds the request's target (reco_fill_ranked_kernel), re-scored with every chunk by the same
+// launch to the same bits, so the count needs no state about the target, no pre-pass and no order among the chunks.
+// reco_rank_kernel: grid (Hn, slabs), a workgroup per request and slab of RECO_RANK_SLAB candidate columns, a column per
+// thread.  A column 1 .. n_valid counts when its id is not the target's, its key beats the target's and, with remove_seen,
+// its id is none of the T ids of the history row (staged in LDS, read as a broadcast).  Ballot + popcount per wave, four wave
+// counts summed by thread 0, which owns partial[h, slab]: first overwrites it, otherwise it is added to.  No atomics.
+enum { RECO_RANK_SLAB = 256 };
+
+__global__ void __launch_bounds__(256) reco_fill_ranked_kernel(const int* __restrict__ cand_items, const int* __restrict__ cand_cates,
+                                                               long M, long c0, int g, const int* __restrict__ target_items,
+                                                               const int* __restrict__ target_cates, long total,
+                                                               int* __restrict__ items, int* __restrict__ cates) {
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+    const long h = i / g;
+    const int j = (int)(i - h * g);
+    const long c = c0 + j - 1;
+    const bool in = j > 0 && c < M;
+    items[i] = j == 0 ? target_items[h] : in ? cand_items[c] : 0;
+    cates[i] = j == 0 ? target_cates[h] : in ? cand_cates[c] : 0;
+  }
+}
+
+__global__ void __launch_bounds__(256) reco_rank_kernel(const float* __restrict__ logit, const int* __restrict__ items, int g,
+                                                        int n_valid, const int* __restrict__ hist_items, long hist_row_stride,
+                                                        int T, int remove_seen, int* __restrict__ partial,
+                                                        float* __restrict__ target_score, int first) {
+  __shared__ int seen[RECO_MAX_T];
+  __shared__ int wcnt[4];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const long h = blockIdx.x;
+  const int slab = blockIdx.y;
+  int* slot = partial + h * gridDim.y + slab;
+  if (slab * RECO_RANK_SLAB >= n_valid) {     // a slab past the ragged chunk's end (uniform branch): nothing to read
+    if (first && tid == 0) *slot = 0;
+    return;
+  }
+  if (remove_seen)
+    for (int t = tid; t < T; t += 256) seen[t] = hist_items[h * hist_row_stride + t];
+  const float* lg = logit + h * g;
+  const int* it = items + h * g;
+  const float ts = lg[0];
+  const int target = it[0];
+  const reco_key tkey = reco_encode(ts, target);
+  __syncthreads();
+  const int j = 1 + slab * RECO_RANK_SLAB + tid;      // <= g - 1 where it is read: n_valid <= g - 1
+  bool beats = false;
+  if (j <= n_valid) {
+    const int id = it[j];
+    beats = id != target && reco_encode(lg[j], id) > tkey;
+    if (beats && remove_seen)
+      for (int t = 0; t < T; ++t) beats &= seen[t] != id;       // (every lane reads the same word: a broadcast)
+  }
+  const unsigned long long ballot = __ballot(beats);
+  if (lane == 0) wcnt[wave] = __popcll(ballot);
+  __syncthreads();
+  if (tid == 0) {
+    const int n = wcnt[0] + wcnt[1] + wcnt[2] + wcnt[3];
+    *slot = first ? n : *slot + n;
+    if (first && slab == 0) target_score[h] = ts;
+  }
+}
+
 extern "C" int clsr_reco_max_chunk(void) { return RECO_MAX_CHUNK; }
 extern "C" int clsr_reco_max_k(void) { return RECO_MAX_K; }
 
@@ -152,6 +215,42 @@ extern "C" int clsr_reco_topk_merge(const float* logit, const int* items, long H
   CLSR_CHECK_ARG(!remove_seen || (hist_items && hist_row_stride >= T));
   hipLaunchKernelGGL(reco_topk_kernel, dim3((int)Hn), dim3(256), 0, (hipStream_t)stream, logit, items, g, n_valid, hist_items,
                      hist_row_stride, T, remove_seen ? 1 : 0, K, best_score, best_item, first ? 1 : 0);
+  CLSR_CHECK_LAUNCH();
+  return CLSR_OK;
+}
+
+extern "C" int clsr_reco_rank_slab(void) { return RECO_RANK_SLAB; }
+
+extern "C" int clsr_reco_rank_supported(long Hn, int g, int T) {
+  if (!(Hn >= 1 && Hn <= INT_MAX && g >= 2 && T >= 1 && T <= RECO_MAX_T && Hn * (long)g <= INT_MAX)) return 0;
+  const long slabs = ((long)g - 1 + RECO_RANK_SLAB - 1) / RECO_RANK_SLAB;
+  return slabs <= 65535 && Hn * slabs <= INT_MAX;
+}
+
+extern "C" int clsr_reco_fill_ranked(const int* cand_items, const int* cand_cates, long M, long c0, int g, const int* target_items,
+                                     const int* target_cates, long Hn, int* items, int* cates, void* stream) {
+  CLSR_CHECK_ARG(cand_items && cand_cates && target_items && target_cates && items && cates);
+  CLSR_CHECK_ARG(M >= 1 && c0 >= 0 && c0 < M && g >= 2 && Hn >= 1);
+  CLSR_CHECK_SUPPORTED(M <= INT_MAX && Hn * (long)g <= INT_MAX);
+  const long total = Hn * g;
+  long blocks = (total + 255) / 256;
+  if (blocks > RECO_FILL_BLOCKS) blocks = RECO_FILL_BLOCKS;
+  hipLaunchKernelGGL(reco_fill_ranked_kernel, dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, cand_items, cand_cates, M, c0,
+                     g, target_items, target_cates, total, items, cates);
+  CLSR_CHECK_LAUNCH();
+  return CLSR_OK;
+}
+
+extern "C" int clsr_reco_rank_count(const float* logit, const int* items, long Hn, int g, int n_valid, const int* hist_items,
+                                    long hist_row_stride, int T, int remove_seen, int* partial, float* target_score, int first,
+                                    void* stream) {
+  CLSR_CHECK_ARG(logit && items && partial && (!first || target_score));
+  CLSR_CHECK_SUPPORTED(clsr_reco_rank_supported(Hn, g, T));
+  CLSR_CHECK_ARG(n_valid >= 1 && n_valid <= g - 1);
+  CLSR_CHECK_ARG(!remove_seen || (hist_items && hist_row_stride >= T));
+  const int slabs = (g - 1 + RECO_RANK_SLAB - 1) / RECO_RANK_SLAB;
+  hipLaunchKernelGGL(reco_rank_kernel, dim3((int)Hn, slabs), dim3(256), 0, (hipStream_t)stream, logit, items, g, n_valid,
+                     hist_items, hist_row_stride, T, remove_seen ? 1 : 0, partial, target_score, first ? 1 : 0);
   CLSR_CHECK_LAUNCH();
   return CLSR_OK;
 }

@@ -11,6 +11,10 @@ history-level tensors are uploaded once per request batch; per chunk there are t
 
 and one synchronisation per request batch fetches the lists.  No score crosses PCIe and no [requests, catalogue] matrix
 exists.  The encoders run again for every chunk, also for the kinds whose user state does not depend on the target.
+
+``run_catalogue_eval`` (``rank_targets``) runs the same loop to say where a request's true next item lands in that order: the
+feed's group is the target in column 0 plus the chunk's candidates, ``clsr_reco_fill_ranked`` and ``clsr_reco_rank_count``
+take the places of fill and merge, and the rank is one plus a sum of counts -- nothing is sorted.
 """
 import collections
 
@@ -19,9 +23,11 @@ import torch
 
 from clsr_amd import _lib, ops
 
-__all__ = ["Recommendations", "ROW_BUDGET", "plan", "merge_catalogue", "recommend", "write_tsv"]
+__all__ = ["Recommendations", "CatalogueRanks", "ROW_BUDGET", "plan", "plan_ranked", "merge_catalogue", "count_catalogue",
+           "recommend", "rank_targets", "rank_metrics", "write_tsv"]
 
 Recommendations = collections.namedtuple("Recommendations", "users items scores")
+CatalogueRanks = collections.namedtuple("CatalogueRanks", "users items scores ranks")
 
 #: rows (requests x candidates) of one scoring pass: the size ``run_eval`` gathers its chunks to by default -- the
 #: row-level buffers of the attention kinds (T x 80 floats a row) stay at half a gigabyte at T = 50
@@ -108,6 +114,91 @@ def recommend(model, infile, catalogue, top_k=10, remove_seen=True, chunk=None):
             items.append(best_i.cpu())      # the one synchronisation of the request batch
             scores.append(best_s.cpu())
     return Recommendations(users, torch.cat(items), torch.cat(scores))
+
+
+def plan_ranked(n_requests, n_candidates, max_group, row_budget=ROW_BUDGET, chunk=None):
+    """``(n, c)`` for ``rank_targets``: requests per batch and CANDIDATES per chunk; the feed's group is ``c + 1`` (the target
+    rides in column 0).  ``c`` as ``plan`` chooses it with ``max_group - 1`` as the largest chunk -- the group stays within
+    ``max_group`` -- and ``chunk`` pins it (refused by name outside ``1 .. max_group - 1``); then ``n`` from what the budget
+    leaves for groups of ``c + 1``.  Always ``n (c + 1) <= max(row_budget, c + 1)``."""
+    cap = int(max_group) - 1
+    if chunk is not None and not 1 <= int(chunk) <= cap:
+        raise ValueError("chunk must lie in 1 .. %d (clsr_reco_max_chunk() - 1: the target takes one row of the group), got %r"
+                         % (cap, chunk))
+    _, c = plan(n_requests, n_candidates, cap, row_budget, chunk)
+    return max(1, min(int(n_requests), int(row_budget) // (c + 1))), c
+
+
+def count_catalogue(net, f, cand_items, cand_cates, M, g, target_items, target_cates, remove_seen, partial, target_score):
+    """The chunk loop of one request batch of ``rank_targets`` on the current stream: ``f`` is the batch's uploaded compact
+    scoring feed of groups of ``g`` = 1 target + ``g - 1`` candidates; per chunk fill -> ``net.forward(f, False)`` -> count into
+    ``partial`` ``[requests, slabs]`` (the first chunk overwrites it and writes ``target_score``).  Nothing synchronises."""
+    nb, T = f["B"] // g, f["T"]
+    stride = T if f["compact"] else g * T
+    for c0 in range(0, M, g - 1):
+        ops.call("clsr_reco_fill_ranked", cand_items, cand_cates, M, c0, g, target_items, target_cates, nb, f["items"], f["cates"])
+        logit = net.forward(f, False)["logit"]
+        ops.call("clsr_reco_rank_count", logit, f["items"], nb, g, min(g - 1, M - c0), f["item_history"], stride, T,
+                 int(bool(remove_seen)), partial, target_score, int(c0 == 0))
+
+
+def rank_targets(model, infile, catalogue, remove_seen=True, chunk=None):
+    """See ``SequentialBaseModel.run_catalogue_eval``: ``CatalogueRanks(users, items, scores, ranks)`` of the positive lines of
+    ``infile``, CPU tensors."""
+    net, it = model.net, model.iterator
+    catalogue.check_vocabulary(net.dims["Vi"], net.dims["Vc"])
+    cols, keep = it.eval_lines(infile)
+    keep = keep[cols["labels"][keep] == 1]
+    N, M, T = len(keep), len(catalogue), int(cols["item_history"].shape[1])
+    if N == 0:
+        raise ValueError("infile %r holds no kept line with label 1: there is no target to rank" % (infile,))
+    n, c = plan_ranked(N, M, ops.query("clsr_reco_max_chunk"), chunk=chunk)
+    g = c + 1
+    if not ops.query("clsr_reco_rank_supported", n, g, T):
+        raise ValueError("run_catalogue_eval: %d requests x (1 + chunk = %d candidates), histories of %d steps is not a shape "
+                         "clsr_reco_rank_count takes" % (n, c, T))
+    slabs = -(-c // ops.query("clsr_reco_rank_slab"))
+    users = torch.from_numpy(np.ascontiguousarray(cols["users"][keep], dtype=np.int32))
+    items = torch.from_numpy(np.ascontiguousarray(cols["items"][keep], dtype=np.int32))
+    cates = torch.from_numpy(np.ascontiguousarray(cols["cates"][keep], dtype=np.int32))
+    scores, ranks = [], []
+    with model._stream_ctx():
+        cand_items, cand_cates = catalogue.device(net.device)
+        items_d, cates_d = items.to(net.device), cates.to(net.device)
+        for a in range(0, N, n):
+            sel = keep[a:a + n]
+            nb = len(sel)
+            key = ("recommend", nb, T, g)
+            f = model._static[key] = net.upload(_request_feed(cols, sel, g), False, into=model._static.get(key))
+            t_items, t_cates = items_d[a:a + nb], cates_d[a:a + nb]
+            partial = torch.empty(nb, slabs, dtype=torch.int32, device=net.device)
+            t_score = torch.empty(nb, dtype=torch.float32, device=net.device)
+            try:
+                count_catalogue(net, f, cand_items, cand_cates, M, g, t_items, t_cates, remove_seen, partial, t_score)
+            except _lib.ClsrLibraryError as e:
+                if "unsupported shape" not in str(e):
+                    raise
+                raise ValueError("chunk = %d: the scoring pass of %s does not take %d requests in groups of %d (%s)"
+                                 % (c, type(model).__name__, nb, g, e))
+            rank = partial.sum(1, dtype=torch.int32) + 1
+            ranks.append(rank.cpu())        # the one synchronisation of the request batch
+            scores.append(t_score.cpu())
+    return CatalogueRanks(users, items, torch.cat(scores), torch.cat(ranks))
+
+
+def rank_metrics(ranks, ks, n_candidates):
+    """The dict of ``run_catalogue_eval`` from integer ranks, in float64 on the host, unrounded."""
+    r = np.asarray(ranks, dtype=np.float64)
+    res = {}
+    for k in ks:
+        hit = r <= k
+        res["hit@%d" % k] = float(hit.mean())
+        res["ndcg@%d" % k] = float(np.where(hit, 1.0 / np.log2(1.0 + r), 0.0).mean())
+    res["mean_mrr"] = float((1.0 / r).mean())
+    res["mean_rank"] = float(r.mean())
+    res["requests"] = int(r.shape[0])
+    res["candidates"] = int(n_candidates)
+    return res
 
 
 def write_tsv(outfile, reco, userdict, itemdict):

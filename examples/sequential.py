@@ -91,7 +91,22 @@ def get_flags():
                    help="after the test evaluation: the K best items of the catalogue (every item the train, valid and test "
                         "files name) for every line of the test file, seen items removed, selected on the device and "
                         "written to recommend.tsv beside the data (user, item, rank, score); not for NEXTITNET")
+    p.add_argument("--catalogue_eval", type=ks_list, default=(), metavar="K1,K2,...",
+                   help="after the test evaluation: unsampled metrics of the test file -- every positive ranked against the "
+                        "whole catalogue (built as for --recommend), seen items removed: hit@k and ndcg@k for the given k, "
+                        "mean_mrr, mean_rank; counted on the device; not for NEXTITNET")
     return p.parse_args()
+
+
+def ks_list(text):
+    """``"1,5,10"`` -> ``(1, 5, 10)`` (positive integers)."""
+    try:
+        ks = tuple(int(tok) for tok in text.split(","))
+    except ValueError:
+        ks = ()
+    if not ks or min(ks) < 1:
+        raise argparse.ArgumentTypeError("expected positive integers separated by commas, got %r" % text)
+    return ks
 
 
 def get_model(flags_obj, model_path, summary_path, user_vocab, item_vocab, cate_vocab, train_num_ngs, dist=None):
@@ -164,6 +179,13 @@ def recommend(model, top_k, files, outfile):
     print("recommend: %d requests x %d candidates, top %d -> %s" % (reco.items.shape[0], len(catalogue), top_k, outfile))
 
 
+def catalogue_eval(model, ks, files):
+    """--catalogue_eval K1,K2,...: the catalogue from ``files`` (train, valid, test), the test file's positives ranked in it."""
+    from clsr_amd.catalogue import Catalogue
+
+    print(model.run_catalogue_eval(files[-1], Catalogue.from_files(model, files), ks=ks, remove_seen=True))
+
+
 def init_data_parallel(flags_obj):
     """One process per GPU (``python -m torch.distributed.run --nproc-per-node N examples/sequential.py ...``):
     RCCL process group, this rank's GPU, and the SAME ``random`` stream on every rank (all ranks iterate the same
@@ -227,6 +249,8 @@ def main():
         print(model.run_weighted_eval(test_file, num_ngs=flags_obj.test_num_ngs))
         if flags_obj.recommend:
             recommend(model, flags_obj.recommend, (train_file, valid_file, test_file), os.path.join(data_path, "recommend.tsv"))
+        if flags_obj.catalogue_eval:
+            catalogue_eval(model, flags_obj.catalogue_eval, (train_file, valid_file, test_file))
         return
     start_time = time.time()
     model = model.fit(train_file, valid_file, valid_num_ngs=flags_obj.val_num_ngs, eval_metric="wauc")
@@ -241,6 +265,8 @@ def main():
         model.predict(test_file, output_file)
     if flags_obj.recommend:
         recommend(model, flags_obj.recommend, (train_file, valid_file, test_file), os.path.join(data_path, "recommend.tsv"))
+    if flags_obj.catalogue_eval:
+        catalogue_eval(model, flags_obj.catalogue_eval, (train_file, valid_file, test_file))
 
 
 if __name__ == "__main__":

@@ -1371,6 +1371,29 @@ int clsr_reco_topk_merge(const float* logit, const int* items, long Hn, int g, i
                          long hist_row_stride, int T, int remove_seen, int K, float* best_score, int* best_item, int first,
                          void* stream);
 
+/* ---- run_catalogue_eval (csrc/reco.hip, clsr_amd/recommend.py: rank_targets): the rank of every request's target in the order
+ *      above, as a count.  The feed's group is one target + the chunk's candidates:
+ *      clsr_reco_fill_ranked: for h < Hn:  items[h g] = target_items[h];  for 1 <= j < g:  items[h g + j] = c0 + j - 1 < M ?
+ *        cand_items[c0 + j - 1] : 0;  cates alike.  g >= 2, 1 <= M < 2^31, 0 <= c0 < M, Hn g < 2^31.
+ *      clsr_reco_rank_count: per request h the target is (logit[h g], items[h g]); a column j in 1 .. n_valid (n_valid in
+ *        1 .. g - 1) counts one when items[h g + j] differs from the target's id, its (score, id) comes before the target's
+ *        in the order and -- remove_seen != 0 -- its id is none of the T ids hist_items[h hist_row_stride .. + T].  The
+ *        launch grid is (Hn, slabs), slabs = ceil((g - 1) / clsr_reco_rank_slab()); workgroup (h, s) counts the columns
+ *        1 + s W .. (s + 1) W and owns partial[h slabs + s] (int32): first != 0 overwrites the slot (every slot, also one
+ *        whose slab lies past n_valid) and writes target_score[h] = logit[h g] (its stored bits); otherwise the count is
+ *        added and target_score is not touched.  Columns j > n_valid are not read.  No atomics; asynchronous.  The rank of
+ *        request h is 1 + the sum of its slots after all chunks: it does not depend on the chunk size, the order of the
+ *        chunks or the launch geometry.
+ *      clsr_reco_rank_supported: 1 <= Hn, g >= 2, Hn g < 2^31, 1 <= T <= 256, slabs <= 65535, Hn slabs < 2^31; otherwise
+ *        -3 from clsr_reco_rank_count. */
+int clsr_reco_rank_slab(void);
+int clsr_reco_rank_supported(long Hn, int g, int T);
+int clsr_reco_fill_ranked(const int* cand_items, const int* cand_cates, long M, long c0, int g, const int* target_items,
+                          const int* target_cates, long Hn, int* items, int* cates, void* stream);
+int clsr_reco_rank_count(const float* logit, const int* items, long Hn, int g, int n_valid, const int* hist_items,
+                         long hist_row_stride, int T, int remove_seen, int* partial, float* target_score, int first,
+                         void* stream);
+
 #ifdef __cplusplus
 }
 #endif
